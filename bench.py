@@ -9,11 +9,17 @@ registration pairs/sec; default workload = configs[1], one 3DMatch-shape fragmen
 
 A step registers `--pairs-per-step` device-resident synthetic pairs on every rank through ONE set of stacked launches
 per stage.  Pairs are sharded over the ranks with no data-path collective; one all_gather of the poses ends the timed
-region (barrier + synchronize on both sides, max over ranks).  Rank 0 prints ONE JSON line: whole-job pairs/s, the
-`roofline` object of the dominant hand-written kernel (k_cyl_net_wg; HIP events on its launch stream inside the library),
-`roofline_other` for every other kernel SURVEY 8(d) assigns a roofline class to, and, at N=1, `cpu_baseline`: the
+region (barrier + synchronize on both sides, max over ranks).  Rank 0 prints ONE JSON line: whole-job pairs/s and the
+`roofline` object of the dominant hand-written kernel (k_cyl_net_wg; HIP events on its launch stream inside the library).
+A plain run does nothing else.  With `--full` the line also carries what takes runs of its own: `roofline_other` for every
+other kernel SURVEY 8(d) assigns a roofline class to (a characterisation pass after the timed region), the single-caller
+latencies, the second timed region on the split-f16 CNN kernels (`*_split`) and, at N=1, `cpu_baseline`: the
 reference's cpp_wrappers cores (oracle/_ref) + the torch-CPU restatement of the model timed on this box's host cores on
 the SAME pair at the SAME keypoint count (no extrapolation).
+
+`--dump-outputs DIR` writes what the timed path returned in its last step (pair / kitti: the poses of that step's pairs,
+stream: the poses of the whole stream) as DIR/poses.npy, float32.  The inputs are seeded: the same arguments give the same
+inputs on every run, so two builds can be compared output for output.
 
 Other workloads (each prints its own line with the same metric; they are not the headline):
   --workload stream   BASELINE configs[2]: 1623 synthetic pairs from RAW clouds, pre-processing included, with DGR recall + RR
@@ -97,7 +103,24 @@ def parse():
                     help='pair workload, STRONG scaling: this many pairs per step for the whole job, pair i of a step on rank i mod N '
                          '(default: --pairs-per-step on every rank = weak scaling)')
     ap.add_argument('--detail-json', default=None, help='also write the uncompacted record (full roofline_other entries) to this file')
+    ap.add_argument('--full', action='store_true',
+                    help='pair / kitti: also the kernel characterisation pass (roofline_other), the single-caller latencies, the split-f16 '
+                         'timed region and the CPU baseline with its parity record (off: the headline only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the outputs of the last timed step to DIR/<name>.npy (pair / kitti / stream)')
     return ap.parse_args()
+
+
+def dump_outputs(d, arrays):
+    """{name: array} -> d/<name>.npy in float32 (float64 stays float64); at most 64 MB in all."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        x = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+        total += x.nbytes
+        assert total <= 64 << 20, f'--dump-outputs: {total} bytes exceed 64 MB'
+        np.save(os.path.join(d, name + '.npy'), x)
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -351,6 +374,18 @@ def dgr_ok(poses, gts, rre_deg=15.0):
     return ok
 
 
+def last_step_poses(mine, gathered, steps, pps, world, total_pairs=None):
+    """The poses of the last timed step of the whole job [pairs, 4, 4]: rank 0's own without a gather; otherwise every rank's
+    last-step rows (step-major in each rank's block), ranks one after the other (weak scaling) or back in the job's pair order
+    i -> rank i mod N (strong scaling)."""
+    if not gathered:
+        return mine[mine.shape[0] - pps:]
+    if total_pairs is None:
+        return torch.cat([g[(steps - 1) * pps:steps * pps] for g in gathered])
+    n = [len(range(r, total_pairs, world)) for r in range(world)]
+    return torch.stack([gathered[i % world][(steps - 1) * n[i % world] + i // world] for i in range(total_pairs)])
+
+
 # ------------------------------------------------------------------------------------------------ main
 def _make_sample(job):
     kind, seed = job
@@ -363,7 +398,8 @@ def make_samples(kind, seeds):
     (33 pairs took ~35 s of the untimed set-up when made one after the other)."""
     import multiprocessing as mp
     jobs = [(kind, s) for s in seeds]
-    workers = max(1, min(len(jobs), len(os.sched_getaffinity(0)), 32))      # (N > 1: the affinity is this rank's share, dist.pin_rank)
+    # (N > 1: the affinity is this rank's share, dist.pin_rank); at most 16: a shared host can show far more cores than a job may use
+    workers = max(1, min(len(jobs), len(os.sched_getaffinity(0)), 16))
     # Under a profiler (rocprofv3 preloads its tool library, which initialises the GPU runtime before main) a forked child inherits a
     # half-initialised runtime and its signal handlers: a worker can hang in the tool's finaliser when the pool is torn down (one
     # profiled run of round 4 sat there for an hour).  No forks then: the samples are made one after the other.
@@ -458,6 +494,8 @@ def main():
     if a.workload == 'stream':
         return run_stream(a, rank, world, dev, cdev, dist, L)
     if a.workload == 'surface':
+        if a.dump_outputs:
+            raise SystemExit('--dump-outputs applies to the pair, kitti and stream workloads (surface times single operator calls)')
         if world != 1:
             raise SystemExit('--workload surface measures one caller on one GPU: run it with --gpus 1')
         return run_surface(a, dev, L)
@@ -566,13 +604,16 @@ def main():
 
     all_poses, mine, gathered, elapsed, timed = timed_region(pipe, a.warmup)
     per_rank_main = list(per_rank)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {'poses': last_step_poses(mine, gathered, a.steps, pps, world, a.total_pairs if strong else None)})
+    # Everything below up to the JSON line, apart from the pose check of the timed steps, is --full only.
     # Kernel characterisation pass (NOT timed, rank 0): two steps one after the other on one stream, so that every kernel of
     # `roofline_other` is measured alone on the chip.  In the pipelined timed region the short keypoint-stage kernels of step i+1
     # share the chip with the CNN kernels of step i: their event spans there measure the contention, not the kernel.
     timed_alone = timed
     latency = {}
     pf_bytes = None
-    if rank == 0 and pool is None and not a.no_pipeline and pps:
+    if a.full and rank == 0 and pool is None and not a.no_pipeline and pps:
         from buffer_amd import ops as _ops
         _ops.PF_BYTES[0] = 0.0
         L.buf_timing_enable(1)
@@ -582,7 +623,7 @@ def main():
         L.buf_timing_enable(0)
         timed_alone = collect_timed(L)
         pf_bytes = _ops.PF_BYTES[0]                   # bytes of the VN gather's hoisted-form table (written + re-read) over those two steps
-    if rank == 0 and pps and not os.environ.get('BUF_NO_TRAFFIC'):      # (not in the PMC-profiled runs: full-step launches only there)
+    if a.full and rank == 0 and pps and not os.environ.get('BUF_NO_TRAFFIC'):      # (not in the PMC-profiled runs: full-step launches only there)
         # what ONE caller of models/BUFFER.py:231-333 sees: one pair, un-batched, un-pipelined, host clock around a synchronised
         # call (median of 10); and the keypoint stage alone (pyramid, point learner, FPS), for one pair and for a whole step
         def med(fn, n=10):
@@ -613,7 +654,7 @@ def main():
 
     # second timed region: the SAME steps with the opt-in fp32-equivalent split-f16 CNN kernels (cnn_arith='split')
     split = None
-    if not a.no_split and a.arith == 'f32':
+    if a.full and not a.no_split and a.arith == 'f32':
         pipe_s = BufferPipeline(replace(cfg, cnn_arith='split'), dev, limits=limits)
         poses_s, mine_s, _, elapsed_s, timed_s = timed_region(pipe_s, 1)
         pipe_s.desc.fused.check_range()
@@ -647,7 +688,9 @@ def main():
         if a.arith == 'split':
             main_roof = roofline_split(timed, pmc, units, None)
         units['patches_per_select'] = 2 * keypts * per_launch
-        _, other = rooflines(timed_alone, pmc, fps_bytes, units, int(L.buf_version()))     # the others: each kernel alone on the chip
+        other = []
+        if a.full:
+            _, other = rooflines(timed_alone, pmc, fps_bytes, units, int(L.buf_version()))     # the others: each kernel alone on the chip
         for e in other:
             # A4: the hoisted form of the four resnet blocks writes PF = [Wf f | Wd f] once per support row and reads it back (a deliberate trade
             # that halved the kernel's time, csrc/vn.hip): its traffic is judged against algorithmic + PF bytes
@@ -674,7 +717,7 @@ def main():
                        'gathered_poses': [int(g.shape[0]) for g in gathered] if gathered else None,
                        'setup_s': round(setup_s, 1), 'per_rank': per_rank_main},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             def hip_register(perms, seed):
                 return pipe.register(inputs[0], seed=seed, perms=[torch.from_numpy(p).to(dev) for p in perms], detail=True)
             hip_register_split = None
@@ -683,7 +726,9 @@ def main():
                     return pipe_s.register(inputs[0], seed=seed, perms=[torch.from_numpy(p).to(dev) for p in perms], detail=True)
             out['cpu_baseline'] = cpu_baseline(samples[0], cfg, limits, hip_register, hip_register_split)
         out['roofline'] = main_roof
-        detail = dict(out, roofline_other=other, timed_kernel_ms_per_step={k: v[1] / alone_steps for k, v in timed_alone.items() if v[0]})
+        detail = dict(out, timed_kernel_ms_per_step={k: v[1] / alone_steps for k, v in timed_alone.items() if v[0]})
+        if a.full:
+            detail['roofline_other'] = other
         if split:
             out['roofline_split'] = roofline_split(split['timed'], pmc, units, split['err'])
             out['value_split'] = pairs / split['elapsed']
@@ -694,7 +739,8 @@ def main():
             detail.update({k: out[k] for k in ('roofline_split', 'value_split', 'ms_per_step_split', 'split')})
         # compact tail (the driver keeps the last 2000 characters of the line): every other kernel as {kernel, bound, frac, avg_us,
         # traffic_ratio = PMC HBM bytes / algorithmic bytes}, measured alone on the chip in 2 un-pipelined steps after the timed region
-        out['roofline_other'] = [compact(e) for e in other]
+        if a.full:
+            out['roofline_other'] = [compact(e) for e in other]
         out.update(latency)
         detail.update(latency)
         if a.detail_json:
@@ -1027,6 +1073,8 @@ def run_stream(a, rank, world, dev, cdev, dist, L):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if rank == 0:
+        if a.dump_outputs:                              # the stream is one step: every pair's pose, in pair order
+            dump_outputs(a.dump_outputs, {'poses': all_poses})
         if gt is None:
             meta = [{'relt_pose': m['relt_pose'], 'overlap_pts': m['overlap_pts']} for m in mine]
         else:

@@ -1,10 +1,12 @@
-"""bench.py's one-line JSON contract (metric, whole-job value, roofline and cpu_baseline objects) on short runs, and the
-N > 1 launch path: two ranks on ONE device over gloo (BENCH_BACKEND=gloo) -- the only multi-rank form a 1-GPU box can run."""
+"""bench.py's one-line JSON contract (metric, whole-job value, roofline and, with --full, cpu_baseline objects) on short runs, the
+plain run (the headline only, --dump-outputs) and the N > 1 launch path: two ranks on ONE device over gloo (BENCH_BACKEND=gloo) --
+the only multi-rank form a 1-GPU box can run."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +22,7 @@ def _run(args, env=None, timeout=1200):
 
 def test_bench_json_line(dev, tmp_path):
     detail = str(tmp_path / 'detail.json')
-    d = _run(['--steps', '2', '--warmup', '1', '--pairs-per-step', '4', '--keypts', '600', '--detail-json', detail])
+    d = _run(['--steps', '2', '--warmup', '1', '--pairs-per-step', '4', '--keypts', '600', '--detail-json', detail, '--full'])
     assert d['metric'] == 'registration pairs/sec' and d['unit'] == 'pairs/s' and d['higher_is_better'] is True
     assert d['n_gpus'] == 1 and d['steps'] == 2 and d['warmup'] == 1 and d['scaling'] == 'weak'
     assert d['dtype'] == 'f32' and d['data'] == 'synthetic' and d['vs_baseline'] is None
@@ -81,6 +83,38 @@ def test_bench_json_line(dev, tmp_path):
     assert vox['bound'] == 'valu' and vox['instr_current'] is True, 'profiles/instr.json is stale: re-run tools/profile_round.sh (make_instr.py)'
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(dev, tmp_path):
+    """Without --full: the headline keys and the dominant kernel's roofline, nothing that takes runs of its own; --dump-outputs writes
+    the poses of the last timed step.  16 distinct pairs, 4 per step: the warm-up step registers pairs 0-3, the timed steps 4-7,
+    8-11 and 12-15, so the dump must hold the poses of pairs 12-15 (synth.make_pair(2012 .. 2015)) in that order."""
+    from buffer_amd import synth
+    out = tmp_path / 'out'
+    steps, warmup, pps, distinct = 3, 1, 4, 16
+    d = _run(['--steps', str(steps), '--warmup', str(warmup), '--pairs-per-step', str(pps), '--distinct-pairs', str(distinct),
+              '--keypts', '600', '--dump-outputs', str(out)])
+    assert d['metric'] == 'registration pairs/sec' and d['unit'] == 'pairs/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert d['steps'] == 3 and d['warmup'] == 1 and abs(d['value'] - 4 * 3 / (d['ms_per_step'] * 3e-3)) < 1e-6 * d['value']
+    assert d['roofline']['launches'] == 3 and d['config']['registered_ok'].startswith('12/12')
+    for k in ('cpu_baseline', 'roofline_other', 'roofline_split', 'value_split', 'split', 'single_pair_latency_ms', 'keypoint_stage_ms'):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ['poses.npy']
+    poses = np.load(out / 'poses.npy')
+    assert poses.shape == (4, 4, 4) and poses.dtype == np.float32 and np.isfinite(poses).all()
+    R = poses[:, :3, :3].astype(np.float64)
+    assert np.abs(R @ R.transpose(0, 2, 1) - np.eye(3)).max() < 1e-3                 # rigid poses
+    # each pose registers its own pair of the last step (bench.py's criterion: RTE < 0.3 m and RRE < 15 deg) and no pair of the
+    # first timed step
+    def ok(T, gt):
+        rte = np.linalg.norm(T[:3, 3] - gt[:3, 3])
+        rre = np.degrees(np.arccos(np.clip((np.trace(T[:3, :3].T @ gt[:3, :3]) - 1) / 2, -1, 1)))
+        return rte < 0.3 and rre < 15.0
+    gts = {k: synth.make_pair(2000 + k)['relt_pose'] for k in range(warmup * pps, distinct)}
+    last = [((warmup + steps - 1) * pps + j) % distinct for j in range(pps)]
+    for j, k in enumerate(last):
+        assert ok(poses[j].astype(np.float64), gts[k]), f'dumped pose {j} does not register pair {k}'
+    assert not any(ok(poses[j].astype(np.float64), gts[warmup * pps + j]) for j in range(pps)), 'the dump holds the first timed step'
+
+
 def test_bench_surface_workload_line(dev, tmp_path):
     """--workload surface: the drop-in mode measured -- every operator of the reference's import surface through the shim packages in
     the reference's call order (7 batch_query + 2 subsample_batch with numpy in / out, 2 FPS + 4 gathers, ball_query + grouping for the
@@ -110,7 +144,7 @@ def test_bench_surface_workload_line(dev, tmp_path):
 
 def test_bench_strong_scaling_mode_two_ranks_over_gloo(dev):
     """--total-pairs: the job's pairs of a step are fixed and dealt i -> rank i mod N (5 pairs on 2 ranks: 3 + 2)."""
-    d = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--total-pairs', '5', '--keypts', '400', '--no-cpu-baseline', '--no-split'],
+    d = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--total-pairs', '5', '--keypts', '400', '--no-cpu-baseline', '--no-split', '--full'],
              env={'BENCH_BACKEND': 'gloo'})
     assert d['n_gpus'] == 2 and d['scaling'] == 'strong' and d['config']['pairs_per_step_job'] == 5
     assert abs(d['value'] - 2 * 5 / (d['ms_per_step'] * 2e-3)) < 1e-6 * d['value']
@@ -119,7 +153,7 @@ def test_bench_strong_scaling_mode_two_ranks_over_gloo(dev):
 
 def test_bench_two_ranks_on_one_device_over_gloo(dev):
     """`python bench.py --gpus 2` with no launcher: bench.py starts torch.distributed.run itself; both ranks share cuda:0."""
-    d = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--pairs-per-step', '3', '--keypts', '400', '--no-cpu-baseline', '--no-split'],
+    d = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--pairs-per-step', '3', '--keypts', '400', '--no-cpu-baseline', '--no-split', '--full'],
              env={'BENCH_BACKEND': 'gloo'})
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak' and 'cpu_baseline' not in d
     assert d['config']['parallelism'] == 'pair-sharded x2' and d['config']['gathered_poses'] == [6, 6]     # steps x pairs, per rank
@@ -143,7 +177,7 @@ def test_bench_refuses_a_world_size_mismatch():
 
 def test_bench_kitti_and_stream_workloads(dev):
     k = _run(['--workload', 'kitti', '--steps', '1', '--warmup', '1', '--pairs-per-step', '2', '--keypts', '300', '--no-cpu-baseline',
-              '--distinct-pairs', '2'])
+              '--distinct-pairs', '2', '--full'])
     assert 'configs[3]' in k['config']['workload'] and k['value'] > 0 and k['config']['sds_points'][0] > 3000
     s = _run(['--workload', 'stream', '--stream-pairs', '24', '--pairs-per-step', '8', '--keypts', '600'])
     assert 'configs[2]' in s['config']['workload'] and s['quality']['pairs'] == 24 and len(s['quality']['per_scene']) == 8

@@ -442,3 +442,26 @@ def test_traffic_summary_keeps_full_step_launches_only(tmp_path):
     assert k['launches_profiled'] == 5 and k['launches_dropped'] == 1
     assert abs(k['hbm_bytes_per_unit'] - (2 * 14.0 + 17.5) * 1024) < 1e-6          # not diluted by the probe launch
     assert t['k_cost_net']['launches_profiled'] == 3 and t['k_cost_net']['launches_dropped'] == 0
+
+
+def test_bench_last_step_poses_follow_the_job_s_pair_order():
+    """bench.py --dump-outputs: the last timed step of the job out of rank 0's rows or the gathered (padded) rank blocks."""
+    sys.path.insert(0, ROOT)
+    from bench import last_step_poses
+
+    def pose(step, pair):                                  # a 4 x 4 block that names its step and its pair of the job
+        return torch.full((4, 4), 100.0 * step + pair)
+
+    steps, world = 3, 2
+    mine = torch.stack([pose(s, j) for s in range(steps) for j in range(4)])
+    assert torch.equal(last_step_poses(mine, None, steps, 4, 1), torch.stack([pose(2, j) for j in range(4)]))
+    # weak scaling: every rank its own 4 pairs per step (pairs 4r .. 4r + 3 of the job)
+    g = [torch.stack([pose(s, 4 * r + j) for s in range(steps) for j in range(4)]) for r in range(world)]
+    assert torch.equal(last_step_poses(g[0], g, steps, 4, world), torch.stack([pose(2, i) for i in range(8)]))
+    # strong scaling: 5 pairs per step dealt i -> rank i mod 2 (3 + 2), blocks padded to 3 rows per step
+    total = 5
+    g = []
+    for r in range(world):
+        rows = [pose(s, i) for s in range(steps) for i in range(r, total, world)]
+        g.append(torch.cat([torch.stack(rows), torch.zeros((steps * 3 - len(rows), 4, 4))]))
+    assert torch.equal(last_step_poses(g[0], g, steps, 3, world, total), torch.stack([pose(2, i) for i in range(total)]))
