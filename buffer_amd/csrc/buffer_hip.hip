@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include "core.hip"
 #include "radius.hip"
+#include "icp.hip"
 #include "subsample.hip"
 #include "pointops.hip"
 #include "vn.hip"

@@ -1,0 +1,469 @@
+// ICP, point-to-point and point-to-plane, for B pairs per call (open3d registration_icp with
+// TransformationEstimationPointToPoint / TransformationEstimationPointToPlane; the point-to-point loop is the one of
+// buffer_amd/icp.py::icp_point_to_point, the point-to-plane step is open3d's, restated, unpinned).
+//
+// Set-up (once per call):
+//   buf_grid_build   one A2 cell grid over all targets, one element per pair, radius = max_dist
+//   k_icp_setup      one workgroup per pair: T <- T_init, anchor = T_init * (source centroid), state cleared
+// Rounds (two launches each, no host wait between rounds):
+//   k_icp_correspond one workgroup per tile of ICP_TILE source points of one pair (tile -> pair through the tile prefix
+//                    offsets).  Per point: p = T s in fp64, rounded to fp32 for the search, nearest target point of the
+//                    pair's grid element by the minimum 64-bit key (fp32 d2 bits, global index) with buf_grid_query's d2
+//                    arithmetic and strict d2 < r2 (= column 0 of the distance-sorted query row; no sort, no row cap),
+//                    non-finite points skipped.  The point's fp64 terms are summed inside the wave (xor butterfly) and
+//                    across the 4 waves through LDS in a fixed order; the tile writes ONE record to the slab.
+//   k_icp_update     one wave per pair: the pair's records summed in a fixed order, fitness / rmse, the state machine of
+//                    icp_point_to_point, the fp64 update (Kabsch with the det correction, or the 6x6 Cholesky solve) and
+//                    T <- dT T.
+// No float atomics: a pair's tiles hold its own points only and every sum has a fixed order, so a pair's result does not
+// depend on the other pairs of the batch and two runs give the same bits.  Finished pairs are skipped by both kernels.
+// Host round trips: one int (the number of active pairs) is read back after every 8th round, so a call makes at most
+// ceil((max_iteration + 1) / 8) small readbacks and no per-pair synchronisation.
+#include "common.h"
+
+#define ICP_TILE 256
+#define ICP_WAVES (ICP_TILE / WAVE)
+#define ICP_P2P BUF_ICP_POINT_TO_POINT
+#define ICP_P2L BUF_ICP_POINT_TO_PLANE
+
+// record values: [0] matches, [1] sum d2, then
+//   point-to-point: sum P (3), sum Q (3), sum P Q^T (9, row-major) with P = p - a, Q = q - a (a = the pair's anchor)
+//   point-to-plane: upper triangle of J^T J (21, row by row), J^T r (6); J = [p x n, n], r = (p - q) . n
+template <int M> struct IcpRec { static constexpr int NV = M == ICP_P2P ? 17 : 29; static constexpr int STRIDE = M == ICP_P2P ? 18 : 30; };
+
+struct IcpState {
+    double anchor[3];
+    double prev_fit, prev_rmse;
+    int done;
+    int pad;
+};
+
+// sum of v over the ICP_TILE threads of the workgroup; the result lands in out[0..NV) (threads 0..NV-1 store it)
+template <int NV>
+__device__ __forceinline__ void icp_block_sum(double (&v)[NV], double (*part)[NV], double* __restrict__ out)
+{
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+#pragma unroll
+    for (int k = 0; k < NV; k++)
+        for (int d = WAVE / 2; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) part[w][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        double s = part[0][threadIdx.x];
+        for (int j = 1; j < ICP_WAVES; j++) s += part[j][threadIdx.x];
+        out[threadIdx.x] = s;
+    }
+}
+
+__global__ void __launch_bounds__(ICP_TILE) k_icp_setup(const float* __restrict__ src, const int* __restrict__ src_off,
+                                                      const double* __restrict__ T_init, double* __restrict__ T,
+                                                      double* __restrict__ fitness, double* __restrict__ rmse, int* __restrict__ iters,
+                                                      IcpState* __restrict__ st)
+{
+    __shared__ double part[ICP_WAVES][3];
+    __shared__ double cen[3];
+    const int b = blockIdx.x, lo = src_off[b], n = src_off[b + 1] - lo;
+    double v[3] = { 0.0, 0.0, 0.0 };
+    for (int i = threadIdx.x; i < n; i += ICP_TILE) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) v[c] += (double)src[3 * (size_t)(lo + i) + c];
+    }
+    icp_block_sum<3>(v, part, cen);
+    __syncthreads();
+    const double* Ti = T_init + 16 * (size_t)b;
+    if (threadIdx.x < 16) T[16 * (size_t)b + threadIdx.x] = Ti[threadIdx.x];
+    if (threadIdx.x == 0) {
+        IcpState s;
+        const double cx = n > 0 ? cen[0] / n : 0.0, cy = n > 0 ? cen[1] / n : 0.0, cz = n > 0 ? cen[2] / n : 0.0;
+        for (int r = 0; r < 3; r++) {
+            const double a = ((Ti[4 * r] * cx + Ti[4 * r + 1] * cy) + Ti[4 * r + 2] * cz) + Ti[4 * r + 3];
+            s.anchor[r] = a == a && fabs(a) < 1e300 ? a : 0.0;            // (a non-finite centroid: NaN rows in the source)
+        }
+        s.prev_fit = 0.0; s.prev_rmse = 0.0; s.done = 0; s.pad = 0;
+        st[b] = s;
+        fitness[b] = 0.0; rmse[b] = 0.0; iters[b] = 0;
+    }
+}
+
+template <int M>
+__global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __restrict__ grids, const int* __restrict__ table,
+                                                           const float4* __restrict__ sorted, const float* __restrict__ src,
+                                                           const int* __restrict__ src_off, const int* __restrict__ tile_off, int npairs,
+                                                           const float* __restrict__ tgt, const float* __restrict__ tgt_normals, int nt,
+                                                           float r2, const double* __restrict__ T, const IcpState* __restrict__ st,
+                                                           int* __restrict__ nn_out, double* __restrict__ slab)
+{
+    constexpr int NV = IcpRec<M>::NV;
+    __shared__ double part[ICP_WAVES][NV];
+    const int tile = blockIdx.x;
+    const int b = find_elem(tile_off, npairs, tile);                       // uniform: a tile holds points of one pair
+    if (st[b].done) return;
+    const int lo = src_off[b], n = src_off[b + 1] - lo;
+    const int li = (tile - tile_off[b]) * ICP_TILE + threadIdx.x;
+    double v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) v[k] = 0.0;
+    if (li < n) {
+        const size_t i = (size_t)(lo + li);
+        const double* Tb = T + 16 * (size_t)b;
+        const double sx = src[3 * i], sy = src[3 * i + 1], sz = src[3 * i + 2];
+        const double px = ((Tb[0] * sx + Tb[1] * sy) + Tb[2] * sz) + Tb[3];
+        const double py = ((Tb[4] * sx + Tb[5] * sy) + Tb[6] * sz) + Tb[7];
+        const double pz = ((Tb[8] * sx + Tb[9] * sy) + Tb[10] * sz) + Tb[11];
+        const float qx = (float)px, qy = (float)py, qz = (float)pz;      // the search runs on the fp32-rounded point
+        int best = nt;
+        if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
+            const CellGrid g = grids[b];
+            // cell coordinates and the 9 x-runs of the 27-cell block exactly as k_grid_query finds them
+            double fx = floor(((double)qx - (double)g.mn[0]) * g.inv_cell);
+            double fy = floor(((double)qy - (double)g.mn[1]) * g.inv_cell);
+            double fz = floor(((double)qz - (double)g.mn[2]) * g.inv_cell);
+            fx = fmin(fmax(fx, -2.0), (double)g.dim[0] + 1.0);
+            fy = fmin(fmax(fy, -2.0), (double)g.dim[1] + 1.0);
+            fz = fmin(fmax(fz, -2.0), (double)g.dim[2] + 1.0);
+            const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
+            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
+            unsigned long long key = ~0ull;
+            for (int j = 0; j < 9; j++) {
+                const int y = cy + (j % 3) - 1, z = cz + (j / 3) - 1;
+                if (x0 > x1 || y < 0 || y >= g.dim[1] || z < 0 || z >= g.dim[2]) continue;
+                const int g0 = g.table_off + x0 + g.dim[0] * (y + g.dim[1] * z);
+                const int rs = g0 == 0 ? 0 : table[g0 - 1], re = table[g0 + (x1 - x0)];
+                for (int p = rs; p < re; p++) {
+                    const float4 c = sorted[p];
+                    const float d2 = sqdist3(qx, qy, qz, c.x, c.y, c.z);
+                    if (d2 < r2) {
+                        const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned int)__float_as_int(c.w);
+                        key = k < key ? k : key;
+                    }
+                }
+            }
+            if (key != ~0ull) best = (int)(unsigned int)(key & 0xffffffffu);
+        }
+        if (nn_out) nn_out[i] = best;
+        if (best < nt) {
+            const double ux = tgt[3 * (size_t)best], uy = tgt[3 * (size_t)best + 1], uz = tgt[3 * (size_t)best + 2];
+            const double dx = px - ux, dy = py - uy, dz = pz - uz;
+            v[0] = 1.0;
+            v[1] = (dx * dx + dy * dy) + dz * dz;
+            if (M == ICP_P2P) {
+                const double* a = st[b].anchor;
+                const double P[3] = { px - a[0], py - a[1], pz - a[2] }, Q[3] = { ux - a[0], uy - a[1], uz - a[2] };
+#pragma unroll
+                for (int r = 0; r < 3; r++) { v[2 + r] = P[r]; v[5 + r] = Q[r]; }
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int c = 0; c < 3; c++) v[8 + 3 * r + c] = P[r] * Q[c];
+            } else {
+                const size_t j = 3 * (size_t)best;
+                const double nx = tgt_normals[j], ny = tgt_normals[j + 1], nz = tgt_normals[j + 2];
+                const double res = (dx * nx + dy * ny) + dz * nz;
+                const double J[6] = { py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz };
+                int k = 2;
+#pragma unroll
+                for (int r = 0; r < 6; r++)
+#pragma unroll
+                    for (int c = r; c < 6; c++) v[k++] = J[r] * J[c];
+#pragma unroll
+                for (int r = 0; r < 6; r++) v[23 + r] = J[r] * res;
+            }
+        }
+    }
+    icp_block_sum<NV>(v, part, slab + (size_t)tile * IcpRec<M>::STRIDE);
+}
+
+// ---- fp64 solvers (one lane) ----------------------------------------------------------------
+// Kabsch: R maximising tr(R H) over proper rotations, H = sum (p - pc)(q - qc)^T.  One-sided Jacobi on the columns of H
+// (H V = U S), singular values sorted descending; with U3 = U1 x U2 and V3 = V1 x V2 the rotation V diag(1, 1, d) U^T of
+// the det-corrected SVD (d = sign det(V U^T)) is [V1 V2 V1xV2][U1 U2 U1xU2]^T whatever the sign of the third pair.
+__device__ static void icp_cross(const double* a, const double* b, double* c)
+{
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+__device__ static bool icp_unit(double* a)
+{
+    const double l = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+    if (!(l > 0.0) || !isfinite(l)) return false;
+    a[0] /= l; a[1] /= l; a[2] /= l;
+    return true;
+}
+
+// a unit vector orthogonal to the unit vector u
+__device__ static void icp_any_orthogonal(const double* u, double* o)
+{
+    const double e[3] = { fabs(u[0]) < 0.6 ? 1.0 : 0.0, fabs(u[0]) < 0.6 ? 0.0 : 1.0, 0.0 };
+    icp_cross(u, e, o);
+    icp_unit(o);
+}
+
+__device__ static bool icp_kabsch_rotation(const double (&H)[3][3], double (&R)[3][3])
+{
+    double A[3][3], V[3][3];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) { A[r][c] = H[r][c]; V[r][c] = r == c ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 40; sweep++) {
+        bool rotated = false;
+        for (int pr = 0; pr < 3; pr++) {
+            const int i = pr == 2 ? 1 : 0, j = pr == 0 ? 1 : 2;
+            const double al = (A[0][i] * A[0][i] + A[1][i] * A[1][i]) + A[2][i] * A[2][i];
+            const double be = (A[0][j] * A[0][j] + A[1][j] * A[1][j]) + A[2][j] * A[2][j];
+            const double ga = (A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j];
+            if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
+            const double ze = (be - al) / (2.0 * ga);
+            const double t = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
+            const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+            for (int k = 0; k < 3; k++) {
+                const double ai = A[k][i], aj = A[k][j];
+                A[k][i] = cs * ai - sn * aj; A[k][j] = sn * ai + cs * aj;
+                const double vi = V[k][i], vj = V[k][j];
+                V[k][i] = cs * vi - sn * vj; V[k][j] = sn * vi + cs * vj;
+            }
+            rotated = true;
+        }
+        if (!rotated) break;
+    }
+    double s[3];
+    int o[3] = { 0, 1, 2 };
+    for (int c = 0; c < 3; c++) s[c] = (A[0][c] * A[0][c] + A[1][c] * A[1][c]) + A[2][c] * A[2][c];
+    for (int a = 0; a < 2; a++)                                               // descending, stable
+        for (int c = 0; c < 2 - a; c++)
+            if (s[o[c]] < s[o[c + 1]]) { const int t = o[c]; o[c] = o[c + 1]; o[c + 1] = t; }
+    double U1[3], U2[3], U3[3], V1[3], V2[3], V3[3];
+    for (int k = 0; k < 3; k++) { U1[k] = A[k][o[0]]; U2[k] = A[k][o[1]]; V1[k] = V[k][o[0]]; V2[k] = V[k][o[1]]; }
+    if (!icp_unit(U1)) return false;                                         // H = 0: no rotation to find
+    const double pj = (U1[0] * U2[0] + U1[1] * U2[1]) + U1[2] * U2[2];
+    for (int k = 0; k < 3; k++) U2[k] -= pj * U1[k];
+    if (!(s[o[1]] > 1e-28 * s[o[0]]) || !icp_unit(U2)) icp_any_orthogonal(U1, U2);   // rank 1: any completion
+    icp_cross(U1, U2, U3);
+    icp_cross(V1, V2, V3);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) R[r][c] = (V1[r] * U1[c] + V2[r] * U2[c]) + V3[r] * U3[c];
+    return true;
+}
+
+// J^T J x = -J^T r by Cholesky (LDL^T without pivoting); false when the system is not positive definite
+__device__ static bool icp_solve6(const double* up, const double* g, double (&x)[6])
+{
+    double A[6][6], L[6][6], D[6], y[6];
+    int k = 0;
+    for (int r = 0; r < 6; r++)
+        for (int c = r; c < 6; c++) { A[r][c] = up[k]; A[c][r] = up[k]; k++; }
+    for (int j = 0; j < 6; j++) {
+        double d = A[j][j];
+        for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
+        if (!(d > 0.0) || !isfinite(d)) return false;
+        D[j] = d;
+        L[j][j] = 1.0;
+        for (int i = j + 1; i < 6; i++) {
+            double e = A[i][j];
+            for (int m = 0; m < j; m++) e -= L[i][m] * L[j][m] * D[m];
+            L[i][j] = e / d;
+        }
+    }
+    for (int i = 0; i < 6; i++) {
+        double e = -g[i];
+        for (int m = 0; m < i; m++) e -= L[i][m] * y[m];
+        y[i] = e;
+    }
+    for (int i = 5; i >= 0; i--) {
+        double e = y[i] / D[i];
+        for (int m = i + 1; m < 6; m++) e -= L[m][i] * x[m];
+        x[i] = e;
+    }
+    for (int i = 0; i < 6; i++)
+        if (!isfinite(x[i])) return false;
+    return true;
+}
+
+template <int M>
+__global__ void __launch_bounds__(WAVE) k_icp_update(const int* __restrict__ src_off, const int* __restrict__ tile_off,
+                                                   const double* __restrict__ slab, int max_iteration, double rel_fitness,
+                                                   double rel_rmse, double* __restrict__ T, double* __restrict__ fitness,
+                                                   double* __restrict__ rmse_out, int* __restrict__ iters, IcpState* __restrict__ st,
+                                                   int* __restrict__ active)
+{
+    constexpr int NV = IcpRec<M>::NV;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (st[b].done) return;
+    const int t0 = tile_off[b], t1 = tile_off[b + 1];
+    double v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) v[k] = 0.0;
+    for (int t = t0 + lane; t < t1; t += WAVE) {
+        const double* rec = slab + (size_t)t * IcpRec<M>::STRIDE;
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] += rec[k];
+    }
+#pragma unroll
+    for (int k = 0; k < NV; k++)
+        for (int d = WAVE / 2; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
+    if (lane != 0) return;
+    const int n = src_off[b + 1] - src_off[b];
+    const double cnt = v[0];
+    const double fit = n > 0 ? cnt / (double)n : 0.0;
+    const double rmse = cnt > 0.0 ? sqrt(v[1] / cnt) : 0.0;
+    fitness[b] = fit;
+    rmse_out[b] = rmse;
+    IcpState s = st[b];
+    const int it = iters[b];
+    bool stop;
+    double dT[4][4];
+    if (it > 0 && fabs(s.prev_fit - fit) < rel_fitness && fabs(s.prev_rmse - rmse) < rel_rmse) stop = true;   // converged
+    else if (it >= max_iteration) stop = true;
+    else if (cnt < (M == ICP_P2P ? 3.0 : 6.0)) stop = true;                                               // too few matches
+    else {
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) dT[r][c] = r == c ? 1.0 : 0.0;
+        if (M == ICP_P2P) {
+            const double* a = s.anchor;
+            double pc[3], qc[3], H[3][3], R[3][3];
+            for (int r = 0; r < 3; r++) { pc[r] = v[2 + r] / cnt; qc[r] = v[5 + r] / cnt; }
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) H[r][c] = v[8 + 3 * r + c] - cnt * pc[r] * qc[c];
+            stop = !icp_kabsch_rotation(H, R);
+            if (!stop) {
+                const double Pa[3] = { a[0] + pc[0], a[1] + pc[1], a[2] + pc[2] }, Qa[3] = { a[0] + qc[0], a[1] + qc[1], a[2] + qc[2] };
+                for (int r = 0; r < 3; r++) {
+                    for (int c = 0; c < 3; c++) dT[r][c] = R[r][c];
+                    dT[r][3] = Qa[r] - ((R[r][0] * Pa[0] + R[r][1] * Pa[1]) + R[r][2] * Pa[2]);
+                }
+            }
+        } else {
+            double x[6];
+            stop = !icp_solve6(v + 2, v + 23, x);
+            if (!stop) {
+                // R = Rz(x2) Ry(x1) Rx(x0), t = x3..5 (open3d TransformVector6dToMatrix4d, restated)
+                const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+                dT[0][0] = cg * cb; dT[0][1] = cg * sb * sa - sg * ca; dT[0][2] = cg * sb * ca + sg * sa;
+                dT[1][0] = sg * cb; dT[1][1] = sg * sb * sa + cg * ca; dT[1][2] = sg * sb * ca - cg * sa;
+                dT[2][0] = -sb;     dT[2][1] = cb * sa;                dT[2][2] = cb * ca;
+                dT[0][3] = x[3]; dT[1][3] = x[4]; dT[2][3] = x[5];
+            }
+        }
+    }
+    if (!stop) {
+        double* Tb = T + 16 * (size_t)b;
+        double Tn[16];
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++)
+                Tn[4 * r + c] = ((dT[r][0] * Tb[c] + dT[r][1] * Tb[4 + c]) + dT[r][2] * Tb[8 + c]) + dT[r][3] * Tb[12 + c];
+        for (int k = 0; k < 16; k++) Tb[k] = Tn[k];
+        iters[b] = it + 1;
+        s.prev_fit = fit;
+        s.prev_rmse = rmse;
+        if (active) atomicAdd(active, 1);
+    } else {
+        s.done = 1;
+    }
+    st[b] = s;
+}
+
+// ------------------------------------------------------------------------------------------
+static int icp_tiles_upper(int n_src_total, int npairs) { return cdiv(n_src_total, ICP_TILE) + npairs; }
+
+struct IcpWs { void* grid; size_t grid_bytes; int* src_off; int* tile_off; IcpState* st; double* slab; int* active; };
+
+static IcpWs carve_icp(WsCarver& w, int ns, int nt, int npairs, int method)
+{
+    IcpWs e;
+    e.grid_bytes = buf_grid_ws_bytes(nt, npairs, 0);
+    e.grid = w.take<char>(e.grid_bytes);
+    e.src_off = w.take<int>((size_t)npairs + 1);
+    e.tile_off = w.take<int>((size_t)npairs + 1);
+    e.st = w.take<IcpState>((size_t)npairs);
+    e.slab = w.take<double>((size_t)icp_tiles_upper(ns, npairs) *
+                            (method == ICP_P2P ? IcpRec<ICP_P2P>::STRIDE : IcpRec<ICP_P2L>::STRIDE));
+    e.active = w.take<int>(64);
+    return e;
+}
+
+extern "C" size_t buf_icp_ws_bytes(int n_src_total, int n_tgt_total, int npairs, int method)
+{
+    if (n_src_total < 0 || n_tgt_total < 0 || npairs <= 0 || (method != ICP_P2P && method != ICP_P2L)) return 0;
+    WsCarver w(nullptr, 0);
+    carve_icp(w, n_src_total, n_tgt_total, npairs, method);
+    return w.used();
+}
+
+template <int M>
+static int icp_rounds(const IcpWs& e, const buf_grid_t& g, const float* src, const float* tgt, const float* tgt_normals, int nt,
+                      int npairs, int ntiles, float r2, int max_iteration, double rel_fitness, double rel_rmse, double* T_out,
+                      double* fitness_out, double* rmse_out, int* iters_out, int* nn_out, hipStream_t s)
+{
+    for (int r = 0; r <= max_iteration; r++) {
+        const bool probe = (r & 7) == 7 && r < max_iteration;
+        if (probe) BUF_CHECK_HIP(hipMemsetAsync(e.active, 0, sizeof(int), s));
+        if (ntiles > 0)
+            k_icp_correspond<M><<<ntiles, ICP_TILE, 0, s>>>((const CellGrid*)g.desc, g.table, (const float4*)g.sorted, src, e.src_off,
+                                                           e.tile_off, npairs, tgt, tgt_normals, nt, r2, T_out, e.st, nn_out, e.slab);
+        k_icp_update<M><<<npairs, WAVE, 0, s>>>(e.src_off, e.tile_off, e.slab, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out,
+                                                rmse_out, iters_out, e.st, probe ? e.active : nullptr);
+        if (probe) {
+            BUF_LAUNCH_CHECK();
+            int left = 0;
+            BUF_CHECK_HIP(hipMemcpyAsync(&left, e.active, sizeof(int), hipMemcpyDeviceToHost, s));
+            BUF_CHECK_HIP(hipStreamSynchronize(s));
+            if (left == 0) break;
+        }
+    }
+    BUF_LAUNCH_CHECK();
+    return BUF_OK;
+}
+
+extern "C" int buf_icp_batched(const float* src, const int* src_lengths_host, const float* tgt, const float* tgt_normals,
+                               const int* tgt_lengths_host, int npairs, int method, float max_dist, const double* T_init,
+                               int max_iteration, double rel_fitness, double rel_rmse, double* T_out, double* fitness_out,
+                               double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    BUF_REQUIRE(npairs >= 0, BUF_EINVAL, "buf_icp_batched: npairs=%d", npairs);
+    BUF_REQUIRE(method == ICP_P2P || method == ICP_P2L, BUF_EINVAL, "buf_icp_batched: unknown method %d", method);
+    BUF_REQUIRE(max_dist > 0.f && max_dist <= 3.4e38f, BUF_EINVAL, "buf_icp_batched: max_dist=%g (must be finite and > 0)", (double)max_dist);
+    BUF_REQUIRE(method != ICP_P2L || tgt_normals, BUF_EINVAL, "buf_icp_batched: point-to-plane needs target normals");
+    BUF_REQUIRE(max_iteration >= 0, BUF_EINVAL, "buf_icp_batched: max_iteration=%d", max_iteration);
+    if (npairs == 0) return BUF_OK;
+    BUF_REQUIRE(src_lengths_host && tgt_lengths_host, BUF_EINVAL, "buf_icp_batched: null lengths");
+    long long ns = 0, nt = 0, nts = 0;
+    for (int b = 0; b < npairs; b++) {
+        BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0, BUF_EINVAL, "buf_icp_batched: negative length in pair %d", b);
+        ns += src_lengths_host[b];
+        nt += tgt_lengths_host[b];
+        nts += cdiv(src_lengths_host[b], ICP_TILE);
+    }
+    BUF_REQUIRE(ns < 0x7fffffffLL && nt < 0x7fffffffLL, BUF_EINVAL, "buf_icp_batched: %lld / %lld points (int32 indices)", ns, nt);
+    BUF_REQUIRE(ns == 0 || src, BUF_EINVAL, "buf_icp_batched: null src");
+    BUF_REQUIRE(nt == 0 || tgt, BUF_EINVAL, "buf_icp_batched: null tgt");
+    BUF_REQUIRE(T_init && T_out && fitness_out && rmse_out && iters_out && ws, BUF_EINVAL, "buf_icp_batched: null argument");
+    BUF_REQUIRE(npairs <= 65535, BUF_EINVAL, "buf_icp_batched: %d pairs (at most 65535 per call)", npairs);
+    const size_t need = buf_icp_ws_bytes((int)ns, (int)nt, npairs, method);
+    BUF_REQUIRE(ws_bytes >= need, BUF_EWORKSPACE, "buf_icp_batched: workspace %zu < %zu bytes", ws_bytes, need);
+
+    WsCarver w(ws, ws_bytes);
+    const IcpWs e = carve_icp(w, (int)ns, (int)nt, npairs, method);
+    buf_grid_t g;
+    int rc = buf_grid_build(&g, tgt, (int)nt, tgt_lengths_host, npairs, max_dist, 0, e.grid, e.grid_bytes, s);
+    if (rc) return rc;
+    rc = upload_offsets(e.src_off, src_lengths_host, npairs, (int)ns, "buf_icp_batched", s);
+    if (rc) return rc;
+    int* tiles = (int*)malloc(sizeof(int) * (size_t)npairs);
+    BUF_REQUIRE(tiles, BUF_EINVAL, "buf_icp_batched: out of host memory");
+    for (int b = 0; b < npairs; b++) tiles[b] = cdiv(src_lengths_host[b], ICP_TILE);
+    rc = upload_offsets(e.tile_off, tiles, npairs, (int)nts, "buf_icp_batched", s);
+    free(tiles);
+    if (rc) return rc;
+    k_icp_setup<<<npairs, ICP_TILE, 0, s>>>(src, e.src_off, T_init, T_out, fitness_out, rmse_out, iters_out, e.st);
+    BUF_LAUNCH_CHECK();
+    const float r2 = max_dist * max_dist;                 // buf_grid_query's threshold
+    if (method == ICP_P2P)
+        return icp_rounds<ICP_P2P>(e, g, src, tgt, nullptr, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
+                                   fitness_out, rmse_out, iters_out, nn_out, s);
+    return icp_rounds<ICP_P2L>(e, g, src, tgt, tgt_normals, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
+                               fitness_out, rmse_out, iters_out, nn_out, s);
+}

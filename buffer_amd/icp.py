@@ -4,7 +4,10 @@
 Per iteration: nearest target point inside the correspondence distance for every transformed source point (A2 cell grid,
 column 0 of the distance-sorted neighbour row: csrc/radius.hip), fitness = matched / source points, RMSE over the matches,
 then the rigid update from the matches (centred 3x3 cross-covariance in fp64, SVD with the det correction) composed onto
-the running transform.  open3d's loop, restated; open3d itself is absent here (parity unpinned)."""
+the running transform.  open3d's loop, restated; open3d itself is absent here (parity unpinned).
+
+icp_batched runs the same loop (and open3d's point-to-plane step) for many pairs at once in csrc/icp.hip (buf_icp_batched):
+state, correspondences, sums and updates stay on the device; one int is read back every 8 rounds."""
 import numpy as np
 import torch
 
@@ -58,3 +61,58 @@ def icp_point_to_point(src, tgt, max_dist, init=None, max_iteration=30, relative
             break
     corr = torch.stack([hit, nn[hit]], 1).to(torch.int32).cpu().numpy() if hit.numel() else empty
     return T, float(fit), float(rmse), corr
+
+
+def icp_batched(srcs, tgts, max_dist, inits=None, method='point_to_point', tgt_normals=None, max_iteration=30,
+                relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False):
+    """ICP of B pairs in one set of launches (csrc/icp.hip, buf_icp_batched): srcs / tgts lists of f32[n_b,3] / f32[m_b,3]
+    device tensors, inits None or B 4x4 transforms, method 'point_to_point' (the loop of icp_point_to_point) or
+    'point_to_plane' (open3d's step, restated, unpinned; needs tgt_normals, a list of f32[m_b,3]).
+    -> list of B dicts: T (f64[4,4] numpy src->tgt), fitness, inlier_rmse, iterations, and correspondences (int32[k,2] numpy,
+    pair-local (source row, target row), only with return_correspondences).  Each pair's result does not depend on the
+    others of the batch; one small readback per 8 rounds instead of three host round trips per iteration and pair."""
+    B = len(srcs)
+    if len(tgts) != B:
+        raise ValueError(f"icp_batched: {B} sources but {len(tgts)} targets")
+    if inits is not None and len(inits) != B:
+        raise ValueError(f"icp_batched: {B} pairs but {len(inits)} initial transforms")
+    if method not in ops.ICP_METHODS:
+        raise ValueError(f"icp_batched: unknown method {method!r} (one of {sorted(ops.ICP_METHODS)})")
+    if method == 'point_to_plane':
+        if tgt_normals is None:
+            raise ValueError("icp_batched: point_to_plane needs tgt_normals (one f32[m,3] per target)")
+        if len(tgt_normals) != B or any(tuple(n.shape) != tuple(t.shape) for n, t in zip(tgt_normals, tgts)):
+            raise ValueError("icp_batched: tgt_normals must hold one [m,3] array per target, shaped like the target")
+    if B == 0:
+        return []
+    if not all(isinstance(x, torch.Tensor) and x.is_cuda for x in list(srcs) + list(tgts)):
+        raise RuntimeError("icp_batched: expected tensors in device memory (buffer_amd has no CPU path)")
+    dev = srcs[0].device
+    src = torch.cat([s.reshape(-1, 3).float() for s in srcs])
+    tgt = torch.cat([t.reshape(-1, 3).float() for t in tgts])
+    nrm = torch.cat([n.reshape(-1, 3).float() for n in tgt_normals]) if method == 'point_to_plane' else None
+    sl = np.array([s.shape[0] for s in srcs], np.int32)
+    tl = np.array([t.shape[0] for t in tgts], np.int32)
+    T0 = np.stack([np.eye(4) if inits is None else np.asarray(inits[b], np.float64).reshape(4, 4) for b in range(B)])
+    T, fit, rmse, iters, nn = ops.icp_batched(src, sl, tgt, tl, max_dist, torch.from_numpy(T0).to(dev), method, nrm, max_iteration,
+                                              relative_fitness, relative_rmse, correspondences=return_correspondences)
+    T, fit, rmse, iters = T.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy()
+    nn = nn.cpu().numpy() if nn is not None else None
+    s_off, t_off = np.concatenate([[0], np.cumsum(sl)]), np.concatenate([[0], np.cumsum(tl)])
+    out = []
+    for b in range(B):
+        r = dict(T=T[b], fitness=float(fit[b]), inlier_rmse=float(rmse[b]), iterations=int(iters[b]))
+        if return_correspondences:
+            row = nn[s_off[b]:s_off[b + 1]]
+            hit = np.flatnonzero(row < t_off[-1])
+            r['correspondences'] = np.stack([hit, row[hit] - t_off[b]], 1).astype(np.int32) if hit.size else np.zeros((0, 2), np.int32)
+        out.append(r)
+    return out
+
+
+def icp_point_to_plane(src, tgt, tgt_normals, max_dist, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+    """src f32[n,3], tgt / tgt_normals f32[m,3] (device) -> (T f64[4,4] numpy src->tgt, fitness, inlier_rmse, corr int32[k,2] numpy):
+    icp_point_to_point's return shape, point-to-plane step (icp_batched with one pair)."""
+    r = icp_batched([src], [tgt], max_dist, None if init is None else [init], 'point_to_plane', [tgt_normals], max_iteration,
+                    relative_fitness, relative_rmse, return_correspondences=True)[0]
+    return r['T'], r['fitness'], r['inlier_rmse'], r['correspondences']

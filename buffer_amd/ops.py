@@ -525,6 +525,34 @@ def post_refine(T_init, src, tgt, thr=0.10, iters=20):
     return T, info
 
 
+ICP_METHODS = {'point_to_point': 0, 'point_to_plane': 1}     # BUF_ICP_POINT_TO_POINT / BUF_ICP_POINT_TO_PLANE
+
+
+def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='point_to_point', tgt_normals=None, max_iteration=30,
+                relative_fitness=1e-6, relative_rmse=1e-6, correspondences=False):
+    """buf_icp_batched: ICP of the pairs stacked in src f32[sum src_lengths,3] / tgt f32[sum tgt_lengths,3] (pair b owns
+    src_lengths[b] / tgt_lengths[b] consecutive rows), T_init f64[B,4,4] -> (T f64[B,4,4], fitness f64[B], rmse f64[B],
+    iterations int32[B], nn int32[sum src_lengths] or None: global target row per source point, sum tgt_lengths = no match)."""
+    L = _lib.lib()
+    src, tgt = _dev(src, torch.float32, "icp_batched.src"), _dev(tgt, torch.float32, "icp_batched.tgt")
+    sl, tl = _host_i32(src_lengths), _host_i32(tgt_lengths)
+    B, dev = int(sl.shape[0]), src.device
+    m = ICP_METHODS[method]
+    nrm = _dev(tgt_normals, torch.float32, "icp_batched.tgt_normals") if tgt_normals is not None else None
+    T_init = _dev(T_init, torch.float64, "icp_batched.T_init").reshape(B, 4, 4)
+    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
+    fit = torch.empty((B,), dtype=torch.float64, device=dev)
+    rmse = torch.empty((B,), dtype=torch.float64, device=dev)
+    iters = torch.empty((B,), dtype=torch.int32, device=dev)
+    nn = torch.empty((max(int(src.shape[0]), 1),), dtype=torch.int32, device=dev) if correspondences else None
+    nbytes = max(L.buf_icp_ws_bytes(int(src.shape[0]), int(tgt.shape[0]), max(B, 1), m), 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_icp_batched(_ptr(src), _hptr(sl), _ptr(tgt), _ptr(nrm), _hptr(tl), B, m, float(max_dist), _ptr(T_init),
+                            int(max_iteration), float(relative_fitness), float(relative_rmse), _ptr(T), _ptr(fit), _ptr(rmse),
+                            _ptr(iters), _ptr(nn), _ptr(ws), nbytes, _stream()), "buf_icp_batched")
+    return T, fit, rmse, iters, (nn[:int(src.shape[0])] if nn is not None else None)
+
+
 def recover_poses_batched(ind, ss_kpts, tt_kpts, ss_R, tt_R, seg_lengths, seeds, cfg):
     """hypotheses + scoring + RANSAC + refinement of every pair of a step in one set of launches: the matches of the pairs are
     stacked, pair p owns seg_lengths[p] consecutive rows -> poses f32[nb,4,4] (identity for pairs with fewer than 3 matches)."""

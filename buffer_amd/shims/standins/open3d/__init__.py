@@ -7,7 +7,8 @@ libbuffer_hip.so (open3d==0.13.0 is a pip dependency of the reference, README.md
     utility.Vector3dVector, Vector2iVector
     io.read_point_cloud                 PLY vertices (utils/tools.py:6-7)
     pipelines.registration              registration_ransac_based_on_correspondence (models/BUFFER.py:314-326) -> buf_ransac_kabsch,
-                                        registration_icp (KITTI/dataset.py:104-107) -> device nearest-neighbour ICP
+                                        registration_icp (KITTI/dataset.py:104-107) -> device nearest-neighbour ICP,
+                                        point-to-point and (TransformationEstimationPointToPlane) point-to-plane
 
 It is installed behind any real open3d (buffer_amd.shims.install appends this directory to sys.path), so an
 environment that has the real package keeps using it.  Point data crosses as numpy arrays exactly as with open3d;

@@ -6,6 +6,15 @@ class TransformationEstimationPointToPoint:
         self.with_scaling = bool(with_scaling)
 
 
+class TransformationEstimationPointToPlane:
+    """L2 point-to-plane ICP step (open3d's, restated, unpinned): needs target normals."""
+
+    def __init__(self, kernel=None):
+        if kernel is not None:
+            raise NotImplementedError("open3d stand-in: robust kernels other than L2 are not provided")
+        self.kernel = None
+
+
 class CorrespondenceCheckerBasedOnEdgeLength:
     def __init__(self, similarity_threshold=0.9):
         self.similarity_threshold = float(similarity_threshold)
@@ -85,10 +94,14 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
-    """KITTI/dataset.py:104-107: point-to-point ICP on the device (buffer_amd/icp.py)."""
+    """KITTI/dataset.py:104-107: point-to-point ICP on the device (buffer_amd/icp.py).  TransformationEstimationPointToPlane runs
+    buffer_amd.icp.icp_batched (csrc/icp.hip) on the target's normals; a target without normals raises RuntimeError (open3d
+    would hand back the initial transform unrefined: refused here rather than returning an unrefined pose)."""
     import torch
     from buffer_amd import icp
     est = estimation_method or TransformationEstimationPointToPoint(False)
+    if isinstance(est, TransformationEstimationPointToPlane):
+        return _registration_icp_point_to_plane(source, target, max_correspondence_distance, init, criteria)
     if est.with_scaling:
         raise NotImplementedError("open3d stand-in: rigid point-to-point ICP only")
     cr = criteria or ICPConvergenceCriteria()
@@ -96,6 +109,22 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     src = torch.from_numpy(np.asarray(source.points, np.float32)).to(dev)
     tgt = torch.from_numpy(np.asarray(target.points, np.float32)).to(dev)
     T, fit, rmse, corr = icp.icp_point_to_point(src, tgt, float(max_correspondence_distance),
+                                                np.eye(4) if init is None else np.asarray(init, np.float64),
+                                                cr.max_iteration, cr.relative_fitness, cr.relative_rmse)
+    return RegistrationResult(T, fit, rmse, corr)
+
+
+def _registration_icp_point_to_plane(source, target, max_correspondence_distance, init, criteria):
+    import torch
+    from buffer_amd import icp
+    if not target.has_normals():
+        raise RuntimeError("open3d stand-in: point-to-plane ICP needs target normals; call target.estimate_normals() first")
+    cr = criteria or ICPConvergenceCriteria()
+    dev = _device()
+    src = torch.from_numpy(np.asarray(source.points, np.float32)).to(dev)
+    tgt = torch.from_numpy(np.asarray(target.points, np.float32)).to(dev)
+    nrm = torch.from_numpy(np.asarray(target.normals, np.float32)).to(dev)
+    T, fit, rmse, corr = icp.icp_point_to_plane(src, tgt, nrm, float(max_correspondence_distance),
                                                 np.eye(4) if init is None else np.asarray(init, np.float64),
                                                 cr.max_iteration, cr.relative_fitness, cr.relative_rmse)
     return RegistrationResult(T, fit, rmse, corr)

@@ -159,8 +159,9 @@ def make_config1_pair(seed=7, n=5000):
                 relt_pose=pose, src_id='config1/src', tgt_id='config1/tgt')
 
 
-def make_kitti_pair(seed, beams=64, az_steps=1900, fds_voxel=0.05, sds_voxel=0.30):
-    """Ring-pattern LiDAR scans (~120k returns) over a ground plane with boxes."""
+def make_kitti_pair(seed, beams=64, az_steps=1900, fds_voxel=0.05, sds_voxel=0.30, raw=False):
+    """Ring-pattern LiDAR scans (~120k returns) over a ground plane with boxes.  raw=True adds the scans
+    before voxelisation as src_raw / tgt_raw (f64[n,3], each in its own sensor frame); the other entries are unchanged."""
     rng = np.random.default_rng(seed)
     boxes = [(rng.uniform(-60, 60), rng.uniform(-60, 60), rng.uniform(2, 10), rng.uniform(2, 10),
               rng.uniform(1.5, 6)) for _ in range(40)]
@@ -194,6 +195,8 @@ def make_kitti_pair(seed, beams=64, az_steps=1900, fds_voxel=0.05, sds_voxel=0.3
         T[:3, 3] = -R @ o
         poses.append(T)
         p = pts @ R.T + T[:3, 3]
+        if raw:
+            out[f'{name}_raw'] = p
         fds = voxel_down_sample(p, fds_voxel)
         sds = voxel_down_sample(fds, sds_voxel)
         nrm = np.tile(np.array([[0, 0, 1.0]]), (sds.shape[0], 1))

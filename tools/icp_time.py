@@ -1,0 +1,86 @@
+"""ICP on KITTI-shape ring scans before voxelisation (synth.make_kitti_pair(raw=True), ~120k returns per scan), the way
+kitti.KittiTestSet refines its ground truth (0.20 m, <= 200 iterations, relative criteria 1e-6): the serial
+icp.icp_point_to_point against icp.icp_batched at batch 1 and at batch --pairs.  The source scan starts from the true pose
+perturbed by a small error (odometry is close, not exact).  Times are HIP-event spans after a warm-up of every path.
+Prints one JSON line:  python tools/icp_time.py [--pairs 16]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from buffer_amd import icp, synth  # noqa: E402
+
+
+def _span(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return out, a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--pairs', type=int, default=16)
+    ap.add_argument('--max-iteration', type=int, default=200)
+    ap.add_argument('--dist', type=float, default=0.20)
+    a = ap.parse_args()
+    dev = torch.device('cuda:0')
+    rng = np.random.default_rng(0)
+    srcs, tgts = [], []
+    for seed in range(a.pairs):
+        s = synth.make_kitti_pair(seed, raw=True)
+        e = np.deg2rad(rng.uniform(-0.3, 0.3, 3))
+        cz, sz, cy, sy = np.cos(e[2]), np.sin(e[2]), np.cos(e[1]), np.sin(e[1])
+        E = np.eye(4)
+        E[:3, :3] = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+        E[:3, 3] = rng.uniform(-0.05, 0.05, 3)
+        M = E @ s['relt_pose']                                               # "odometry": the true pose with a small error
+        xyz0 = s['src_raw'] @ M[:3, :3].T + M[:3, 3]
+        srcs.append(torch.from_numpy(xyz0.astype(np.float32)).to(dev))
+        tgts.append(torch.from_numpy(s['tgt_raw'].astype(np.float32)).to(dev))
+    kw = dict(max_iteration=a.max_iteration)
+    # warm-up of every path (code objects, allocator)
+    icp.icp_point_to_point(srcs[0], tgts[0], a.dist, np.eye(4), 3)
+    icp.icp_batched(srcs[:1], tgts[:1], a.dist, max_iteration=3)
+    icp.icp_batched(srcs, tgts, a.dist, max_iteration=3)
+
+    calls = [0]
+    kabsch = icp._kabsch
+
+    def counted(p, q):
+        calls[0] += 1
+        return kabsch(p, q)
+    icp._kabsch = counted
+    serial, t_serial, it_serial = [], 0.0, []
+    for s, t in zip(srcs, tgts):
+        calls[0] = 0
+        r, ms = _span(lambda: icp.icp_point_to_point(s, t, a.dist, np.eye(4), a.max_iteration))
+        serial.append(r[0]); t_serial += ms; it_serial.append(calls[0])
+    icp._kabsch = kabsch
+    one, t_one = [], 0.0
+    for s, t in zip(srcs, tgts):
+        r, ms = _span(lambda: icp.icp_batched([s], [t], a.dist, **kw)[0])
+        one.append(r); t_one += ms
+    batch, t_batch = _span(lambda: icp.icp_batched(srcs, tgts, a.dist, **kw))
+    it1, itb = [r['iterations'] for r in one], [r['iterations'] for r in batch]
+    B = len(srcs)
+    print(json.dumps(dict(
+        pairs=B, points_per_scan=int(np.mean([s.shape[0] for s in srcs])), max_dist=a.dist, max_iteration=a.max_iteration,
+        serial_ms_per_pair=t_serial / B, serial_ms_per_iteration=t_serial / max(sum(it_serial), 1),
+        batch1_ms_per_pair=t_one / B, batch1_ms_per_iteration=t_one / max(sum(it1), 1),
+        batched_ms_per_pair=t_batch / B, batched_ms_per_pair_iteration=t_batch / max(sum(itb), 1),
+        batched_rounds=max(itb) + 1, iterations_serial=it_serial, iterations_batched=itb,
+        iterations_batch1_equal_batched=it1 == itb,
+        max_abs_T_diff_serial_vs_batched=float(max(np.abs(x - y['T']).max() for x, y in zip(serial, batch))),
+        max_abs_T_diff_batch1_vs_batched=float(max(np.abs(x['T'] - y['T']).max() for x, y in zip(one, batch))))))
+
+
+if __name__ == '__main__':
+    main()
