@@ -90,6 +90,35 @@ __device__ __forceinline__ int xcd_contiguous_block(int bid, int nb)
     return x * q + min(x, r) + idx;
 }
 
+// ---- A2 cell-grid lookups (the grid of radius.hip; every kernel that reads it finds a query's cells with these two) ----
+// Cell coordinate of a query coordinate v along one axis of an element's grid.  fp64: a query must land in exactly the cell its
+// coordinate rounds to (the cell edge exceeds the radius by 1e-5 only).  Clamped to [-2, dim + 1] before the int conversion:
+// far-away queries simply find no cell.  (The build side clamps to [0, dim - 1] instead: cell_coord in radius.hip.)
+__device__ __forceinline__ int query_cell_coord(float v, float mn, double inv_cell, int dim)
+{
+    double f = floor(((double)v - (double)mn) * inv_cell);
+    f = fmin(fmax(f, -2.0), (double)dim + 1.0);
+    return (int)f;
+}
+
+// x-run j (0..8: y = cy + j % 3 - 1, z = cz + j / 3 - 1) of the 27-cell block around cell (cx, cy, cz) of an element whose dense
+// table starts at table slot toff, dims (dx, dy, dz): rows [start, start + len) of the cell-ordered array (the table holds
+// inclusive cell ends).  An empty run (0, 0) where it falls outside the grid, and for j >= 9 (the lanes past the ninth of the
+// kernels that fetch one run per lane).  I = the index type of the table offsets.
+template <typename I>
+__device__ __forceinline__ void cell_xrun(const int* __restrict__ table, I toff, int dx, int dy, int dz, int cx, int cy, int cz, int j,
+                                          int& start, int& len)
+{
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, dx - 1);
+    const int y = cy + (j % 3) - 1, z = cz + (j / 3) - 1;
+    start = 0; len = 0;
+    if (j < 9 && x0 <= x1 && y >= 0 && y < dy && z >= 0 && z < dz) {
+        const I g0 = toff + x0 + (I)dx * (y + (I)dy * z);
+        start = g0 == 0 ? 0 : table[g0 - 1];
+        len = table[g0 + (x1 - x0)] - start;
+    }
+}
+
 // element b such that off[b] <= i < off[b+1]
 __device__ __forceinline__ int find_elem(const int* __restrict__ off, int nb, int i)
 {

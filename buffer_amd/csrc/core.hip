@@ -250,19 +250,10 @@ __global__ void __launch_bounds__(256) k_cell_rank(const int* __restrict__ cell_
             const int b = (int)(c / cells_per_elem), cl = (int)(c - (long long)b * cells_per_elem);
             const int dx = dims[b * dims_stride], dy = dims[b * dims_stride + 1], dz = dims[b * dims_stride + 2];
             const int cx = cl % dx, t2 = cl / dx, cy = t2 % dy, cz = t2 / dy;
-            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, dx - 1);
             const long long toff = (long long)b * cells_per_elem;
             int rs[9], len[9];
 #pragma unroll
-            for (int j = 0; j < 9; j++) {
-                const int y = cy + (j % 3) - 1, z = cz + (j / 3) - 1;
-                rs[j] = 0; len[j] = 0;
-                if (y >= 0 && y < dy && z >= 0 && z < dz) {
-                    const long long g0 = toff + x0 + (long long)dx * (y + (long long)dy * z);
-                    rs[j] = g0 == 0 ? 0 : table[g0 - 1];
-                    len[j] = table[g0 + (x1 - x0)] - rs[j];
-                }
-            }
+            for (int j = 0; j < 9; j++) cell_xrun(table, toff, dx, dy, dz, cx, cy, cz, j, rs[j], len[j]);     // 64-bit table offsets
             int4* rec = reinterpret_cast<int4*>(cruns + 20 * (size_t)s);
             rec[0] = make_int4(rs[0], rs[1], rs[2], rs[3]);
             rec[1] = make_int4(rs[4], rs[5], rs[6], rs[7]);

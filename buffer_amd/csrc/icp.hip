@@ -1,6 +1,6 @@
 // ICP, point-to-point and point-to-plane, for B pairs per call (open3d registration_icp with
-// TransformationEstimationPointToPoint / TransformationEstimationPointToPlane; the point-to-point loop is the one of
-// buffer_amd/icp.py::icp_point_to_point, the point-to-plane step is open3d's, restated, unpinned).
+// TransformationEstimationPointToPoint / TransformationEstimationPointToPlane, restated, unpinned: Kabsch for point-to-point,
+// open3d's 6x6 step for point-to-plane).  Every ICP entry point of buffer_amd/icp.py runs here.
 //
 // Set-up (once per call):
 //   buf_grid_build   one A2 cell grid over all targets, one element per pair, radius = max_dist
@@ -12,8 +12,8 @@
 //                    arithmetic and strict d2 < r2 (= column 0 of the distance-sorted query row; no sort, no row cap),
 //                    non-finite points skipped.  The point's fp64 terms are summed inside the wave (xor butterfly) and
 //                    across the 4 waves through LDS in a fixed order; the tile writes ONE record to the slab.
-//   k_icp_update     one wave per pair: the pair's records summed in a fixed order, fitness / rmse, the state machine of
-//                    icp_point_to_point, the fp64 update (Kabsch with the det correction, or the 6x6 Cholesky solve) and
+//   k_icp_update     one wave per pair: the pair's records summed in a fixed order, fitness / rmse, open3d's stopping
+//                    rules, the fp64 update (Kabsch with the det correction, or the 6x6 Cholesky solve) and
 //                    T <- dT T.
 // No float atomics: a pair's tiles hold its own points only and every sum has a fixed order, so a pair's result does not
 // depend on the other pairs of the batch and two runs give the same bits.  Finished pairs are skipped by both kernels.
@@ -117,22 +117,15 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __r
         int best = nt;
         if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
             const CellGrid g = grids[b];
-            // cell coordinates and the 9 x-runs of the 27-cell block exactly as k_grid_query finds them
-            double fx = floor(((double)qx - (double)g.mn[0]) * g.inv_cell);
-            double fy = floor(((double)qy - (double)g.mn[1]) * g.inv_cell);
-            double fz = floor(((double)qz - (double)g.mn[2]) * g.inv_cell);
-            fx = fmin(fmax(fx, -2.0), (double)g.dim[0] + 1.0);
-            fy = fmin(fmax(fy, -2.0), (double)g.dim[1] + 1.0);
-            fz = fmin(fmax(fz, -2.0), (double)g.dim[2] + 1.0);
-            const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
-            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
+            const int cx = query_cell_coord(qx, g.mn[0], g.inv_cell, g.dim[0]);
+            const int cy = query_cell_coord(qy, g.mn[1], g.inv_cell, g.dim[1]);
+            const int cz = query_cell_coord(qz, g.mn[2], g.inv_cell, g.dim[2]);
             unsigned long long key = ~0ull;
+#pragma unroll 1                                                           // (one copy of the candidate loop)
             for (int j = 0; j < 9; j++) {
-                const int y = cy + (j % 3) - 1, z = cz + (j / 3) - 1;
-                if (x0 > x1 || y < 0 || y >= g.dim[1] || z < 0 || z >= g.dim[2]) continue;
-                const int g0 = g.table_off + x0 + g.dim[0] * (y + g.dim[1] * z);
-                const int rs = g0 == 0 ? 0 : table[g0 - 1], re = table[g0 + (x1 - x0)];
-                for (int p = rs; p < re; p++) {
+                int rs, len;
+                cell_xrun(table, g.table_off, g.dim[0], g.dim[1], g.dim[2], cx, cy, cz, j, rs, len);
+                for (int p = rs; p < rs + len; p++) {
                     const float4 c = sorted[p];
                     const float d2 = sqdist3(qx, qy, qz, c.x, c.y, c.z);
                     if (d2 < r2) {

@@ -558,20 +558,10 @@ __global__ void __launch_bounds__(SPB_WAVES * WAVE) k_select_patches_grid(const 
     // the 9 cell runs around the keypoint (lanes 0..8), flattened
     int rs = 0, len = 0;
     {
-        double fx = floor(((double)qx - (double)g.mn[0]) * g.inv_cell);
-        double fy = floor(((double)qy - (double)g.mn[1]) * g.inv_cell);
-        double fz = floor(((double)qz - (double)g.mn[2]) * g.inv_cell);
-        fx = fmin(fmax(fx, -2.0), (double)g.dim[0] + 1.0);
-        fy = fmin(fmax(fy, -2.0), (double)g.dim[1] + 1.0);
-        fz = fmin(fmax(fz, -2.0), (double)g.dim[2] + 1.0);
-        const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
-        const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-        const int y = cy + (lane % 3) - 1, z = cz + (lane / 3) - 1;
-        if (lane < 9 && x0 <= x1 && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2]) {
-            const int g0 = g.table_off + x0 + g.dim[0] * (y + g.dim[1] * z);
-            rs = g0 == 0 ? 0 : table[g0 - 1];
-            len = table[g0 + (x1 - x0)] - rs;
-        }
+        const int cx = query_cell_coord(qx, g.mn[0], g.inv_cell, g.dim[0]);
+        const int cy = query_cell_coord(qy, g.mn[1], g.inv_cell, g.dim[1]);
+        const int cz = query_cell_coord(qz, g.mn[2], g.inv_cell, g.dim[2]);
+        cell_xrun(table, g.table_off, g.dim[0], g.dim[1], g.dim[2], cx, cy, cz, lane, rs, len);
     }
     int st[9], pre[9], total = 0;
 #pragma unroll

@@ -127,24 +127,14 @@ __global__ void __launch_bounds__(WAVE) k_grid_query(const CellGrid* __restrict_
         int b = find_elem(q_off, nb, qi);
         CellGrid g = grids[b];
         qx = queries[3 * (size_t)qi]; qy = queries[3 * (size_t)qi + 1]; qz = queries[3 * (size_t)qi + 2];
-        double fx = floor(((double)qx - (double)g.mn[0]) * g.inv_cell);
-        double fy = floor(((double)qy - (double)g.mn[1]) * g.inv_cell);
-        double fz = floor(((double)qz - (double)g.mn[2]) * g.inv_cell);
-        // clamp far-away queries before the int conversion; they simply find no cell
-        fx = fmin(fmax(fx, -2.0), (double)g.dim[0] + 1.0);
-        fy = fmin(fmax(fy, -2.0), (double)g.dim[1] + 1.0);
-        fz = fmin(fmax(fz, -2.0), (double)g.dim[2] + 1.0);
-        int cx = (int)fx, cy = (int)fy, cz = (int)fz;
-        int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
+        const int cx = query_cell_coord(qx, g.mn[0], g.inv_cell, g.dim[0]);
+        const int cy = query_cell_coord(qy, g.mn[1], g.inv_cell, g.dim[1]);
+        const int cz = query_cell_coord(qz, g.mn[2], g.inv_cell, g.dim[2]);
 #pragma unroll
         for (int j = 0; j < 9; j++) {
-            int y = cy + (j % 3) - 1, z = cz + (j / 3) - 1;
-            if (x0 <= x1 && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2]) {
-                int g0 = g.table_off + x0 + g.dim[0] * (y + g.dim[1] * z);
-                int g1 = g0 + (x1 - x0);
-                rs[j] = g0 == 0 ? 0 : table[g0 - 1];
-                re[j] = table[g1];
-            }
+            int len;
+            cell_xrun(table, g.table_off, g.dim[0], g.dim[1], g.dim[2], cx, cy, cz, j, rs[j], len);
+            re[j] = rs[j] + len;
         }
     }
 
@@ -307,19 +297,11 @@ __global__ void __launch_bounds__(QW_WAVES * WAVE) k_grid_query_wave(const CellG
     const float qd = d == 0 ? qx : (d == 1 ? qy : qz);
     const float mnd = d == 0 ? g.mn[0] : (d == 1 ? g.mn[1] : g.mn[2]);
     const int dimd = d == 0 ? g.dim[0] : (d == 1 ? g.dim[1] : g.dim[2]);
-    double fd = floor(((double)qd - (double)mnd) * g.inv_cell);
-    fd = fmin(fmax(fd, -2.0), (double)dimd + 1.0);                        // far-away queries simply find no cell
-    const int cd = (int)fd;
+    const int cd = query_cell_coord(qd, mnd, g.inv_cell, dimd);
     const int cx = __shfl(cd, 0, QG), cy = __shfl(cd, 1, QG), cz = __shfl(cd, 2, QG);
     {
         int rs = 0, len = 0;
-        const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-        const int y = cy + (l16 % 3) - 1, z = cz + (l16 / 3) - 1;
-        if (active && l16 < 9 && x0 <= x1 && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2]) {
-            const int g0 = g.table_off + x0 + g.dim[0] * (y + g.dim[1] * z);
-            rs = g0 == 0 ? 0 : table[g0 - 1];
-            len = table[g0 + (x1 - x0)] - rs;
-        }
+        if (active && l16 < 9) cell_xrun(table, g.table_off, g.dim[0], g.dim[1], g.dim[2], cx, cy, cz, l16, rs, len);
         if (l16 < 10) { runs[w][grp][l16] = rs; runs[w][grp][10 + l16] = len; }          // slots 9 / 19: zero padding
     }
     wave_sync();

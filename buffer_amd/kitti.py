@@ -10,7 +10,7 @@ and exits; run it first so that a timed run starts from a full cache.
 
 The reference refines the odometry ground truth with open3d ICP on first use and caches it under icp/
 (dataset.py:95-117); here the cached file is used when present, otherwise the same ICP refinement runs on the device
-(buffer_amd/icp.py) and fills the cache; --allow-odometry-gt skips the refinement.  The summary reports how many pairs used
+(buffer_amd/icp.py::icp_batched) and fills the cache; --allow-odometry-gt skips the refinement.  The summary reports how many pairs used
 which source (`gt_source`).  Host code is file IO and bookkeeping; voxelisation, normals and registration run on the device."""
 import glob
 import math
@@ -86,41 +86,37 @@ class KittiTestSet:
         fn = os.path.join(self.pc_path, 'sequences', '%02d' % drive, 'velodyne', '%06d.bin' % t)
         return np.ascontiguousarray(np.fromfile(fn, dtype=np.float32).reshape(-1, 4)[:, :3])
 
+    def _odometry_transform(self, index):
+        """the odometry transform M of scan t0 -> scan t1 (dataset.py:100-102)"""
+        drive, t0, t1 = self.files[index]
+        p0, p1 = (odometry_to_positions(o) for o in self.odometry(drive)[[t0, t1]])
+        return (VELO2CAM @ p0.T @ np.linalg.inv(p1.T) @ np.linalg.inv(VELO2CAM)).T
+
     def ground_truth(self, index, device=None):
         """dataset.py:95-117: transform scan t0 -> scan t1.  The reference refines the odometry transform M with
         point-to-point ICP on the raw scans (threshold 0.20 m, <= 200 iterations), stores `M @ T_icp` under
         icp/<drive>_<t0>_<t1>.npy and evaluates against that.  Here: the cached file if present; otherwise the same
-        refinement on the device (buffer_amd/icp.py, needs `device`), written to the same cache; the raw odometry
+        refinement on the device (refine_ground_truths, needs `device`), written to the same cache; the raw odometry
         transform only with `allow_odometry_gt`.  Every pair's source is recorded in `gt_source`."""
-        drive, t0, t1 = self.files[index]
-        cached = os.path.join(self.icp_path, '%d_%d_%d.npy' % (drive, t0, t1))
-        if os.path.exists(cached):
-            if self.gt_source.get(index) != 'icp-device':             # (a file this object refined itself keeps its label)
-                self.gt_source[index] = 'icp-cache'
-            return np.load(cached)
-        p0, p1 = (odometry_to_positions(o) for o in self.odometry(drive)[[t0, t1]])
-        M = (VELO2CAM @ p0.T @ np.linalg.inv(p1.T) @ np.linalg.inv(VELO2CAM)).T
-        if self.allow_odometry_gt:
-            self.gt_source[index] = 'odometry'
-            return M
-        if device is None:
-            raise FileNotFoundError(f'{cached} missing: the reference evaluates against ICP-refined poses; call with a device '
-                                    f'to refine here, or pass allow_odometry_gt=True (--allow-odometry-gt) for raw odometry')
-        from . import icp
-        xyz0 = self.scan(drive, t0).astype(np.float64) @ M[:3, :3].T + M[:3, 3]
-        T_icp, _, _, _ = icp.icp_point_to_point(torch.from_numpy(xyz0.astype(np.float32)).to(device),
-                                                torch.from_numpy(self.scan(drive, t1)).to(device), 0.20, np.eye(4), 200)
-        M2 = M @ T_icp                                                 # the reference's composition order (dataset.py:110)
-        os.makedirs(self.icp_path, exist_ok=True)
-        np.save(cached, M2)
-        self.gt_source[index] = 'icp-device'
-        return M2
+        cached = os.path.join(self.icp_path, '%d_%d_%d.npy' % self.files[index])
+        if not os.path.exists(cached):
+            if self.allow_odometry_gt:
+                self.gt_source[index] = 'odometry'
+                return self._odometry_transform(index)
+            if device is None:
+                raise FileNotFoundError(f'{cached} missing: the reference evaluates against ICP-refined poses; call with a device '
+                                        f'to refine here, or pass allow_odometry_gt=True (--allow-odometry-gt) for raw odometry')
+            self.refine_ground_truths([index], device)
+        if self.gt_source.get(index) != 'icp-device':                 # (a file this object refined itself keeps its label)
+            self.gt_source[index] = 'icp-cache'
+        return np.load(cached)
 
     def refine_ground_truths(self, indices, device, batch=16):
         """Fill the icp/ cache for every listed pair whose file is missing, `batch` pairs per buf_icp_batched call
-        (buffer_amd/icp.py::icp_batched): the refinement of ground_truth() -- odometry transform M, point-to-point ICP of the
-        raw scans at 0.20 m, <= 200 iterations, `M @ T_icp` -- without a host round trip per iteration and pair.  Existing cache
-        files are left alone; refined pairs are labelled 'icp-device'.  Returns the indices refined."""
+        (buffer_amd/icp.py::icp_batched): odometry transform M, point-to-point ICP of the raw scans at 0.20 m,
+        <= 200 iterations, `M @ T_icp` (the reference's composition order, dataset.py:110).  A pair's result does not depend
+        on the batch, so a file has the same bits whichever call wrote it.  Existing cache files are left alone; refined pairs
+        are labelled 'icp-device'.  Returns the indices refined."""
         from . import icp
         todo = [i for i in indices if not os.path.exists(os.path.join(self.icp_path, '%d_%d_%d.npy' % self.files[i]))]
         for lo in range(0, len(todo), max(int(batch), 1)):
@@ -128,8 +124,7 @@ class KittiTestSet:
             Ms, srcs, tgts = [], [], []
             for i in chunk:
                 drive, t0, t1 = self.files[i]
-                p0, p1 = (odometry_to_positions(o) for o in self.odometry(drive)[[t0, t1]])
-                M = (VELO2CAM @ p0.T @ np.linalg.inv(p1.T) @ np.linalg.inv(VELO2CAM)).T     # as ground_truth()
+                M = self._odometry_transform(i)
                 xyz0 = self.scan(drive, t0).astype(np.float64) @ M[:3, :3].T + M[:3, 3]
                 Ms.append(M)
                 srcs.append(torch.from_numpy(xyz0.astype(np.float32)).to(device))

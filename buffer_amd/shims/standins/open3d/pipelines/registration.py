@@ -94,37 +94,22 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
-    """KITTI/dataset.py:104-107: point-to-point ICP on the device (buffer_amd/icp.py).  TransformationEstimationPointToPlane runs
-    buffer_amd.icp.icp_batched (csrc/icp.hip) on the target's normals; a target without normals raises RuntimeError (open3d
-    would hand back the initial transform unrefined: refused here rather than returning an unrefined pose)."""
+    """KITTI/dataset.py:104-107: ICP on the device (buffer_amd/icp.py, csrc/icp.hip).  TransformationEstimationPointToPlane uses
+    the target's normals; a target without normals raises RuntimeError (open3d would hand back the initial transform unrefined:
+    refused here rather than returning an unrefined pose)."""
     import torch
     from buffer_amd import icp
     est = estimation_method or TransformationEstimationPointToPoint(False)
-    if isinstance(est, TransformationEstimationPointToPlane):
-        return _registration_icp_point_to_plane(source, target, max_correspondence_distance, init, criteria)
-    if est.with_scaling:
+    plane = isinstance(est, TransformationEstimationPointToPlane)
+    if not plane and est.with_scaling:
         raise NotImplementedError("open3d stand-in: rigid point-to-point ICP only")
-    cr = criteria or ICPConvergenceCriteria()
-    dev = _device()
-    src = torch.from_numpy(np.asarray(source.points, np.float32)).to(dev)
-    tgt = torch.from_numpy(np.asarray(target.points, np.float32)).to(dev)
-    T, fit, rmse, corr = icp.icp_point_to_point(src, tgt, float(max_correspondence_distance),
-                                                np.eye(4) if init is None else np.asarray(init, np.float64),
-                                                cr.max_iteration, cr.relative_fitness, cr.relative_rmse)
-    return RegistrationResult(T, fit, rmse, corr)
-
-
-def _registration_icp_point_to_plane(source, target, max_correspondence_distance, init, criteria):
-    import torch
-    from buffer_amd import icp
-    if not target.has_normals():
+    if plane and not target.has_normals():
         raise RuntimeError("open3d stand-in: point-to-plane ICP needs target normals; call target.estimate_normals() first")
     cr = criteria or ICPConvergenceCriteria()
     dev = _device()
-    src = torch.from_numpy(np.asarray(source.points, np.float32)).to(dev)
-    tgt = torch.from_numpy(np.asarray(target.points, np.float32)).to(dev)
-    nrm = torch.from_numpy(np.asarray(target.normals, np.float32)).to(dev)
-    T, fit, rmse, corr = icp.icp_point_to_plane(src, tgt, nrm, float(max_correspondence_distance),
-                                                np.eye(4) if init is None else np.asarray(init, np.float64),
-                                                cr.max_iteration, cr.relative_fitness, cr.relative_rmse)
+    clouds = [source.points, target.points] + ([target.normals] if plane else [])
+    run = icp.icp_point_to_plane if plane else icp.icp_point_to_point
+    T, fit, rmse, corr = run(*(torch.from_numpy(np.asarray(c, np.float32)).to(dev) for c in clouds), float(max_correspondence_distance),
+                             np.eye(4) if init is None else np.asarray(init, np.float64),
+                             cr.max_iteration, cr.relative_fitness, cr.relative_rmse)
     return RegistrationResult(T, fit, rmse, corr)

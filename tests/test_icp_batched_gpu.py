@@ -1,5 +1,5 @@
-"""Batched on-device ICP (csrc/icp.hip, buffer_amd/icp.py::icp_batched): parity with the serial icp_point_to_point, one exact
-step against numpy, determinism, point-to-plane, edge cases, the open3d stand-in and the KITTI cache filler."""
+"""On-device ICP (csrc/icp.hip, buffer_amd/icp.py): parity with a serial host restatement of the point-to-point loop, one exact
+step against numpy, determinism, point-to-plane, edge cases, the open3d stand-in and the KITTI ground-truth cache."""
 import os
 import subprocess
 import sys
@@ -58,30 +58,65 @@ def _six_pairs():
     return srcs, tgts
 
 
-def _serial(src, tgt, dist, init, k, rf, rr, monkeypatch):
-    """icp_point_to_point with its update count (updates = calls of its Kabsch)."""
-    from buffer_amd import icp
-    calls = [0]
-    orig = icp._kabsch
+def _kabsch_dev(p, q):
+    """rigid T (4x4 f64, numpy) minimising sum |R p + t - q|^2; p, q f64[n,3] device tensors."""
+    pc, qc = p.mean(0), q.mean(0)
+    H = ((p - pc).T @ (q - qc)).cpu().numpy()
+    U, _, Vt = np.linalg.svd(H)
+    D = np.diag([1.0, 1.0, np.sign(np.linalg.det(Vt.T @ U.T)) or 1.0])
+    R = Vt.T @ D @ U.T
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = qc.cpu().numpy() - R @ pc.cpu().numpy()
+    return T
 
-    def counted(p, q):
-        calls[0] += 1
-        return orig(p, q)
-    monkeypatch.setattr(icp, '_kabsch', counted)
-    T, fit, rmse, corr = icp.icp_point_to_point(src, tgt, dist, init, k, rf, rr)
-    monkeypatch.setattr(icp, '_kabsch', orig)
-    return T, fit, rmse, corr, calls[0]
+
+def _serial(src, tgt, dist, init, k, rf, rr):
+    """The reference: open3d's point-to-point loop on the host, one pair, three host round trips per iteration (nearest target
+    point = column 0 of ops.CellGrid.query, torch fp64 sums, numpy Kabsch) -> (T, fitness, rmse, corr, updates)."""
+    from buffer_amd import ops
+    dev = src.device
+    T = np.eye(4) if init is None else np.asarray(init, np.float64).copy()
+    n, m = int(src.shape[0]), int(tgt.shape[0])
+    if n == 0 or m == 0:
+        return T, 0.0, 0.0, np.zeros((0, 2), np.int32), 0
+    grid = ops.CellGrid(tgt.float().contiguous(), [m], float(dist))
+    src64, tgt64 = src.double(), tgt.double()
+
+    def correspond(Tn):
+        Tt = torch.from_numpy(Tn).to(dev)
+        moved = src64 @ Tt[:3, :3].T + Tt[:3, 3]
+        nn = grid.query(moved.float().contiguous(), [n], 1)[:, 0].long()
+        hit = torch.nonzero(nn < m).flatten()
+        if hit.numel() == 0:
+            return moved, hit, nn, 0.0, 0.0
+        d2 = ((moved[hit] - tgt64[nn[hit]]) ** 2).sum(1)
+        return moved, hit, nn, hit.numel() / n, float(torch.sqrt(d2.mean()).item())
+
+    moved, hit, nn, fit, rmse = correspond(T)
+    updates = 0
+    for _ in range(int(k)):
+        if hit.numel() < 3:
+            break
+        T = _kabsch_dev(moved[hit], tgt64[nn[hit]]) @ T
+        updates += 1
+        prev_fit, prev_rmse = fit, rmse
+        moved, hit, nn, fit, rmse = correspond(T)
+        if abs(prev_fit - fit) < rf and abs(prev_rmse - rmse) < rr:
+            break
+    corr = torch.stack([hit, nn[hit]], 1).to(torch.int32).cpu().numpy() if hit.numel() else np.zeros((0, 2), np.int32)
+    return T, float(fit), float(rmse), corr, updates
 
 
 @pytest.mark.gpu
-def test_parity_with_the_serial_point_to_point_loop(dev, monkeypatch):
+def test_parity_with_the_host_reference_point_to_point_loop(dev):
     from buffer_amd import icp
     srcs, tgts = _six_pairs()
     S, Tg = _dev_list(srcs, dev), _dev_list(tgts, dev)
     k = 6
     res = icp.icp_batched(S, Tg, 0.05, max_iteration=k, relative_fitness=0.0, relative_rmse=0.0)
     for b in range(6):
-        T, fit, rmse, _, it = _serial(S[b], Tg[b], 0.05, None, k, 0.0, 0.0, monkeypatch)
+        T, fit, rmse, _, it = _serial(S[b], Tg[b], 0.05, None, k, 0.0, 0.0)
         assert res[b]['iterations'] == it, (b, res[b]['iterations'], it)
         assert np.abs(res[b]['T'] - T).max() < 1e-7, b
         assert abs(res[b]['fitness'] - fit) < 1e-12 and abs(res[b]['inlier_rmse'] - rmse) < 1e-9, b
@@ -90,7 +125,7 @@ def test_parity_with_the_serial_point_to_point_loop(dev, monkeypatch):
     assert res[5]['fitness'] == 0.0 and res[5]['inlier_rmse'] == 0.0 and np.array_equal(res[5]['T'], np.eye(4))
     res = icp.icp_batched(S, Tg, 0.05, max_iteration=60)                  # default convergence criteria
     for b in range(6):
-        T, fit, rmse, _, it = _serial(S[b], Tg[b], 0.05, None, 60, 1e-6, 1e-6, monkeypatch)
+        T, fit, rmse, _, it = _serial(S[b], Tg[b], 0.05, None, 60, 1e-6, 1e-6)
         assert np.abs(res[b]['T'] - T).max() < 1e-6, b
         assert abs(res[b]['fitness'] - fit) < 1e-3, b
 
@@ -239,6 +274,24 @@ def test_edge_cases(dev):
 
 
 @pytest.mark.gpu
+def test_point_to_point_wrapper_edge_cases(dev):
+    from buffer_amd import icp
+    src, tgt, _ = _pair(62, 3000, 4000)
+    T0 = np.eye(4)
+    T0[:3, 3] = [0.01, 0.0, 0.0]
+    S, Tg = _dev_list([src, tgt], dev)
+    for a, b in ((S[:0], Tg), (S, Tg[:0])):                               # empty source, empty target
+        T, fit, rmse, corr = icp.icp_point_to_point(a, b, 0.05, T0)
+        assert np.array_equal(T, T0) and fit == 0.0 and rmse == 0.0
+        assert corr.shape == (0, 2) and corr.dtype == np.int32
+    with pytest.raises(RuntimeError):
+        icp.icp_point_to_point(torch.from_numpy(src), torch.from_numpy(tgt), 0.05)
+    src[::5] = np.nan
+    T, fit, rmse, corr = icp.icp_point_to_point(*_dev_list([src, tgt], dev), 0.05)
+    assert np.isfinite(T).all() and fit > 0.3 and not np.isin(corr[:, 0], np.arange(0, len(src), 5)).any()
+
+
+@pytest.mark.gpu
 def test_open3d_standin_point_to_plane_and_point_to_point(dev):
     import buffer_amd.shims as shims
     shims.install()
@@ -271,8 +324,19 @@ def test_kitti_refine_ground_truths_matches_the_serial_refinement(tmp_path, dev)
     _mini_sequence(root)
     serial = kitti.KittiTestSet(root, drives=(8,))
     n = len(serial)
-    want = [serial.ground_truth(i, dev) for i in range(n)]
+    want = []                                                              # the serial host refinement (_serial) of every pair
+    for i in range(n):
+        drive, t0, t1 = serial.files[i]
+        p0, p1 = (kitti.odometry_to_positions(o) for o in serial.odometry(drive)[[t0, t1]])
+        M = (kitti.VELO2CAM @ p0.T @ np.linalg.inv(p1.T) @ np.linalg.inv(kitti.VELO2CAM)).T
+        xyz0 = serial.scan(drive, t0).astype(np.float64) @ M[:3, :3].T + M[:3, 3]
+        T = _serial(*_dev_list([xyz0, serial.scan(drive, t1)], dev), 0.20, np.eye(4), 200, 1e-6, 1e-6)[0]
+        want.append(M @ T)
     icp_dir = os.path.join(root, 'icp')
+    one = [serial.ground_truth(i, dev) for i in range(n)]                  # a cache miss refines that pair alone
+    assert all(serial.gt_source[i] == 'icp-device' for i in range(n))
+    for i in range(n):
+        assert np.array_equal(np.load(os.path.join(icp_dir, '%d_%d_%d.npy' % serial.files[i])), one[i]), i
     for f in os.listdir(icp_dir):
         os.remove(os.path.join(icp_dir, f))
     keep = os.path.join(icp_dir, '%d_%d_%d.npy' % serial.files[0])
@@ -284,6 +348,7 @@ def test_kitti_refine_ground_truths_matches_the_serial_refinement(tmp_path, dev)
     for i in range(1, n):
         got = np.load(os.path.join(icp_dir, '%d_%d_%d.npy' % serial.files[i]))
         assert np.abs(got - want[i]).max() < 1e-6, i
+        assert np.array_equal(got, one[i]), i                              # ground_truth() and a batch of 2 write the same bits
         assert ds.gt_source[i] == 'icp-device'
         assert np.array_equal(ds.ground_truth(i), got) and ds.gt_source[i] == 'icp-device'
     for f in os.listdir(icp_dir):

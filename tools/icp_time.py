@@ -1,6 +1,6 @@
 """ICP on KITTI-shape ring scans before voxelisation (synth.make_kitti_pair(raw=True), ~120k returns per scan), the way
-kitti.KittiTestSet refines its ground truth (0.20 m, <= 200 iterations, relative criteria 1e-6): the serial
-icp.icp_point_to_point against icp.icp_batched at batch 1 and at batch --pairs.  The source scan starts from the true pose
+kitti.KittiTestSet refines its ground truth (0.20 m, <= 200 iterations, relative criteria 1e-6): icp.icp_batched at batch 1
+(one pair per call, as icp.icp_point_to_point runs it) and at batch --pairs.  The source scan starts from the true pose
 perturbed by a small error (odometry is close, not exact).  Times are HIP-event spans after a warm-up of every path.
 Prints one JSON line:  python tools/icp_time.py [--pairs 16]"""
 import argparse
@@ -46,24 +46,10 @@ def main():
         srcs.append(torch.from_numpy(xyz0.astype(np.float32)).to(dev))
         tgts.append(torch.from_numpy(s['tgt_raw'].astype(np.float32)).to(dev))
     kw = dict(max_iteration=a.max_iteration)
-    # warm-up of every path (code objects, allocator)
-    icp.icp_point_to_point(srcs[0], tgts[0], a.dist, np.eye(4), 3)
+    # warm-up of both paths (code objects, allocator)
     icp.icp_batched(srcs[:1], tgts[:1], a.dist, max_iteration=3)
     icp.icp_batched(srcs, tgts, a.dist, max_iteration=3)
 
-    calls = [0]
-    kabsch = icp._kabsch
-
-    def counted(p, q):
-        calls[0] += 1
-        return kabsch(p, q)
-    icp._kabsch = counted
-    serial, t_serial, it_serial = [], 0.0, []
-    for s, t in zip(srcs, tgts):
-        calls[0] = 0
-        r, ms = _span(lambda: icp.icp_point_to_point(s, t, a.dist, np.eye(4), a.max_iteration))
-        serial.append(r[0]); t_serial += ms; it_serial.append(calls[0])
-    icp._kabsch = kabsch
     one, t_one = [], 0.0
     for s, t in zip(srcs, tgts):
         r, ms = _span(lambda: icp.icp_batched([s], [t], a.dist, **kw)[0])
@@ -73,12 +59,10 @@ def main():
     B = len(srcs)
     print(json.dumps(dict(
         pairs=B, points_per_scan=int(np.mean([s.shape[0] for s in srcs])), max_dist=a.dist, max_iteration=a.max_iteration,
-        serial_ms_per_pair=t_serial / B, serial_ms_per_iteration=t_serial / max(sum(it_serial), 1),
         batch1_ms_per_pair=t_one / B, batch1_ms_per_iteration=t_one / max(sum(it1), 1),
         batched_ms_per_pair=t_batch / B, batched_ms_per_pair_iteration=t_batch / max(sum(itb), 1),
-        batched_rounds=max(itb) + 1, iterations_serial=it_serial, iterations_batched=itb,
+        batched_rounds=max(itb) + 1, iterations_batched=itb,
         iterations_batch1_equal_batched=it1 == itb,
-        max_abs_T_diff_serial_vs_batched=float(max(np.abs(x - y['T']).max() for x, y in zip(serial, batch))),
         max_abs_T_diff_batch1_vs_batched=float(max(np.abs(x['T'] - y['T']).max() for x, y in zip(one, batch))))))
 
 
