@@ -56,3 +56,16 @@ KITTI_TO_ETH = replace(THREEDMATCH_TO_ETH, voxel_size_1=0.30, inlier_th=2.0, wei
 KITTI_TO_3DLOMATCH = replace(Config(), dataset='3DLoMatch', voxel_size_1=0.30, keypts_th=0.0, weights='kitti')   # generalization/KITTI2ThreeD
 PRESETS = {'3DMatch': THREEDMATCH, 'KITTI': KITTI, '3DMatch->KITTI': THREEDMATCH_TO_KITTI, '3DMatch->ETH': THREEDMATCH_TO_ETH,
            'KITTI->ETH': KITTI_TO_ETH, 'KITTI->3DLoMatch': KITTI_TO_3DLOMATCH}
+# the presets each test-set driver runs: those whose TARGET data set it reads (the first is the driver's default)
+DRIVER_PRESETS = {'threedmatch': ('3DMatch', 'KITTI->3DLoMatch'), 'kitti': ('KITTI', '3DMatch->KITTI'),
+                  'eth': ('3DMatch->ETH', 'KITTI->ETH')}
+
+
+def preset(name, driver=None):
+    """PRESETS[name].  With `driver` ('threedmatch', 'kitti' or 'eth') only the presets of DRIVER_PRESETS[driver] are valid.
+    Any other name is a ValueError that lists the valid ones."""
+    valid = list(PRESETS) if driver is None else list(DRIVER_PRESETS[driver])
+    if name not in valid:
+        what = 'unknown preset' if name not in PRESETS else f'the {driver} driver does not read the target data set of preset'
+        raise ValueError(f'{what} {name!r}; valid presets: ' + ', '.join(valid))
+    return PRESETS[name]

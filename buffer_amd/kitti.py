@@ -184,19 +184,16 @@ def summarize(dataset, poses, rte_thresh=0.3, rre_thresh=1.0):
                 gt_source={k: src.count(k) for k in ('icp-cache', 'icp-device', 'odometry')})
 
 
-def main(argv=None):
-    """python -m buffer_amd.kitti --root <data root>   (one process per GPU under torchrun)"""
+def parse_args(argv=None):
+    """the command line of main() -> (args, Config of --preset)"""
     import argparse
-    import json
-    import time
 
-    import torch.distributed as dist
-
-    from . import dist as bdist
-    from .config import KITTI
-    from .pipeline import BufferPipeline
+    from .config import DRIVER_PRESETS, preset
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument('--root', required=True)
+    ap.add_argument('--preset', default=DRIVER_PRESETS['kitti'][0],
+                    help='constants and weights (buffer_amd/config.py): ' + ', '.join(DRIVER_PRESETS['kitti']) +
+                         ' (generalization/ThreeD2KITTI: 3DMatch weights, scale 10)')
     ap.add_argument('--batch', type=int, default=4)
     ap.add_argument('--limits', default=None)
     ap.add_argument('--allow-odometry-gt', action='store_true',
@@ -205,8 +202,27 @@ def main(argv=None):
                     help='only fill the ICP ground-truth cache <root>/icp/ (this rank\'s shard, --batch-icp pairs per call) and exit')
     ap.add_argument('--batch-icp', type=int, default=16)
     a = ap.parse_args(argv)
+    try:
+        cfg = preset(a.preset, 'kitti')
+    except ValueError as e:
+        ap.error(str(e))
+    return a, cfg
+
+
+def main(argv=None):
+    """python -m buffer_amd.kitti --root <data root> [--preset 3DMatch->KITTI]   (one process per GPU under torchrun).
+    Returns the poses f32[n,4,4] (numpy) on rank 0."""
+    import json
+    import time
+
+    import torch.distributed as dist
+
+    from . import dist as bdist
+    from .pipeline import BufferPipeline
+    a, cfg = parse_args(argv)
     rank, world, dev, cdev = bdist.init(int(os.environ.get('LOCAL_RANK', 0)))
-    ds = KittiTestSet(a.root, allow_odometry_gt=a.allow_odometry_gt)
+    ds = KittiTestSet(a.root, downsample=cfg.downsample, voxel_size_0=cfg.voxel_size_0, max_num_pts=cfg.max_num_pts,
+                      allow_odometry_gt=a.allow_odometry_gt)
     if a.refine_gt:
         ids = bdist.shard_indices(len(ds), rank, world)
         t0 = time.perf_counter()
@@ -215,7 +231,7 @@ def main(argv=None):
         if world > 1:
             dist.destroy_process_group()
         return
-    pipe = BufferPipeline(KITTI, dev)
+    pipe = BufferPipeline(cfg, dev)
     if a.limits:
         pipe.limits = [int(x) for x in a.limits.split(',')]
     else:
@@ -231,12 +247,14 @@ def main(argv=None):
     poses = bdist.gather_poses(ids, register_pairs(pipe, ds, ids, a.batch), len(ds), device=cdev)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    poses = poses.cpu().numpy()
     if rank == 0:
-        out = summarize(ds, poses.cpu().numpy())
-        out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits)
+        out = summarize(ds, poses)
+        out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+    return poses if rank == 0 else None
 
 
 if __name__ == '__main__':

@@ -249,6 +249,131 @@ def make_raw_pair_device(seed, overlap, device, n_raw=250_000, size=(1.9, 1.9, 1
     return out
 
 
+def _eth_primitives(rng, kind, half):
+    """The surfaces of one outdoor scene: (ground height function, list of (area weight, sampler(rng, n) -> f64[n,3]))."""
+    gx, gy = rng.uniform(-0.08, 0.08, 2)
+    p1, p2 = rng.uniform(0, 2 * np.pi, 2)
+
+    def h(x, y):                                                     # sloped, gently rolling ground
+        return gx * x + gy * y + 0.25 * np.sin(0.21 * x + p1) * np.cos(0.17 * y + p2)
+
+    def ground(rng, n):
+        x, y = rng.uniform(-half, half, (2, n))
+        return np.stack([x, y, h(x, y)], 1)
+
+    def cylinder(cx, cy, r, height):                                 # trunk or post
+        z0 = h(cx, cy)
+
+        def f(rng, n):
+            a, z = rng.uniform(0, 2 * np.pi, n), rng.uniform(0, height, n)
+            return np.stack([cx + r * np.cos(a), cy + r * np.sin(a), z0 + z], 1)
+        return 2 * np.pi * r * height, f
+
+    def blob(c, radii):                                              # canopy / shrub: points filling an ellipsoid, denser outside
+        def f(rng, n):
+            d = rng.normal(size=(n, 3))
+            d /= np.linalg.norm(d, axis=1, keepdims=True)
+            return c + d * radii * rng.uniform(0, 1, (n, 1)) ** 0.25
+        return 4 * np.pi * float(np.mean(radii)) ** 2, f
+
+    def wall(x0, y0, ang, length, height):
+        d = np.array([np.cos(ang), np.sin(ang)])
+
+        def f(rng, n):
+            s, t = rng.uniform(0, length, n), rng.uniform(0, height, n)
+            x, y = x0 + s * d[0], y0 + s * d[1]
+            return np.stack([x, y, h(x, y) + t], 1)
+        return length * height, f
+
+    prims = [((2 * half) ** 2, ground)]
+    if kind == 'wood':
+        for _ in range(70):
+            cx, cy = rng.uniform(-half, half, 2)
+            r, H = rng.uniform(0.12, 0.45), rng.uniform(6, 12)
+            prims.append(cylinder(cx, cy, r, H))
+            prims.append(blob(np.array([cx, cy, h(cx, cy) + H + rng.uniform(-1, 1)]), rng.uniform(1.5, 3.5, 3)))
+        for _ in range(40):
+            cx, cy = rng.uniform(-half, half, 2)
+            prims.append(blob(np.array([cx, cy, h(cx, cy) + 0.4]), rng.uniform(0.4, 1.2, 3)))
+    else:
+        for _ in range(3):                                           # gazebos: posts on a ring under a sloped roof
+            cx, cy = rng.uniform(-0.6 * half, 0.6 * half, 2)
+            R, H = rng.uniform(2.5, 4.5), rng.uniform(2.5, 3.2)
+            for a in np.linspace(0, 2 * np.pi, 8, endpoint=False):
+                prims.append(cylinder(cx + R * np.cos(a), cy + R * np.sin(a), 0.12, H))
+            z = h(cx, cy) + H
+            for sgn in (-1, 1):
+                o, u, v = np.array([cx - R, cy, z + 1.2]), np.array([2 * R, 0, 0]), np.array([0, sgn * (R + 0.5), -1.2])
+
+                def roof(rng, n, o=o, u=u, v=v):
+                    a, b = rng.uniform(0, 1, (2, n))
+                    return o + a[:, None] * u + b[:, None] * v
+                prims.append((float(np.linalg.norm(np.cross(u, v))), roof))
+        for _ in range(12):
+            x0, y0 = rng.uniform(-half, half, 2)
+            prims.append(wall(x0, y0, rng.uniform(0, np.pi), rng.uniform(4, 15), rng.uniform(1.5, 4)))
+        for _ in range(15):
+            cx, cy = rng.uniform(-half, half, 2)
+            prims.append(cylinder(cx, cy, rng.uniform(0.1, 0.3), rng.uniform(4, 9)))
+    return h, prims
+
+
+def make_eth_root(root, scenes=('gazebo_summer', 'wood_autmn'), stations=3, seed=0, n_raw=120_000, max_range=30.0, half=35.0,
+                  spacing=9.0, non_finite_rows=0):
+    """A mini ETH test set in the reference's layout (generalization/ThreeD2ETH/dataset.py:34-52): per scene `stations` terrestrial
+    scans written as <root>/<scene>/Hokuyo_<k>.ply (f32, each in its own scanner frame) and a tab-separated gt.log (the format
+    threedmatch.load_gt_log parses) with every pair i < j: T_i @ inv(T_j), T_k = world -> scan k, so that inv(gt) maps scan i
+    (source) into scan j (target).  Outdoor geometry: sloped ground over a 2*half m square; trunks with canopy clusters and shrubs for
+    `wood_*` scenes, gazebo posts and roofs, walls and poles otherwise.  Scanners stand `spacing` m apart on a line, 1.6 m above the
+    ground, yaw uniform, tilt <= 2 degrees; each sees up to `max_range` m with a point density falling off as 1/r (overlap is
+    partial), about n_raw returns, 1 cm range noise.  non_finite_rows > 0 appends that many NaN / inf rows to every scan (open3d's
+    reader drops them; so must ETHTestSet).  -> {scene: [T_k f64[4,4]]}.  Host-side numpy only."""
+    import os
+
+    from .threedmatch import write_ply
+    rng = np.random.default_rng(seed)
+    out = {}
+    for scene in scenes:
+        h, prims = _eth_primitives(rng, 'wood' if scene.startswith('wood') else 'gazebo', half)
+        area = np.array([a for a, _ in prims])
+        a0 = rng.uniform(0, 2 * np.pi)
+        c0 = rng.uniform(-5, 5, 2) - 0.5 * (stations - 1) * spacing * np.array([np.cos(a0), np.sin(a0)])
+        poses = []
+        for k in range(stations):
+            sxy = c0 + k * spacing * np.array([np.cos(a0), np.sin(a0)]) + rng.uniform(-1.5, 1.5, 2)
+            s = np.array([sxy[0], sxy[1], h(sxy[0], sxy[1]) + 1.6])
+            counts = rng.multinomial(5 * n_raw, area / area.sum())
+            pts = np.concatenate([f(rng, int(c)) for (_, f), c in zip(prims, counts) if c])
+            d = pts - s
+            r = np.linalg.norm(d, axis=1)
+            keep = (r > 1.0) & (r < max_range) & (rng.uniform(0, 1, r.shape[0]) < np.minimum(1.0, 6.0 / np.maximum(r, 1e-9)))
+            pts, d, r = pts[keep], d[keep], r[keep]
+            pts = pts + d / r[:, None] * rng.normal(scale=0.01, size=(r.shape[0], 1))      # range noise along the beam
+            if pts.shape[0] > n_raw:
+                pts = pts[np.sort(rng.choice(pts.shape[0], n_raw, replace=False))]
+            tilt = random_rotation(rng, np.deg2rad(2.0))
+            yaw = rng.uniform(-np.pi, np.pi)
+            R = tilt @ np.array([[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1]])
+            T = np.eye(4)
+            T[:3, :3], T[:3, 3] = R, -R @ s
+            poses.append(T)
+            scan = (pts @ R.T + T[:3, 3]).astype(np.float32)
+            if non_finite_rows:
+                bad = np.tile(np.array([[np.nan, 0, 0], [0, np.inf, 0], [0, 0, -np.inf]], np.float32), (non_finite_rows // 3 + 1, 1))
+                at = np.sort(rng.choice(scan.shape[0], non_finite_rows, replace=False))
+                scan = np.insert(scan, at, bad[:non_finite_rows], axis=0)
+            write_ply(os.path.join(root, scene, f'Hokuyo_{k}.ply'), scan)
+        with open(os.path.join(root, scene, 'gt.log'), 'w') as f:
+            for i in range(stations):
+                for j in range(i + 1, stations):
+                    G = poses[i] @ np.linalg.inv(poses[j])
+                    f.write(f'{i}\t{j}\t{stations}\n')
+                    for row in G:
+                        f.write('\t'.join(repr(float(x)) for x in row) + '\n')
+        out[scene] = poses
+    return out
+
+
 def information_matrix(points):
     """6x6 information matrix of a set of overlap points p (fragment-j frame), in the convention of the 3DMatch
     gt.info files that ThreeDMatch/test.py:92-111 consumes: for er = [t, q_xyz] (translation and quaternion vector part of

@@ -23,9 +23,11 @@ _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short':
               'double': 'f8', 'float64': 'f8'}
 
 
-def read_ply(path):
+def read_ply(path, drop_non_finite=False):
     """Vertex positions of a .ply point cloud (ascii, binary_little_endian or binary_big_endian) -> f32[n,3].
-    (open3d.io.read_point_cloud in utils/tools.py:6-7; only x, y, z are used by the reference.)"""
+    (open3d.io.read_point_cloud in utils/tools.py:6-7; only x, y, z are used by the reference.)
+    drop_non_finite: leave out every row with a NaN or inf coordinate, as open3d's read_point_cloud does by default
+    (remove_nan_points / remove_infinite_points); off by default, so a row reaches the caller as stored."""
     with open(path, 'rb') as f:
         if f.readline().strip() != b'ply':
             raise ValueError(f'{path}: not a PLY file')
@@ -66,7 +68,10 @@ def read_ply(path):
             cols = [rows[k] for k in 'xyz']
         else:
             raise ValueError(f'{path}: unknown PLY format {fmt}')
-    return np.stack(cols, axis=1).astype(np.float32)
+    pts = np.stack(cols, axis=1).astype(np.float32)
+    if drop_non_finite:
+        pts = np.ascontiguousarray(pts[np.isfinite(pts).all(axis=1)])
+    return pts
 
 
 def write_ply(path, pts):
@@ -196,9 +201,35 @@ def summarize(dataset, stats, log_root, log_name):
                 registration_recall=rr, per_scene=[float(x) for x in per_scene])
 
 
-def main(argv=None):
-    """python -m buffer_amd.threedmatch --root <data root> [--dataset 3DLoMatch]   (one process per GPU under torchrun)"""
+def parse_args(argv=None):
+    """the command line of main() -> (args, Config of --preset).  --dataset defaults to the preset's target data set."""
     import argparse
+    import time
+
+    from .config import DRIVER_PRESETS, preset
+    ap = argparse.ArgumentParser(description=main.__doc__)
+    ap.add_argument('--root', required=True)
+    ap.add_argument('--preset', default=DRIVER_PRESETS['threedmatch'][0],
+                    help='constants and weights (buffer_amd/config.py): ' + ', '.join(DRIVER_PRESETS['threedmatch']) +
+                         ' (generalization/KITTI2ThreeD: KITTI weights on the 3DLoMatch pairs)')
+    ap.add_argument('--dataset', default=None, choices=['3DMatch', '3DLoMatch'], help="default: the preset's target data set")
+    ap.add_argument('--log-root', default=None)
+    ap.add_argument('--log-name', default=time.strftime('%m%d%H%M') + '.log')
+    ap.add_argument('--batch', type=int, default=32)
+    ap.add_argument('--limits', default=None, help='frozen neighbourhood limits "a,b,c" (default: calibrate like dataloader.py:18-51)')
+    a = ap.parse_args(argv)
+    try:
+        cfg = preset(a.preset, 'threedmatch')
+    except ValueError as e:
+        ap.error(str(e))
+    if a.dataset is None:
+        a.dataset = cfg.dataset
+    return a, cfg
+
+
+def main(argv=None):
+    """python -m buffer_amd.threedmatch --root <data root> [--preset KITTI->3DLoMatch] [--dataset 3DLoMatch]   (one process per GPU
+    under torchrun).  Returns the poses f32[n,4,4] (numpy) on rank 0."""
     import json
     import time
 
@@ -206,17 +237,10 @@ def main(argv=None):
 
     from . import dist as bdist
     from .pipeline import BufferPipeline
-    ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument('--root', required=True)
-    ap.add_argument('--dataset', default='3DMatch', choices=['3DMatch', '3DLoMatch'])
-    ap.add_argument('--log-root', default=None)
-    ap.add_argument('--log-name', default=time.strftime('%m%d%H%M') + '.log')
-    ap.add_argument('--batch', type=int, default=32)
-    ap.add_argument('--limits', default=None, help='frozen neighbourhood limits "a,b,c" (default: calibrate like dataloader.py:18-51)')
-    a = ap.parse_args(argv)
+    a, cfg = parse_args(argv)
     rank, world, dev, cdev = bdist.init(int(os.environ.get('LOCAL_RANK', 0)))
-    ds = ThreeDMatchTestSet(a.root, a.dataset)
-    pipe = BufferPipeline(device=dev)
+    ds = ThreeDMatchTestSet(a.root, a.dataset, downsample=cfg.downsample, voxel_size_0=cfg.voxel_size_0, max_num_pts=cfg.max_num_pts)
+    pipe = BufferPipeline(cfg, dev)
     if a.limits:
         pipe.limits = [int(x) for x in a.limits.split(',')]
     else:
@@ -232,14 +256,16 @@ def main(argv=None):
     poses = bdist.gather_poses(ids, register_pairs(pipe, ds, ids, a.batch), len(ds), device=cdev)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    poses = poses.cpu().numpy()
     if rank == 0:
         log_root = a.log_root or f'log_{a.dataset}'
-        stats = write_logs(ds, poses.cpu().numpy(), log_root, a.log_name)
+        stats = write_logs(ds, poses, log_root, a.log_name)
         out = summarize(ds, stats, log_root, a.log_name)
-        out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits)
+        out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+    return poses if rank == 0 else None
 
 
 if __name__ == '__main__':
