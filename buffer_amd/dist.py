@@ -165,6 +165,38 @@ def gather_poses(local_ids, local_poses, n_pairs, device=None, extra=None, expli
     return (out, ext) if E else out
 
 
+def gather_counts(local_ids, local_counts, n_pairs, device=None):
+    """The integer sibling of gather_poses for the per-stage metric rows: all ranks call; local_counts int32[k,C] for the pairs
+    local_ids = shard_indices(n_pairs, rank, world) in order (k = 0 is fine) -> int32[n_pairs,C] on every rank, row i = the
+    counts of pair i, -1 ("not evaluated") where nothing was reported.  ONE all_gather of an int32 [cap, C] block per rank; the
+    counts travel as integers, never through a float block."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    local_counts = torch.as_tensor(local_counts, dtype=torch.int32)
+    device = device or local_counts.device
+    cap = (n_pairs + world - 1) // world
+    k = len(local_ids)
+    if list(local_ids) != shard_indices(n_pairs, rank, world):
+        raise ValueError('gather_counts: local_ids are not shard_indices(n_pairs, rank, world)')
+    if local_counts.dim() != 2 or local_counts.shape[0] != k:
+        raise ValueError(f'gather_counts: {k} local pairs but counts of shape {tuple(local_counts.shape)}')
+    ncol = int(local_counts.shape[1])
+    buf = torch.full((cap, ncol), -1, dtype=torch.int32, device=device)
+    if k:
+        buf[:k] = local_counts.to(device)
+    if world > 1:
+        parts = [torch.empty_like(buf) for _ in range(world)]
+        dist.all_gather(parts, buf)
+    else:
+        parts = [buf]
+    out = torch.full((n_pairs, ncol), -1, dtype=torch.int32, device=device)
+    for r in range(world):
+        ids = shard_indices(n_pairs, r, world)
+        if ids:
+            out[torch.as_tensor(ids, dtype=torch.long, device=device)] = parts[r][:len(ids)]
+    return out
+
+
 def broadcast_limits(limits, device='cpu'):
     """neighbourhood limits are calibrated once (rank 0) and shared, so every rank truncates identically."""
     t = torch.as_tensor(list(limits), dtype=torch.int64, device=device)

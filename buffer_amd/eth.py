@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import evaluate, preprocess
-from .threedmatch import load_gt_log, read_ply, register_pairs   # register_pairs: the batched path of the 3DMatch driver
+from .threedmatch import load_gt_log, read_ply, register_pairs, stage_report   # register_pairs: the batched path of the 3DMatch driver
 
 SCENES = ['gazebo_summer', 'gazebo_winter', 'wood_autmn', 'wood_summer']      # dataset.py:34-39 (the reference's spelling)
 
@@ -92,6 +92,10 @@ def parse_args(argv=None):
     ap.add_argument('--scenes', nargs='+', default=None, help='default: ' + ' '.join(SCENES))
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--limits', default=None, help='frozen neighbourhood limits "a,b,c" (default: calibrate like dataloader.py:18-51)')
+    ap.add_argument('--stage-metrics', action='store_true',
+                    help='also compute the per-stage ground-truth metrics (repeatability, inlier ratio, FMR, consensus precision): '
+                         'summary key "stage", per-pair rows in <log-root>/stage_metrics.json')
+    ap.add_argument('--log-root', default=None, help='where --stage-metrics writes stage_metrics.json (default: log_ETH)')
     a = ap.parse_args(argv)
     try:
         cfg = preset(a.preset, 'eth')
@@ -126,13 +130,19 @@ def main(argv=None):
         pipe.limits = bdist.broadcast_limits(pipe.limits if rank == 0 else [0, 0, 0], device=cdev)
     ids = bdist.shard_indices(len(ds), rank, world)
     t0 = time.perf_counter()
-    poses = bdist.gather_poses(ids, register_pairs(pipe, ds, ids, a.batch), len(ds), device=cdev)
+    res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics)
+    poses = bdist.gather_poses(ids, res[0] if a.stage_metrics else res, len(ds), device=cdev)
+    counts = bdist.gather_counts(ids, res[1].to(cdev), len(ds), device=cdev).cpu().numpy() if a.stage_metrics else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     poses = poses.cpu().numpy()
     if rank == 0:
         out = summarize(ds, poses)
         out.update(preset=a.preset, pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits)
+        if a.stage_metrics:
+            out['stage'] = stage_report([ds.scene(i) for i in range(len(ds))], counts, cfg.num_keypts)
+            evaluate.write_stage_metrics(os.path.join(a.log_root or 'log_ETH', 'stage_metrics.json'), [f'{s} {t}' for s, t in ds.files],
+                                         counts, cfg.num_keypts, out['stage'])
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

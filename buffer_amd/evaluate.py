@@ -103,3 +103,50 @@ def dgr_success(pose_est, pose_gt, rte_thresh=0.3, rre_thresh=15.0):
     rte = np.linalg.norm(pose_est[:3, 3] - pose_gt[:3, 3])
     rre = np.arccos(np.clip((np.trace(pose_est[:3, :3].T @ pose_gt[:3, :3]) - 1) / 2, -1 + 1e-16, 1 - 1e-16)) * 180 / math.pi
     return bool(rte < rte_thresh and rre < rre_thresh), float(rte), float(rre)
+
+
+STAGE_COLUMNS = ('rep_src', 'rep_tgt', 'nn_inl', 'mutual', 'mutual_inl', 'cons', 'cons_true')     # ops.METRIC_COLUMNS, host side
+
+
+def stage_summary(counts, P, fmr_ratio=0.05):
+    """Per-stage metrics of a set of pairs from their count rows (BufferPipeline.register_batch(..., metrics_gt=), brought to the
+    host): counts int[n,7] in the column order STAGE_COLUMNS, P keypoints per cloud.  A row of -1 is a pair that was not
+    evaluated (it never reached matching); such rows are left out of every figure and counted in `not_evaluated`.
+    -> dict(pairs            evaluated pairs,
+            not_evaluated    rows of -1,
+            repeatability    mean of (rep_src + rep_tgt) / 2P: keypoints with a keypoint of the other cloud nearby under the truth,
+            inlier_ratio     mean of nn_inl / P: putative (1-NN, no mutual check) matches that are right,
+            fmr              Feature Matching Recall: the share of pairs with nn_inl / P > fmr_ratio (strict; 0.05 is the 3DMatch
+                             benchmark's customary ratio -- a parameter of the metric),
+            mutual_inlier_ratio   mean of mutual_inl / mutual: mutual matches that are right,
+            consensus_precision   mean of cons_true / cons: members of the returned pose's consensus set that are right).
+    A ratio with a zero denominator (no mutual match, an empty consensus set, P = 0) counts as 0 for that pair; with no evaluated
+    pair every figure is 0."""
+    c = np.asarray(counts, np.int64).reshape(-1, len(STAGE_COLUMNS))
+    ok = ~(c < 0).any(axis=1)
+    e = c[ok].astype(np.float64)
+    col = {k: e[:, i] for i, k in enumerate(STAGE_COLUMNS)}
+
+    def ratio(num, den):
+        den = np.broadcast_to(np.asarray(den, np.float64), num.shape)
+        return np.divide(num, den, out=np.zeros_like(num), where=den > 0)
+
+    def mean(x):
+        return float(x.mean()) if x.size else 0.0
+
+    inl = ratio(col['nn_inl'], float(P))
+    return dict(pairs=int(ok.sum()), not_evaluated=int((~ok).sum()),
+                repeatability=mean(ratio(col['rep_src'] + col['rep_tgt'], 2.0 * P)), inlier_ratio=mean(inl),
+                fmr=mean((inl > fmr_ratio).astype(np.float64)),
+                mutual_inlier_ratio=mean(ratio(col['mutual_inl'], col['mutual'])),
+                consensus_precision=mean(ratio(col['cons_true'], col['cons'])))
+
+
+def write_stage_metrics(path, ids, counts, P, summary):
+    """<log root>/stage_metrics.json: the per-pair count rows in data-set order (ids: one label per pair) and the summary dict."""
+    import json
+    c = np.asarray(counts, np.int64).reshape(-1, len(STAGE_COLUMNS))
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(dict(columns=list(STAGE_COLUMNS), num_keypts=int(P), summary=summary,
+                       pairs=[dict(id=str(ids[i]), counts=[int(v) for v in c[i]]) for i in range(c.shape[0])]), f, indent=1)

@@ -155,7 +155,10 @@ class KittiTestSet:
         return out
 
 
-def register_pairs(pipe, dataset, indices, batch=4):
+def register_pairs(pipe, dataset, indices, batch=4, stage_metrics=False):
+    """This rank's share of the pairs through the device pipeline -> f32[k,4,4] (device), in the order of `indices`.
+    stage_metrics: also the per-stage metric rows against the data set's ground truth (BufferPipeline.register_batch,
+    metrics_gt=) -> (poses, counts int32[k,7] on the device); the poses are the same."""
     dev = pipe.device
     poses = []
     idx = list(indices)
@@ -163,9 +166,19 @@ def register_pairs(pipe, dataset, indices, batch=4):
     # stage run beside the CNN kernels of batch i (BufferPipeline.register_batches; results equal batch-by-batch calls)
     chunks = [idx[lo:lo + batch] for lo in range(0, len(idx), batch)]
     makers = [(lambda ch=ch: [upload(s) for s in items_batched(dataset, ch, dev)]) for ch in chunks]
-    for ps in pipe.register_batches(makers, seeds=chunks):
+    if not stage_metrics:
+        for ps in pipe.register_batches(makers, seeds=chunks):
+            poses += ps
+        return torch.stack(poses) if poses else torch.zeros((0, 4, 4), dtype=torch.float32, device=dev)
+    # each chunk's ground truth rides along (read when the chunk's fragments are): one metric launch per chunk after its pose recovery
+    gts = [(lambda ch=ch: [dataset.meta(i, dev)['relt_pose'] for i in ch]) for ch in chunks]
+    counts = []
+    for ps, cs in pipe.register_batches(makers, seeds=chunks, metrics_gt=gts):
         poses += ps
-    return torch.stack(poses) if poses else torch.zeros((0, 4, 4), dtype=torch.float32, device=dev)
+        counts.append(cs)
+    if not poses:
+        return torch.zeros((0, 4, 4), dtype=torch.float32, device=dev), torch.zeros((0, 7), dtype=torch.int32, device=dev)
+    return torch.stack(poses), torch.cat(counts)
 
 
 def summarize(dataset, poses, rte_thresh=0.3, rre_thresh=1.0):
@@ -201,6 +214,10 @@ def parse_args(argv=None):
     ap.add_argument('--refine-gt', action='store_true',
                     help='only fill the ICP ground-truth cache <root>/icp/ (this rank\'s shard, --batch-icp pairs per call) and exit')
     ap.add_argument('--batch-icp', type=int, default=16)
+    ap.add_argument('--stage-metrics', action='store_true',
+                    help='also compute the per-stage ground-truth metrics (repeatability, inlier ratio, FMR, consensus precision): '
+                         'summary key "stage", per-pair rows in <log-root>/stage_metrics.json')
+    ap.add_argument('--log-root', default=None, help='where --stage-metrics writes stage_metrics.json (default: log_KITTI)')
     a = ap.parse_args(argv)
     try:
         cfg = preset(a.preset, 'kitti')
@@ -244,13 +261,20 @@ def main(argv=None):
         pipe.limits = bdist.broadcast_limits(pipe.limits if rank == 0 else [0, 0, 0], device=cdev)
     ids = bdist.shard_indices(len(ds), rank, world)
     t0 = time.perf_counter()
-    poses = bdist.gather_poses(ids, register_pairs(pipe, ds, ids, a.batch), len(ds), device=cdev)
+    res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics)
+    poses = bdist.gather_poses(ids, res[0] if a.stage_metrics else res, len(ds), device=cdev)
+    counts = bdist.gather_counts(ids, res[1].to(cdev), len(ds), device=cdev).cpu().numpy() if a.stage_metrics else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     poses = poses.cpu().numpy()
     if rank == 0:
         out = summarize(ds, poses)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
+        if a.stage_metrics:
+            from . import evaluate
+            out['stage'] = evaluate.stage_summary(counts, cfg.num_keypts)
+            evaluate.write_stage_metrics(os.path.join(a.log_root or 'log_KITTI', 'stage_metrics.json'),
+                                         ['%d %d %d' % f for f in ds.files], counts, cfg.num_keypts, out['stage'])
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

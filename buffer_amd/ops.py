@@ -553,6 +553,33 @@ def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='po
     return T, fit, rmse, iters, (nn[:int(src.shape[0])] if nn is not None else None)
 
 
+METRIC_COLUMNS = ('rep_src', 'rep_tgt', 'nn_inl', 'mutual', 'mutual_inl', 'cons', 'cons_true')      # BUF_METRICS_* of buffer_hip.h
+
+
+def match_metrics(kp, s_nn, t_nn, T_gt, T_est, tau_kp, tau_match, dist_th, want_d2=False):
+    """buf_match_metrics: the per-stage ground-truth counts of B pairs in one launch, nothing read back.
+    kp f32[2*B*P,3] (pair b: source rows [2bP, 2bP+P), target rows [(2b+1)P, (2b+2)P)), s_nn / t_nn int[B,P] descriptor-space 1-NN
+    (source -> target row and the reverse), T_gt [B,4,4] (taken as f64), T_est [B,4,4] (f32) -> counts int32[B,7] on the device,
+    columns METRIC_COLUMNS; with want_d2 also f32[2*B*P], the squared distance of every keypoint to the nearest keypoint of the
+    pair's other cloud under the ground truth."""
+    L = _lib.lib()
+    kp = _dev(kp, torch.float32, "match_metrics.kp")
+    s_nn, t_nn = _dev(s_nn, torch.int32, "match_metrics.s_nn"), _dev(t_nn, torch.int32, "match_metrics.t_nn")
+    if s_nn.dim() != 2 or s_nn.shape != t_nn.shape:
+        raise ValueError(f"match_metrics: s_nn {tuple(s_nn.shape)} and t_nn {tuple(t_nn.shape)} must both be [B,P]")
+    B, P = int(s_nn.shape[0]), int(s_nn.shape[1])
+    if kp.dim() != 2 or tuple(kp.shape) != (2 * B * P, 3):
+        raise ValueError(f"match_metrics: kp {tuple(kp.shape)} is not [2*{B}*{P},3]")
+    dev = kp.device
+    T_gt = torch.as_tensor(T_gt, dtype=torch.float64).to(dev).reshape(B, 4, 4).contiguous()
+    T_est = _dev(T_est, torch.float32, "match_metrics.T_est").reshape(B, 4, 4).contiguous()
+    counts = torch.empty((B, len(METRIC_COLUMNS)), dtype=torch.int32, device=dev)
+    d2 = torch.empty((2 * B * P,), dtype=torch.float32, device=dev) if want_d2 else None
+    check(L.buf_match_metrics(_ptr(kp), _ptr(s_nn), _ptr(t_nn), B, P, _ptr(T_gt), _ptr(T_est), float(tau_kp), float(tau_match),
+                              float(dist_th), _ptr(counts), _ptr(d2), _stream()), "buf_match_metrics")
+    return (counts, d2) if want_d2 else counts
+
+
 def recover_poses_batched(ind, ss_kpts, tt_kpts, ss_R, tt_R, seg_lengths, seeds, cfg):
     """hypotheses + scoring + RANSAC + refinement of every pair of a step in one set of launches: the matches of the pairs are
     stacked, pair p owns seg_lengths[p] consecutive rows -> poses f32[nb,4,4] (identity for pairs with fewer than 3 matches)."""

@@ -49,9 +49,12 @@ class BufferPipeline:
         return dict(points=pts, lengths=lens, features=feats, src_raw=src_raw, tgt_raw=tgt_raw)
 
     @torch.no_grad()
-    def register(self, inp, seed=0, perms=None, detail=False):
-        """inp from upload() -> pose f32[4,4] (src -> tgt), device tensor."""
+    def register(self, inp, seed=0, perms=None, detail=False, metrics_gt=None, tau_kp=None, tau_match=None, dist_th=None):
+        """inp from upload() -> pose f32[4,4] (src -> tgt), device tensor.
+        metrics_gt: the pair's ground-truth 4x4 (src -> tgt) -> (pose, counts int32[7] on the device), the pair's row of the
+        per-stage metrics (register_batch); with detail=True the row is out['stage_counts'] instead.  The pose is the same."""
         cfg = self.cfg
+        met = None if metrics_gt is None else self._metric_args([metrics_gt], tau_kp, tau_match, dist_th)
         if self.limits is None:
             raise RuntimeError('neighbourhood limits not calibrated: call calibrate() or pass limits=')
         pyr = pyramid.build_pyramid(inp['points'], inp['lengths'], self.limits, cfg)
@@ -66,7 +69,7 @@ class BufferPipeline:
             a = orient_axes(axis[lo:hi], p)
             keep = ops.compact_greater(score[lo:hi, 0], cfg.keypts_th).long()       # BUFFER.py:255-259
             if keep.shape[0] == 0:
-                return self._identity(out, detail)
+                return self._identity(out, detail, met)
             cand_p.append(p[keep]); cand_a.append(a[keep])
         # both fragments sampled in one launch, one workgroup per cloud (BUFFER.py:266-271)
         fps = ops.furthest_point_sample_ragged(torch.cat(cand_p), [c.shape[0] for c in cand_p], cfg.num_keypts).long()
@@ -84,7 +87,7 @@ class BufferPipeline:
         res = [{k: (v[i * P:(i + 1) * P] if v is not None else None) for k, v in emb.items()} for i in range(2)]
         s_mids, t_mids = registration.mutual_matching(res[0]['desc'], res[1]['desc'])
         if s_mids.shape[0] < 3:
-            return self._identity(out, detail)
+            return self._identity(out, detail, met)
         ss_kpts, tt_kpts = kp[0][s_mids].contiguous(), kp[1][t_mids].contiguous()
         e = cfg.ele_n
         ind = self.inlier(res[0]['equi'][s_mids][:, :, 1:e - 1].contiguous(),
@@ -92,31 +95,53 @@ class BufferPipeline:
         pose, diag = registration.recover_pose(ind, ss_kpts, tt_kpts, res[0]['R'][s_mids].contiguous(),
                                                res[1]['R'][t_mids].contiguous(), cfg, seed)
         self.check_range()
+        if met is not None:                                 # the batched kernel at B = 1 from this pair's own state (two more 1-NN
+            _, s_idx = ops.knn(res[1]['desc'][None], res[0]['desc'][None], 1)      # launches: mutual_matching keeps no full rows)
+            _, t_idx = ops.knn(res[0]['desc'][None], res[1]['desc'][None], 1)
+            out['stage_counts'] = ops.match_metrics(torch.cat(kp), s_idx[:, :, 0], t_idx[:, :, 0], met['gt'], pose[None], met['tau_kp'],
+                                                    met['tau_match'], met['dist_th'])[0]
         if detail:
             out.update(dict(pyr=pyr, axis=axis, eps=eps, score=score, kpts=kp, kaxis=ka, desc=res, s_mids=s_mids,
                             t_mids=t_mids, ind=ind, **diag))
             return pose, out
-        return pose
+        return pose if met is None else (pose, out['stage_counts'])
 
     @torch.no_grad()
-    def register_batch(self, inps, seeds=None, perms=None):
+    def register_batch(self, inps, seeds=None, perms=None, metrics_gt=None, tau_kp=None, tau_match=None, dist_th=None):
         """Several pairs through ONE set of launches per stage (the MI355X-native form: the pyramid, the VN
         blocks, FPS (one workgroup per cloud), patch selection, voxelisation, both CNNs and the 1-NN search all take the
         stacked batch; only the per-pair pose recovery loops).  inps: list of upload() dicts ->
-        list of pose f32[4,4] device tensors.  Per pair the arithmetic is that of register()."""
-        poses = self._describe_and_match(self._keypoints(inps, seeds, perms))
+        list of pose f32[4,4] device tensors.  Per pair the arithmetic is that of register().
+
+        metrics_gt: the B ground-truth poses (src -> tgt, [B,4,4] or a list of 4x4; host or device) switches the per-stage
+        metrics on -> (poses, counts), counts int32[B,7] ON THE DEVICE (columns ops.METRIC_COLUMNS: rep_src, rep_tgt, nn_inl,
+        mutual, mutual_inl, cons, cons_true; evaluate.stage_summary turns host rows into ratios).  One more kernel
+        (buf_match_metrics) is enqueued after pose recovery on the same stream, from the keypoints and 1-NN rows the batch already
+        holds; nothing is read back here (.cpu() is the caller's) and the poses are bit-identical to a call without metrics_gt.
+        A pair that never reaches matching -- a cloud with no point above keypts_th, or fewer than 3 mutual matches, i.e. the
+        pairs answered with the identity -- gets -1 in every column ("not evaluated", as opposed to a count of zero).
+        tau_kp (repeatability distance) and tau_match (match inlier distance) default to cfg.dist_th, the inlier distance of the
+        configuration's data set; dist_th (consensus distance of the returned pose) is cfg.dist_th unless overridden."""
+        met = None if metrics_gt is None else self._metric_args(metrics_gt, tau_kp, tau_match, dist_th, len(inps))
+        st = self._keypoints(inps, seeds, perms)
+        if met is not None:
+            st['metrics'] = met
+        res = self._describe_and_match(st)
         self.check_range()
-        return poses
+        return res
 
     @torch.no_grad()
-    def register_batches(self, batches, seeds=None):
+    def register_batches(self, batches, seeds=None, metrics_gt=None, tau_kp=None, tau_match=None, dist_th=None):
         """A sequence of batches, software-pipelined over two HIP streams: the keypoint stage of batch i+1 (pyramid, point
         learner, FPS -- short kernels, FPS latency-bound on 2B of the 256 CUs) is enqueued on a high-priority side stream
         BEFORE the descriptor / matching stage of batch i goes onto the current stream, so it runs beside the chip-filling
         CNN kernels instead of in front of them.  Results are those of register_batch batch by batch.
         batches: list of lists of upload() dicts -- or of callables returning such a list, which are then evaluated on the side
         stream as part of the keypoint stage (device pre-processing of the next batch beside the CNN kernels of this one);
-        seeds: list of lists -> list of lists of poses."""
+        seeds: list of lists -> list of lists of poses.
+        metrics_gt: one entry per batch, each the batch's ground-truth poses as in register_batch (or a callable returning them,
+        evaluated when the batch is) -> list of (poses, counts int32[B,7] on the device) per batch; the metric kernel of a batch
+        follows its pose recovery on the current stream, so the two-stream overlap is as without it."""
         dev = self.device
         main = torch.cuda.current_stream(dev)
         if not hasattr(self, '_kp_stream'):
@@ -128,7 +153,14 @@ class BufferPipeline:
         def stage1(i):
             with torch.cuda.stream(side):
                 inps = batches[i]() if callable(batches[i]) else batches[i]
+                met = None
+                if metrics_gt is not None:                 # (uploaded before the keypoint stage is queued: the copy waits for nothing)
+                    gt = metrics_gt[i]() if callable(metrics_gt[i]) else metrics_gt[i]
+                    met = self._metric_args(gt, tau_kp, tau_match, dist_th, len(inps))
                 st = self._keypoints(inps, seeds[i], None)
+                if met is not None:
+                    st['metrics'] = met
+                    st['cross'] = tuple(st.get('cross', ())) + (met['gt'],)
                 if callable(batches[i]):                   # inputs made on the side stream are read on the current one too
                     st['cross'] = tuple(st.get('cross', ())) + tuple(v for x in inps for v in x.values() if isinstance(v, torch.Tensor))
                 ev = torch.cuda.Event()
@@ -199,9 +231,18 @@ class BufferPipeline:
         poses = [None] * B
         if 'starved' in st:
             bad = st['starved']
+            met = st.get('metrics')
+            rows = [None] * B
             for b in (b for b in range(B) if b not in bad):        # redo the healthy pairs one by one
-                poses[b] = self.register(inps[b], seed=seeds[b], perms=perms[b] if perms is not None else None)
+                pb = perms[b] if perms is not None else None
+                if met is None:
+                    poses[b] = self.register(inps[b], seed=seeds[b], perms=pb)
+                else:
+                    poses[b], rows[b] = self.register(inps[b], seed=seeds[b], perms=pb, metrics_gt=met['gt'][b], tau_kp=met['tau_kp'],
+                                                      tau_match=met['tau_match'], dist_th=met['dist_th'])
             st['poses'] = [p if p is not None else torch.eye(4, device=dev) for p in poses]
+            if met is not None:
+                st['poses'] = (st['poses'], torch.stack([r if r is not None else self._no_counts() for r in rows]))
             return st
         kp, ka = st['kp'], st['ka']
         P = cfg.num_keypts
@@ -218,7 +259,7 @@ class BufferPipeline:
         _, t_idx = ops.knn(desc[:, 0].contiguous(), desc[:, 1].contiguous(), 1)
         s_nn, t_nn = s_idx[:, :, 0], t_idx[:, :, 0]
         st['mutual'] = t_nn.gather(1, s_nn) == torch.arange(P, device=dev)[None]
-        st['s_nn'], st['emb'] = s_nn, emb
+        st['s_nn'], st['t_nn'], st['emb'] = s_nn, t_nn, emb
         return st
 
     def _match(self, st):
@@ -242,8 +283,36 @@ class BufferPipeline:
         # hypotheses, all-vs-all scoring, RANSAC and refinement of all B pairs: one set of launches (csrc/registration.hip,
         # batched section), bit-identical to the pair-by-pair recover_pose of register()
         all_poses = ops.recover_poses_batched(ind, ss_all, tt_all, sR_all, tR_all, m_counts, seeds, cfg)
-        return [all_poses[b] for b in range(B)]
+        poses = [all_poses[b] for b in range(B)]
+        met = st.get('metrics')
+        if met is None:
+            return poses
+        counts = ops.match_metrics(kp, s_nn, st['t_nn'], met['gt'], all_poses, met['tau_kp'], met['tau_match'], met['dist_th'])
+        lost = np.nonzero(m_counts < 3)[0]                  # answered with the identity: never reached pose recovery
+        if lost.size:
+            counts[torch.from_numpy(lost).to(dev)] = -1
+        return poses, counts
 
-    def _identity(self, out, detail):
+    def _metric_args(self, gt, tau_kp, tau_match, dist_th, B=1):
+        """ground truth [B,4,4] (list of 4x4 / array / tensor, host or device) as f64 on the device + the three thresholds"""
+        if isinstance(gt, (list, tuple)):
+            gt = np.stack([g.cpu().numpy() if isinstance(g, torch.Tensor) else np.asarray(g) for g in gt]).astype(np.float64) \
+                if len(gt) else np.zeros((0, 4, 4))
+        gt = torch.as_tensor(gt).to(self.device, torch.float64)
+        if tuple(gt.shape) != (B, 4, 4):
+            raise ValueError(f'metrics_gt: expected {B} ground-truth 4x4 poses, got shape {tuple(gt.shape)}')
+        d = float(self.cfg.dist_th)
+        return dict(gt=gt.contiguous(), tau_kp=d if tau_kp is None else float(tau_kp), tau_match=d if tau_match is None else float(tau_match),
+                    dist_th=d if dist_th is None else float(dist_th))
+
+    def _no_counts(self):
+        """the count row of a pair that was not evaluated"""
+        return torch.full((len(ops.METRIC_COLUMNS),), -1, dtype=torch.int32, device=self.device)
+
+    def _identity(self, out, detail, met=None):
         pose = torch.eye(4, device=self.device)       # ThreeDMatch/test.py:242-245: failed pair -> identity
-        return (pose, out) if detail else pose
+        if met is not None:
+            out['stage_counts'] = self._no_counts()
+        if detail:
+            return pose, out
+        return pose if met is None else (pose, out['stage_counts'])

@@ -164,8 +164,10 @@ def upload(sample):
                 lengths=np.array([src.shape[0], tgt.shape[0]], np.int32), src_raw=sample['src_fds_pts'], tgt_raw=sample['tgt_fds_pts'])
 
 
-def register_pairs(pipe, dataset, indices, batch=32):
-    """This rank's share of the pairs through the device pipeline -> f32[k,4,4] (device), in the order of `indices`."""
+def register_pairs(pipe, dataset, indices, batch=32, stage_metrics=False):
+    """This rank's share of the pairs through the device pipeline -> f32[k,4,4] (device), in the order of `indices`.
+    stage_metrics: also the per-stage metric rows against the data set's ground truth (BufferPipeline.register_batch,
+    metrics_gt=) -> (poses, counts int32[k,7] on the device); the poses are the same."""
     dev = pipe.device
     poses = []
     idx = list(indices)
@@ -173,9 +175,19 @@ def register_pairs(pipe, dataset, indices, batch=32):
     # stage run beside the CNN kernels of batch i (BufferPipeline.register_batches; results equal batch-by-batch calls)
     chunks = [idx[lo:lo + batch] for lo in range(0, len(idx), batch)]
     makers = [(lambda ch=ch: [upload(s) for s in items_batched(dataset, ch, dev)]) for ch in chunks]
-    for ps in pipe.register_batches(makers, seeds=chunks):
+    if not stage_metrics:
+        for ps in pipe.register_batches(makers, seeds=chunks):
+            poses += ps
+        return torch.stack(poses) if poses else torch.zeros((0, 4, 4), dtype=torch.float32, device=dev)
+    # each chunk's ground truth rides along (read when the chunk's fragments are): one metric launch per chunk after its pose recovery
+    gts = [(lambda ch=ch: [dataset.meta(i, dev)['relt_pose'] for i in ch]) for ch in chunks]
+    counts = []
+    for ps, cs in pipe.register_batches(makers, seeds=chunks, metrics_gt=gts):
         poses += ps
-    return torch.stack(poses) if poses else torch.zeros((0, 4, 4), dtype=torch.float32, device=dev)
+        counts.append(cs)
+    if not poses:
+        return torch.zeros((0, 4, 4), dtype=torch.float32, device=dev), torch.zeros((0, 7), dtype=torch.int32, device=dev)
+    return torch.stack(poses), torch.cat(counts)
 
 
 def write_logs(dataset, poses, log_root, log_name):
@@ -201,6 +213,16 @@ def summarize(dataset, stats, log_root, log_name):
                 registration_recall=rr, per_scene=[float(x) for x in per_scene])
 
 
+def stage_report(scene_of, counts, P, fmr_ratio=0.05):
+    """evaluate.stage_summary of all pairs and per scene (scene_of: one scene name per row of counts, data-set order)
+    -> dict(overall figures..., per_scene={scene: figures})"""
+    counts = np.asarray(counts).reshape(-1, 7)
+    scene_of = np.asarray(list(scene_of), dtype=object)
+    out = evaluate.stage_summary(counts, P, fmr_ratio)
+    out['per_scene'] = {s: evaluate.stage_summary(counts[scene_of == s], P, fmr_ratio) for s in dict.fromkeys(scene_of.tolist())}
+    return out
+
+
 def parse_args(argv=None):
     """the command line of main() -> (args, Config of --preset).  --dataset defaults to the preset's target data set."""
     import argparse
@@ -217,6 +239,9 @@ def parse_args(argv=None):
     ap.add_argument('--log-name', default=time.strftime('%m%d%H%M') + '.log')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--limits', default=None, help='frozen neighbourhood limits "a,b,c" (default: calibrate like dataloader.py:18-51)')
+    ap.add_argument('--stage-metrics', action='store_true',
+                    help='also compute the per-stage ground-truth metrics (repeatability, inlier ratio, FMR, consensus precision): '
+                         'summary key "stage", per-pair rows in <log-root>/stage_metrics.json')
     a = ap.parse_args(argv)
     try:
         cfg = preset(a.preset, 'threedmatch')
@@ -253,7 +278,9 @@ def main(argv=None):
         pipe.limits = bdist.broadcast_limits(pipe.limits if rank == 0 else [0, 0, 0], device=cdev)
     ids = bdist.shard_indices(len(ds), rank, world)
     t0 = time.perf_counter()
-    poses = bdist.gather_poses(ids, register_pairs(pipe, ds, ids, a.batch), len(ds), device=cdev)
+    res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics)
+    poses = bdist.gather_poses(ids, res[0] if a.stage_metrics else res, len(ds), device=cdev)
+    counts = bdist.gather_counts(ids, res[1].to(cdev), len(ds), device=cdev).cpu().numpy() if a.stage_metrics else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     poses = poses.cpu().numpy()
@@ -262,6 +289,10 @@ def main(argv=None):
         stats = write_logs(ds, poses, log_root, a.log_name)
         out = summarize(ds, stats, log_root, a.log_name)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
+        if a.stage_metrics:
+            out['stage'] = stage_report([f[0].split(os.sep)[-2] for f in ds.files], counts, cfg.num_keypts)
+            evaluate.write_stage_metrics(os.path.join(log_root, 'stage_metrics.json'), [f'{s} {t}' for s, t in ds.files], counts,
+                                         cfg.num_keypts, out['stage'])
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -464,6 +464,44 @@ int     buf_icp_batched(const float* src, const int* src_lengths_host, const flo
                         int max_iteration, double rel_fitness, double rel_rmse, double* T_out_f64, double* fitness_out,
                         double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream);
 
+/* N3  Per-stage ground-truth metrics of B registered pairs (a diagnostic beside the registration path: keypoint repeatability,
+ * inlier counts of the putative and the mutual matches, the consensus set of the returned pose).  One launch, nothing read back.
+ * kp f32[2*B*P,3]: the keypoints in the batched pipeline's layout, pair b owns rows [2bP, 2bP+P) (source) and [(2b+1)P, (2b+2)P)
+ * (target); s_nn / t_nn int32[B,P]: descriptor-space 1-NN of every source keypoint among the pair's target keypoints and the
+ * reverse (rows of the pair's own cloud, 0..P-1; an index outside that range matches nothing); T_gt_f64 f64[B,4,4] ground truth
+ * src -> tgt; T_est_f32 f32[B,4,4] the returned pose (widened to fp64 exactly).
+ * Arithmetic (a numpy restatement gives the same bits, the convention of buf_icp_batched):
+ *   p = T s in fp64 without FMA, ((r0*x + r1*y) + r2*z) + t per row, rounded to fp32;
+ *   d2 = (dx*dx + dy*dy) + dz*dz in fp32; a point is within tau when d2 < (float)tau * (float)tau (strict);
+ *   the inverse of T_gt is formed on the device in fp64 as [R^T, -R^T t] with tinv_i = -((R0i*t0 + R1i*t1) + R2i*t2), and applied
+ *   in the same operation order; non-finite points are within nothing (their d2 is NaN or inf and fails every comparison);
+ *   the nearest keypoint is the running minimum over ascending rows with a strict <, so the lowest row keeps a tie.
+ * out_counts int32[B, BUF_METRICS_NCOUNT], per pair:
+ *   REP_SRC     source keypoints whose nearest target keypoint under T_gt is within tau_kp
+ *   REP_TGT     target keypoints whose nearest source keypoint under the inverse of T_gt is within tau_kp
+ *   NN_INL      source keypoints s with |T_gt kp_s - kp_tgt[s_nn[s]]| within tau_match (putative = 1-NN, no mutual check: the count
+ *               behind Feature Matching Recall)
+ *   MUTUAL      mutual matches, t_nn[s_nn[s]] == s
+ *   MUTUAL_INL  mutual matches within tau_match under T_gt
+ *   CONS        mutual matches within dist_th under T_est (the consensus set of the returned pose)
+ *   CONS_TRUE   of those, the ones also within tau_match under T_gt
+ * out_nn_d2 (nullable) f32[2*B*P]: the fp32 d2 from every keypoint (kp's row order) to its nearest keypoint of the pair's other
+ * cloud under the ground truth; +inf where there is none (non-finite points).
+ * Integer atomics only: results are bitwise reproducible and independent of the other pairs of the batch.
+ * BUF_EINVAL before any device work for npairs < 0 or P < 0, a threshold that is not finite and > 0, and a null required pointer
+ * with npairs * P > 0; npairs == 0 or P == 0 succeeds and touches nothing. */
+#define BUF_METRICS_NCOUNT     7
+#define BUF_METRICS_REP_SRC    0
+#define BUF_METRICS_REP_TGT    1
+#define BUF_METRICS_NN_INL     2
+#define BUF_METRICS_MUTUAL     3
+#define BUF_METRICS_MUTUAL_INL 4
+#define BUF_METRICS_CONS       5
+#define BUF_METRICS_CONS_TRUE  6
+int     buf_match_metrics(const float* kp, const int* s_nn, const int* t_nn, int npairs, int P, const double* T_gt_f64,
+                          const float* T_est_f32, float tau_kp, float tau_match, float dist_th, int* out_counts,
+                          float* out_nn_d2 /* nullable */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
