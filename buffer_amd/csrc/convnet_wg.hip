@@ -5,10 +5,11 @@
 // into 48 input channels), circular in azimuth and zero-padded in elevation (utils/common.py:265-310).  With the map cut
 // into 4 x 10 tiles of 2 x 2 outputs,
 //     Y = A^T [ sum_c (G g G^T)[c] (.) (B^T d[c] B) ] A          (d: the tile's 4 x 4 input window)
-// turns the 9-tap implicit GEMM (9 x 144 rows per channel pair) into 16 component GEMMs over tile rows.  The bottom tile row
-// (output row 6; row 7 does not exist and window rows 7, 8 are padding) is the plain two-tap form in elevation for the M-tile
-// that holds nothing else: 8 components (wg_round_bottom).  16 + 16 + 8 = 40 matrix instructions per (4 input, 16 output
-// channels) against 75 of the direct form.  All arithmetic stays fp32 (v_mfma_f32_16x16x4_f32); the filter transform is done
+// turns the 9-tap implicit GEMM (9 x 144 rows per channel pair) into 16 component GEMMs over tile rows.  Output row 6 (row 7
+// does not exist and window rows 7, 8 are padding) runs in the DIRECT form for its columns 0..15, the M-tile that holds nothing
+// else: two filter rows x three azimuth taps on 16 positions, 6 full matrix instructions (wg_round_direct).  16 + 16 + 6 = 38
+// matrix instructions per (4 input, 16 output channels), 27 968 per patch of the released stack, against 75 of the direct form
+// throughout.  All arithmetic stays fp32 (v_mfma_f32_16x16x4_f32); the filter transform is done
 // once on the host in fp64.
 //
 // One workgroup owns one patch for the whole stack.  Activations live in ONE LDS buffer [128][160] (rows of 22 = 20 azimuth
@@ -22,9 +23,9 @@
 //   * 128 output channels (52 % of the MFMAs): a wavefront owns an N-tile PAIR and one transform feeds the 8 MFMAs of both
 //     (1.06 VALU per MFMA in the loop).  The layer is in place -- the outputs of a pair (80 registers) wait until every
 //     wavefront has read its input, in accumulation registers -- and the M-tiles run in two rounds: both Winograd tiles (64
-//     accumulator registers), then the bottom row.
-//   * 64 output channels: pairs as well, by splitting M -- a wavefront owns an N-tile pair for ONE Winograd M-tile plus the bottom
-//     row of one N-tile (32 + 8 MFMAs per k-step for every wavefront, nothing to exchange).  32 output channels: the same inside
+//     accumulator registers), then row 6.
+//   * 64 output channels: pairs as well, by splitting M -- a wavefront owns an N-tile pair for ONE Winograd M-tile plus row 6
+//     of one N-tile (32 + 6 MFMAs per k-step for every wavefront, nothing to exchange).  32 output channels: the same inside
 //     each half of K (the two wavefronts of a K split hand their partial sums over through the free upper rows of the buffer).
 // The filter stream: weights come through a buffer resource with wavefront-uniform offsets (a global_load_dwordx4 with a
 // 64-bit VGPR address costs ~50 cycles of SIMD issue beside MFMAs, an SGPR-based one ~10: tools/micro/mfma_vmem.hip), tiled
@@ -34,10 +35,10 @@
 // through the four passes and after each pass the column transform of the running sum is folded into the 2 x 2 outputs in
 // registers (the C/D layout keeps a tile in one lane).
 // LDS banking (ds_read_b64: bank = word mod 64, lanes 0-31 and 32-63 served separately): the 40 tiles are dealt to the
-// three M-tiles such that the 16 lanes of a k-step channel cover 32 distinct banks, and the channel stride 160 = 32 mod 64
+// two Winograd M-tiles such that the 16 lanes of a k-step channel cover 32 distinct banks, and the channel stride 160 = 32 mod 64
 // puts the second channel of the half-wave on the other 32:
 //     M-tile 0: tile row 0 (10) + tile row 1, columns 4..9     M-tile 1: tile row 2 (10) + row 1, columns 0..3 + row 3, columns 8, 9
-//     M-tile 2: tile row 3, columns 0..7 (8 lanes idle)
+//     M-tile 2: output row 6, columns 0..15, one position per lane (no tiles: wg_round_direct has its own reads)
 #include "common.h"
 #include <type_traits>
 
@@ -81,18 +82,20 @@ __device__ long long* wg_stamp_ptr;
 #define WG_STAMP_IN(SLOT)
 #endif
 
-// tile (ty, tx) held by row idx of M-tile t (branch-free)
+// tile (ty, tx) held by row idx of the Winograd M-tile t = 0, 1 (branch-free)
 __device__ __forceinline__ bool wg_tile(int t, int idx, int& ty, int& tx)
 {
     if (t == 0) { const bool a = idx < 10; ty = a ? 0 : 1; tx = a ? idx : idx - 6; return true; }
     if (t == 1) { const bool a = idx < 10, b = idx < 14; ty = a ? 2 : (b ? 1 : 3); tx = a ? idx : (b ? idx - 10 : idx - 6); return true; }
-    ty = 3; tx = idx & 7;
-    return idx < 8;
+    ty = 3; tx = 0;                                            // M-tile 2 holds no tiles: output row 6 in the direct form (wg_round_direct)
+    return false;
 }
 
-// LDS byte address of window row a (0..3) of the tile that lane (li, lk) holds in M-tile t, for the lane's channel of k-step 0
+// LDS byte address of window row a (0..3) of the tile that lane (li, lk) holds in M-tile t, for the lane's channel of k-step 0.
+// M-tile 2 is position-indexed: lane li is output column li of row 6, its window rows are 5 and 6 (a = 0, 1) from the halo word on.
 __device__ __forceinline__ unsigned wg_row_addr(unsigned act_addr, int t, int a, int li, int lk)
 {
+    if (t == 2) return act_addr + 4u * (unsigned)(lk * WG_CS + (a < 2 ? (5 + a) * WG_ROW + li : WG_ZERO));
     int ty, tx;
     const bool ok = wg_tile(t, li, ty, tx);
     const int row = 2 * ty - 1 + a;
@@ -104,19 +107,13 @@ __device__ __forceinline__ unsigned wg_row_addr(unsigned act_addr, int t, int a,
 __device__ __forceinline__ float wg_add(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float wg_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
-// Window rows (A1, A2) of row component I and the number of M-tiles it runs over in [T0, T1)
+// Window rows (A1, A2) of row component I
 __host__ __device__ constexpr int wg_a1(int I) { return I == 0 ? 0 : 1; }
 __host__ __device__ constexpr int wg_a2(int I) { return I == 3 ? 3 : 2; }
-__host__ __device__ constexpr int wg_te(int I, int T1) { return (I == 3 && T1 == 3) ? 2 : T1; }   // M-tile 2: bottom tile row only, component 3 unused
 
-// Does the pass of row component I (M-tiles [T0, T1)) hand its successor I + 1 the first two LDS steps?  Only where steps 0
-// and 1 have the same (k-step, M-tile) shape in both passes.
-__host__ __device__ constexpr bool wg_chains(int I, int T0, int T1)
-{
-    if (I < 0 || I >= 3) return false;
-    const int nt = wg_te(I, T1) - T0, ntn = wg_te(I + 1, T1) - T0;
-    return nt >= 1 && ntn >= 1 && (1 / nt) == (1 / ntn) && (1 % nt) == (1 % ntn);
-}
+// Does the pass of row component I hand its successor I + 1 the first two LDS steps?  (Every pass of a round has the same
+// (k-step, M-tile) step shape.)
+__host__ __device__ constexpr bool wg_chains(int I) { return I >= 0 && I < 3; }
 
 // LDS reads of one step.  Two ds_read_b64 per row: the empty asm keeps the compiler from fusing them into the half-rate
 // ds_read2_b64.
@@ -132,18 +129,6 @@ __host__ __device__ constexpr bool wg_chains(int I, int T0, int T1)
         asm volatile("" : "+v"(A1_));                                                                     \
     }
 
-// one window row only (the bottom-row form)
-#define WG_LOAD1(DST, A0, OFS)                                                                            \
-    {                                                                                                     \
-        DST[0] = *(wg_lds_f2)(size_t)((A0) + (OFS));                                                      \
-        asm volatile("" : "+v"(A0));                                                                      \
-        DST[1] = *(wg_lds_f2)(size_t)((A0) + (OFS) + 8);                                                  \
-        asm volatile("" : "+v"(A0));                                                                      \
-    }
-#define WG_LOAD(BOT_, DST, A0, A1_, OFS)                                                                  \
-    {                                                                                                     \
-        if constexpr (BOT_) WG_LOAD1(DST, A0, OFS) else WG_LOAD2(DST, A0, A1_, OFS)                       \
-    }
 
 // A lane's 16 bytes of a weight block through a buffer resource: wavefront-uniform byte offset (SGPR) + the lane's 32-bit offset.
 // The form matters: global_load_dwordx4 with a 64-bit VGPR address costs ~50 cycles of the SIMD's issue beside MFMAs, an
@@ -172,24 +157,21 @@ __device__ __forceinline__ wgf4 wg_ldw(__amdgpu_buffer_rsrc_t rs, unsigned unifo
 // Weights: W[n][k-step & 1], a ring of TWO k-steps per N-tile -- the registers of a k-step are reloaded with the k-step two
 // further on (of this pass, or of whatever runs next: wp_next) as soon as its MFMAs are through, so every load is issued two
 // k-steps before its use with half the registers of a whole-iteration buffer (the paired layers were spilling their outputs).
-template <int I, int NN, int T0, int T1, bool PRIMED, int INEXT, bool BOT = false, unsigned KSTEP = WG_KSTEP, bool DIFF = false>
+template <int I, int NN, int T0, int T1, bool PRIMED, int INEXT, unsigned KSTEP = WG_KSTEP>
 __device__ __forceinline__ void wg_pass(unsigned (&RA)[3][4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_next, unsigned lofs, int niter,
-                                        int wstride, wgf4 (&W)[NN][2], wgf4 (&acc)[NN][3][4], wgf2 (&D)[2][4], wgf4 (*Wb)[2] = nullptr, unsigned bofs = 0)
+                                        int wstride, wgf4 (&W)[NN][2], wgf4 (&acc)[NN][3][4], wgf2 (&D)[2][4])
 {
-    constexpr int A1 = BOT ? I : wg_a1(I), A2 = BOT ? I : wg_a2(I);      // bottom-row form: I is the filter row = window row, no second row
-    constexpr int TE = BOT ? T1 : wg_te(I, T1);
-    constexpr int NT = TE > T0 ? TE - T0 : 1;
-    if constexpr (TE <= T0) return;
-    constexpr int A1N = BOT ? (INEXT < 0 ? 0 : INEXT) : wg_a1(INEXT < 0 ? 0 : INEXT), A2N = BOT ? A1N : wg_a2(INEXT < 0 ? 0 : INEXT);
-    constexpr int NTN = (INEXT < 0 || BOT) ? NT : (wg_te(INEXT, T1) - T0);
-    static_assert(INEXT < 0 || (NTN >= 1 && (1 / NT) == (1 / NTN) && (1 % NT) == (1 % NTN)), "steps 0 and 1 of the chained pass have this pass's shape");
+    static_assert(T0 < T1 && T1 <= 2, "the Winograd M-tiles (M-tile 2 is wg_round_direct's)");
+    constexpr int A1 = wg_a1(I), A2 = wg_a2(I);
+    constexpr int NT = T1 - T0;
+    constexpr int A1N = wg_a1(INEXT < 0 ? 0 : INEXT), A2N = wg_a2(INEXT < 0 ? 0 : INEXT);
     float V[2][4];
     unsigned P[NT][2];
 #pragma unroll
     for (int t = 0; t < NT; t++) { P[t][0] = RA[T0 + t][A1]; P[t][1] = RA[T0 + t][A2]; }
     if constexpr (!PRIMED) {
 #pragma unroll
-        for (int g = 0; g < 2; g++) WG_LOAD(BOT, D[g], P[g % NT][0], P[g % NT][1], (g / NT) * KSTEP)
+        for (int g = 0; g < 2; g++) WG_LOAD2(D[g], P[g % NT][0], P[g % NT][1], (g / NT) * KSTEP)
     }
     // row component (d0 - d2 | d1 + d2 | d2 - d1 | d1 - d3), then the four column components
 #define WG_XFORM(BUF)                                                                                     \
@@ -197,11 +179,8 @@ __device__ __forceinline__ void wg_pass(unsigned (&RA)[3][4], __amdgpu_buffer_rs
         float r_[4];                                                                                      \
         _Pragma("unroll") for (int b = 0; b < 4; b++) {                                                   \
             const float da_ = D[BUF][b >> 1][b & 1];                                                      \
-            if constexpr (BOT) r_[b] = da_;                                                               \
-            else {                                                                                        \
-                const float db_ = D[BUF][2 + (b >> 1)][b & 1];                                            \
-                r_[b] = I == 1 ? wg_add(da_, db_) : (I == 2 ? wg_sub(db_, da_) : wg_sub(da_, db_));       \
-            }                                                                                             \
+            const float db_ = D[BUF][2 + (b >> 1)][b & 1];                                                \
+            r_[b] = I == 1 ? wg_add(da_, db_) : (I == 2 ? wg_sub(db_, da_) : wg_sub(da_, db_));           \
         }                                                                                                 \
         V[BUF][0] = wg_sub(r_[0], r_[2]); V[BUF][1] = wg_add(r_[1], r_[2]);                               \
         V[BUF][2] = wg_sub(r_[2], r_[1]); V[BUF][3] = wg_sub(r_[1], r_[3]);                               \
@@ -217,47 +196,28 @@ __device__ __forceinline__ void wg_pass(unsigned (&RA)[3][4], __amdgpu_buffer_rs
 #pragma unroll
         for (int s = 0; s < 4 * NT; s++) {
             const int t = T0 + s % NT, kk = s / NT, g = s + 2;
-            if (g < 4 * NT) WG_LOAD(BOT, D[s & 1], P[g % NT][0], P[g % NT][1], (g / NT) * KSTEP)
+            if (g < 4 * NT) WG_LOAD2(D[s & 1], P[g % NT][0], P[g % NT][1], (g / NT) * KSTEP)
             else {
                 const int t2 = (g - 4 * NT) % NT;                // the next iteration's base from here on (this one no longer reads through it)
                 if ((g - 4 * NT) / NT == 0) { P[t2][0] += adv; P[t2][1] += adv; }
                 if constexpr (INEXT >= 0) {                      // last iteration: the next pass's first steps instead
                     unsigned q0 = more ? P[t2][0] : RA[T0 + t2][A1N], q1 = more ? P[t2][1] : RA[T0 + t2][A2N];
-                    WG_LOAD(BOT, D[s & 1], q0, q1, ((g - 4 * NT) / NT) * KSTEP)
+                    WG_LOAD2(D[s & 1], q0, q1, ((g - 4 * NT) / NT) * KSTEP)
                 } else
-                    WG_LOAD(BOT, D[s & 1], P[t2][0], P[t2][1], ((g - 4 * NT) / NT) * KSTEP)
+                    WG_LOAD2(D[s & 1], P[t2][0], P[t2][1], ((g - 4 * NT) / NT) * KSTEP)
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DIFF) {                                // the filter block is the difference of two stored ones (wg_round_bottom)
-                wgf4 wd[NN];
 #pragma unroll
-                for (int n = 0; n < NN; n++)
+            for (int n = 0; n < NN; n++)
 #pragma unroll
-                    for (int j = 0; j < 4; j++) wd[n][j] = wg_sub(W[n][kk & 1][j], Wb[n][kk & 1][j]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int n = 0; n < NN; n++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        acc[n][t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wd[n][j], V[s & 1][j], acc[n][t][j], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int n = 0; n < NN; n++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        acc[n][t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(W[n][kk & 1][j], V[s & 1][j], acc[n][t][j], 0, 0, 0);
-            }
+                for (int j = 0; j < 4; j++)
+                    acc[n][t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(W[n][kk & 1][j], V[s & 1][j], acc[n][t][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             WG_XFORM((s + 1) & 1)
             if (s % NT == NT - 1) {                              // k-step kk is through: its registers take the k-step two further on
 #pragma unroll
                 for (int n = 0; n < NN; n++)
                     W[n][kk & 1] = kk < 2 ? wg_ldw(rs, wcur + n * 256 + (kk + 2) * wstride, lofs) : wg_ldw(rs, wn + n * 256 + (kk - 2) * wstride, lofs);
-                if constexpr (DIFF) {                            // (past the pass: the same offset behind whatever runs next -- unused, in bounds)
-#pragma unroll
-                    for (int n = 0; n < NN; n++)
-                        Wb[n][kk & 1] = kk < 2 ? wg_ldw(rs, wcur + bofs + n * 256 + (kk + 2) * wstride, lofs) : wg_ldw(rs, wn + bofs + n * 256 + (kk - 2) * wstride, lofs);
-                }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -298,23 +258,20 @@ __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_r
             for (int j = 0; j < 4; j++) acc[n][t][j] = (wgf4){ zero, zero, zero, zero };
     auto run = [&](auto ic) __attribute__((always_inline)) {
         constexpr int I = decltype(ic)::value;
-        // component 3 does nothing for a round that only has M-tile 2: the pass before it hands over to whatever runs next
-        constexpr int INEXT = (I == 3 || (I == 2 && wg_te(3, T1) <= T0)) ? 0 : I + 1;
+        constexpr int INEXT = I == 3 ? 0 : I + 1;
         if constexpr (I == 1) {
 #pragma unroll
             for (int n = 0; n < NN; n++)
 #pragma unroll
                 for (int t = T0; t < T1; t++) acc[n][t][1] += bv[n];
         }
-        constexpr int ICHAIN = (INEXT != 0 && wg_chains(I, T0, T1)) ? INEXT : -1;      // the next row component of this round, if any
-        wg_pass<I, NN, T0, T1, wg_chains(I - 1, T0, T1), ICHAIN, false, KSTEP>(RA, rs, wp + I * pstride, INEXT == 0 ? wp_after : wp + (I + 1) * pstride, lofs, niter, wstride, W, acc, D);
+        constexpr int ICHAIN = (INEXT != 0 && wg_chains(I)) ? INEXT : -1;      // the next row component of this round, if any
+        wg_pass<I, NN, T0, T1, wg_chains(I - 1), ICHAIN, KSTEP>(RA, rs, wp + I * pstride, INEXT == 0 ? wp_after : wp + (I + 1) * pstride, lofs, niter, wstride, W, acc, D);
         if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);     // k_cost_net: the fold is not mixed into the next pass's start (spills)
 #pragma unroll
         for (int n = 0; n < NN; n++)
 #pragma unroll
             for (int t = T0; t < T1; t++) {
-                if (I == 3 && t == 2) continue;
-                if (I == 2 ? false : t == 2) continue;          // M-tile 2 (bottom tile row) only has output row 0 = F_2
                 const wgf4 f0 = acc[n][t][0] + acc[n][t][1] + acc[n][t][2];
                 const wgf4 f1 = acc[n][t][1] - acc[n][t][2] - acc[n][t][3];
                 if constexpr (I == 0) { Y[n][t][1][0] = f0; Y[n][t][1][1] = f1; }                 // F_0 (enters with a minus sign below)
@@ -341,46 +298,112 @@ __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_r
     run(integral_constant<int, 3>{});
 }
 
-// M-tile 2 is the bottom tile row: its window rows 2 and 3 are elevation padding and its second output row (7) does not
-// exist, so its one output row is the plain two-tap form in elevation
-//     y[6] = A^T-columns of sum_c ( colB(d[5]) (.) colG(g[0]) + colB(d[6]) (.) colG(g[1]) ),
-// two passes of four column components (8 tile-components instead of the 12 the row components 0..2 took, and no row
-// combination in the input transform).  colG(g[0]) is the Winograd block i = 0; colG(g[1]) = U_1 - U_2 is formed in registers
-// from the blocks 1 and 2 as they arrive (4 subtractions per N-tile and k-step, a second weight ring): stored as a fifth
-// block it made the filter set 3.8 MB -- more than the 4 MB L2 of an XCD holds beside the activation stream, and the kernel's
-// HBM-side traffic went from 47 to 85 KB per patch.  The four accumulators run through both taps; the bias starts in component 1.
+// M-tile 2 is output row 6, columns 0..15 (columns 16..19 are the two Winograd tiles that ride in M-tile 1), in the DIRECT form: its
+// window ends in the elevation padding (row 7), so two filter rows x three azimuth taps are all there is,
+//     y[o][6][p] = b[o] + sum_c sum_{a = 0, 1} sum_{b = 0, 1, 2} g[o][c][a][b] * x[c][5 + a][p - 1 + b],          p = 0..15
+// and the 16 positions fill the M-tile: 6 matrix instructions per (4 input, 16 output channels) where the eight Winograd tiles of
+// these positions took 8 in half-empty ones.  Lane (li, lk) holds position p = li and channel lk of the k-step; a tap's operand is an
+// LDS word as it stands (row * 22 + p + {0, 1, 2}: the halo word in front of column 0 serves p - 1 at p = 0) -- no input transform,
+// no output fold.  The reads are 4-byte ones: nothing aligns p.  Within one read the 16 lanes of a channel are on consecutive banks;
+// the two channels of a half-wave share them (ds_read_b32 banks by word mod 32 and the channel stride is 0 mod 32), a two-way
+// conflict on 6 reads per k-step that the LDS has room for.
+// The six taps are formed in registers from the Winograd blocks the filter set already has, U_ij = (G g G^T)_ij:
+//     g[0][0] = U_00    g[0][1] = U_01 - U_02    g[0][2] = U_03        and with D_j = U_1j - U_2j
+//     g[1][0] = D_0     g[1][1] = D_1 - D_2      g[1][2] = D_3
+// (six subtractions per N-tile and k-step.  Nothing is stored for this round: a fifth block, U_1 - U_2, once made the filter set
+// 3.8 MB -- more than the 4 MB L2 of an XCD holds beside the activation stream -- and the kernel's HBM-side traffic went from 47
+// to 85 KB per patch.)
+// One accumulator per filter row, K ascending, taps b = 0, 1, 2 in this order within a k-step -- the same for every N-tile and layer
+// form; the bias starts in row 0's accumulator and the two are added once at the end.  (Two chains per N-tile: the dependent latency
+// of v_mfma_f32_16x16x4_f32 is 40 cycles against 32 of issue, and a wavefront with one N-tile has nothing else to put between.)
+// Steps are k-steps, pipelined as in wg_pass: the MFMAs of step s back to back, then the LDS reads of step s + 2 into the operand
+// registers just consumed, then the taps of step s + 1, whose weight registers (a ring of two k-steps per block) are reloaded with
+// the k-step two further on.  On entry W holds block 0's first two k-steps (the look-ahead of the round before).
+typedef const __attribute__((address_space(3))) float* wg_lds_f1;
+#define WG_LOADD(DST, A0, OFS)                                                                            \
+    {                                                                                                     \
+        _Pragma("unroll") for (int a_ = 0; a_ < 2; a_++)                                                  \
+            _Pragma("unroll") for (int b_ = 0; b_ < 3; b_++)                                              \
+                DST[a_ * 3 + b_] = *(wg_lds_f1)(size_t)((A0) + (OFS) + 4 * (a_ * WG_ROW + b_));           \
+    }
 template <int NN>
-__device__ __forceinline__ void wg_round_bottom(unsigned (&RA)[3][4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_after, unsigned lofs, int niter,
-                                                int wstride, unsigned pstride, const float* __restrict__ bias_lane, wgf4 (&W)[NN][2], wgf4 (&Y)[NN][3][2][2])
+__device__ __forceinline__ void wg_round_direct(unsigned row5, __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned lofs, int niter, int wstride,
+                                                unsigned pstride, const float* __restrict__ bias_lane, wgf4 (&W)[NN][2], wgf4 (&Y)[NN])
 {
-    wgf2 D[2][4];
-    wgf4 acc[NN][3][4];
+    wgf4 Wr[3][NN][2];                                          // blocks 0..2, two k-steps each
+#pragma unroll
+    for (int n = 0; n < NN; n++)
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            Wr[0][n][k] = W[n][k];
+            Wr[1][n][k] = wg_ldw(rs, wp + pstride + n * 256 + k * wstride, lofs);
+            Wr[2][n][k] = wg_ldw(rs, wp + 2 * pstride + n * 256 + k * wstride, lofs);
+        }
+    float X[2][6];                                              // window words [row 5 | row 6][tap] of two steps in flight
+    unsigned pa = row5;
+    WG_LOADD(X[0], pa, 0)
+    WG_LOADD(X[1], pa, WG_KSTEP)
+    wgf4 acc[NN][2];
     float zero = 0.f;
     asm volatile("" : "+v"(zero));
 #pragma unroll
-    for (int n = 0; n < NN; n++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            acc[n][2][j] = (j == 1 && bias_lane) ? *reinterpret_cast<const wgf4*>(bias_lane + n * 16) : (wgf4){ zero, zero, zero, zero };
-    wgf4 Wb[NN][2];                                             // block 2's first two k-steps (block 1's arrive through tap 0's look-ahead)
-#pragma unroll
-    for (int n = 0; n < NN; n++)
-#pragma unroll
-        for (int k = 0; k < 2; k++) Wb[n][k] = wg_ldw(rs, wp + 2 * pstride + n * 256 + k * wstride, lofs);
-    wg_pass<0, NN, 2, 3, false, 1, true>(RA, rs, wp, wp + pstride, lofs, niter, wstride, W, acc, D);
-    wg_pass<1, NN, 2, 3, true, -1, true, WG_KSTEP, true>(RA, rs, wp + pstride, wp_after, lofs, niter, wstride, W, acc, D, Wb, pstride);
-#pragma unroll
     for (int n = 0; n < NN; n++) {
-        Y[n][2][0][0] = acc[n][2][0] + acc[n][2][1] + acc[n][2][2];
-        Y[n][2][0][1] = acc[n][2][1] - acc[n][2][2] - acc[n][2][3];
+        acc[n][0] = bias_lane ? *reinterpret_cast<const wgf4*>(bias_lane + n * 16) : (wgf4){ zero, zero, zero, zero };
+        acc[n][1] = (wgf4){ zero, zero, zero, zero };
     }
+    float G[NN][6];
+#define WG_TAPS(SLOT)                                                                                     \
+    _Pragma("unroll") for (int n = 0; n < NN; n++) {                                                      \
+        const wgf4 u0_ = Wr[0][n][SLOT], u1_ = Wr[1][n][SLOT], u2_ = Wr[2][n][SLOT];                      \
+        const float d1_ = wg_sub(u1_[1], u2_[1]), d2_ = wg_sub(u1_[2], u2_[2]);                           \
+        G[n][0] = u0_[0]; G[n][1] = wg_sub(u0_[1], u0_[2]); G[n][2] = u0_[3];                             \
+        G[n][3] = wg_sub(u1_[0], u2_[0]); G[n][4] = wg_sub(d1_, d2_); G[n][5] = wg_sub(u1_[3], u2_[3]);   \
+    }
+#define WG_RELOAD(SLOT, OFS)                                                                              \
+    _Pragma("unroll") for (int n = 0; n < NN; n++)                                                        \
+        _Pragma("unroll") for (int blk = 0; blk < 3; blk++) Wr[blk][n][SLOT] = wg_ldw(rs, (OFS) + blk * pstride + n * 256, lofs);
+    WG_TAPS(0)
+    WG_RELOAD(0, wp + 2 * wstride)
+#pragma unroll 1
+    for (int it = 0; it < niter; it++) {
+        const bool more = it + 1 < niter;
+        const unsigned wcur = wp + 4 * it * wstride;
+        const unsigned wn = more ? wcur + 4 * wstride : wp;      // past the end: the round's own first k-steps again (unused, in bounds)
+        const unsigned adv = more ? 4u * WG_KSTEP : 0u;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+#pragma unroll
+            for (int b = 0; b < 3; b++)
+#pragma unroll
+                for (int a = 0; a < 2; a++)
+#pragma unroll
+                    for (int n = 0; n < NN; n++)
+                        acc[n][a] = __builtin_amdgcn_mfma_f32_16x16x4f32(G[n][a * 3 + b], X[s & 1][a * 3 + b], acc[n][a], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (s < 2) WG_LOADD(X[s & 1], pa, (s + 2) * WG_KSTEP)
+            else {
+                if (s == 2) pa += adv;                           // the next iteration's base from here on
+                WG_LOADD(X[s & 1], pa, (s - 2) * WG_KSTEP)
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            WG_TAPS((s + 1) & 1)                                 // k-step s + 1's taps; its registers take the k-step two further on
+            if (s == 0) WG_RELOAD(1, wcur + 3 * wstride)
+            else WG_RELOAD((s + 1) & 1, wn + (s - 1) * wstride)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#undef WG_TAPS
+#undef WG_RELOAD
+#pragma unroll
+    for (int n = 0; n < NN; n++) Y[n] = acc[n][0] + acc[n][1];
 }
 
 // ReLU + store of one N-tile's outputs: into the activation buffer (with the circular halo copies) or to y[32][140].
 // The weights are the MFMA's first operand, so the C/D layout has lane column li = the tile and rows lk * 4 + r = the
 // output channel: a store instruction writes 16 different positions of a channel (distinct banks), not 16 channels at one
 // position (one bank: the channel stride is a multiple of 32 words).
-template <bool GLB, int NU = 2>
+template <bool GLB>
 __device__ __forceinline__ void wg_store_tile(const wgf4 (&Yt)[2][2], int t, int nt, int relu, float* __restrict__ act, float* __restrict__ out_glb,
                                               int li, int lk)
 {
@@ -390,7 +413,7 @@ __device__ __forceinline__ void wg_store_tile(const wgf4 (&Yt)[2][2], int t, int
         int ty, tx;
         const bool valid = wg_tile(t, li, ty, tx);
 #pragma unroll
-        for (int u = 0; u < NU; u++) {                            // (M-tile 2 is tile row 3: NU = 1, its second output row is row 7)
+        for (int u = 0; u < 2; u++) {                             // (the tiles of tile row 3 in M-tile 1: their second output row is row 7)
             const int row = 2 * ty + u;
             const bool ok = valid && row < 7;
             if constexpr (GLB) {
@@ -421,28 +444,51 @@ __device__ __forceinline__ void wg_store_tile(const wgf4 (&Yt)[2][2], int t, int
     }
 }
 
+// The same for M-tile 2 (wg_round_direct): the C/D layout there has lane column li = output column li of row 6, one value per
+// register.  Column 0 goes behind column 19 as well; column 19 and its copy in front of column 0 belong to M-tile 1.
+template <bool GLB>
+__device__ __forceinline__ void wg_store_row6(const wgf4& Yr, int nt, int relu, float* __restrict__ act, float* __restrict__ out_glb, int li, int lk)
+{
+    const int n0 = nt * 16 + lk * 4;
+    const float lo = relu ? 0.f : -__builtin_inff();
+    if constexpr (GLB) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) out_glb[(size_t)(n0 + r) * 140 + 6 * 20 + li] = fmaxf(Yr[r], lo);
+    } else {
+        const int pos = 6 * WG_ROW + li + 1;
+        const int h0 = li == 0 ? 6 * WG_ROW + 21 : WG_ZERO + 4;   // (lanes with no halo copy to make: the dump word)
+        float* p = act + n0 * WG_CS;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const float v = fmaxf(Yr[r], lo);
+            p[r * WG_CS + pos] = v; p[r * WG_CS + h0] = v;
+        }
+    }
+}
+
 template <int T0, int T1, bool GLB>
 __device__ __forceinline__ void wg_store(const wgf4 (&Y)[3][2][2], int nt, int relu, float* __restrict__ act, float* __restrict__ out_glb,
                                          int li, int lk)
 {
 #pragma unroll
     for (int t = T0; t < T1; t++) {
-        if (t == 2) wg_store_tile<GLB, 1>(Y[t], t, nt, relu, act, out_glb, li, lk);
-        else wg_store_tile<GLB, 2>(Y[t], t, nt, relu, act, out_glb, li, lk);
+        if (t == 2) wg_store_row6<GLB>(Y[t][0][0], nt, relu, act, out_glb, li, lk);     // (the one quad of M-tile 2 rides in slot [0][0])
+        else wg_store_tile<GLB>(Y[t], t, nt, relu, act, out_glb, li, lk);
     }
 }
 
-// Window-row addresses of the lane: 3 M-tiles x 4 rows, channel lk of k-step k0
+// Window-row addresses of the lane: 2 Winograd M-tiles x 4 rows and row 5 of M-tile 2 (row 6 is an immediate offset behind it),
+// channel lk of k-step k0
 __device__ __forceinline__ void wg_addresses(const float* act, int k0, int li, int lk, unsigned (&RA)[3][4])
 {
     const unsigned act_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)act + (unsigned)k0 * WG_KSTEP;
 #pragma unroll
     for (int t = 0; t < 3; t++)
 #pragma unroll
-        for (int a = 0; a < 4; a++) RA[t][a] = wg_row_addr(act_addr, t, a, li, lk);
+        for (int a = 0; a < (t == 2 ? 1 : 4); a++) RA[t][a] = wg_row_addr(act_addr, t, a, li, lk);
 }
 
-// The 12 window-row addresses depend on the lane only (the map's geometry is the same in every layer): formed ONCE per kernel and parked in
+// The 9 window-row addresses depend on the lane only (the map's geometry is the same in every layer): formed ONCE per kernel and parked in
 // accumulation registers (round 6, WG_ADDR_PARK); a layer reads them back (one v_accvgpr_read each, plus one add where its K range does not
 // start at channel 0) instead of re-deriving tile coordinates and padding selects -- ~110 vector instructions per layer and wavefront.
 #ifndef WG_ADDR_PARK
@@ -455,7 +501,7 @@ __device__ __forceinline__ void wg_park_addresses(const float* act, int li, int 
 #pragma unroll
     for (int t = 0; t < 3; t++)
 #pragma unroll
-        for (int a = 0; a < 4; a++) {
+        for (int a = 0; a < (t == 2 ? 1 : 4); a++) {
             const unsigned v = wg_row_addr(act_addr, t, a, li, lk);
             asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(pk.a[t][a]) : "v"(v));
         }
@@ -477,8 +523,8 @@ __device__ __forceinline__ void wg_first_weights(__amdgpu_buffer_rsrc_t rs, unsi
 }
 
 // One layer with 32 output channels (two N-tiles, four wavefronts): wavefront w owns N-tile w & 1 over ALL three M-tiles and the
-// K half w >> 1; the upper half hands its partial sums (40 registers) to the lower one through the rows of the channels >= 64
-// (free: Cin <= 64), which adds them and stores.  Round 2 split the M-tiles {0} | {1, 2} over the wavefront pair instead: 16 against
+// K half w >> 1; the upper half hands its partial sums (36 registers) to the lower one through the rows of the channels >= 64
+// (free: Cin <= 64), which adds them and stores (9 quads: 4 + 4 of the Winograd M-tiles, one of row 6).  Round 2 split the M-tiles {0} | {1, 2} over the wavefront pair instead: 16 against
 // 28 tile-components, i.e. the layer took 28 / 22 of its balanced time -- these two layers are 6.5 % of the MFMAs and were 11 % of
 // the kernel.  The bias rides in the lower half's accumulators.
 #define WG_XCH_C 64
@@ -496,7 +542,7 @@ __device__ __forceinline__ void wg_layer_ksplit(float* __restrict__ act, float* 
 #pragma unroll
     for (int t = 0; t < 3; t++)
 #pragma unroll
-        for (int a = 0; a < 4; a++) RA[t][a] = wg_parked(pk, t, a) + (unsigned)k0 * WG_KSTEP;
+        for (int a = 0; a < (t == 2 ? 1 : 4); a++) RA[t][a] = wg_parked(pk, t, a) + (unsigned)k0 * WG_KSTEP;
 #else
     wg_addresses(act, k0, li, lk, RA);
 #endif
@@ -507,25 +553,27 @@ __device__ __forceinline__ void wg_layer_ksplit(float* __restrict__ act, float* 
     wg_first_weights<1, 0, 2>(rs, wp, lofs, wstride, W);
     wgf4 Y[1][3][2][2];
     wg_round<1, 0, 2>(RA, rs, wp, wp, lofs, kn >> 2, wstride, (unsigned)(k4 * wstride), half ? nullptr : bias + nt * 16 + lk * 4, W, Y);
-    wg_round_bottom<1>(RA, rs, wp, wp, lofs, kn >> 2, wstride, (unsigned)(k4 * wstride), half ? nullptr : bias + nt * 16 + lk * 4, W, Y);
-    wgf4* slot = reinterpret_cast<wgf4*>(act + WG_XCH_C * WG_CS) + nt * 640 + lane;                  // 10 x 64 float4 per N-tile
+    wgf4 Yb[1];
+    wg_round_direct<1>(RA[2][0], rs, wp, lofs, kn >> 2, wstride, (unsigned)(k4 * wstride), half ? nullptr : bias + nt * 16 + lk * 4, W, Yb);
+    Y[0][2][0][0] = Yb[0];
+    wgf4* slot = reinterpret_cast<wgf4*>(act + WG_XCH_C * WG_CS) + nt * 640 + lane;                  // 9 x 64 float4 per N-tile (in slots of 10)
     if (half) {
 #pragma unroll
-        for (int q = 0; q < 10; q++) slot[q * 64] = Y[0][q >> 2][(q >> 1) & 1][q & 1];              // t = q / 4, u, column; t = 2 has u = 0 only
+        for (int q = 0; q < 9; q++) slot[q * 64] = Y[0][q >> 2][(q >> 1) & 1][q & 1];               // t = q / 4, u, column; t = 2 is one quad
     }
     WG_STAMP_IN(18)
     WG_SYNC();                                       // partial sums are in place AND every wavefront has finished reading the input
     WG_STAMP_IN(19)
     if (!half) {
 #pragma unroll
-        for (int q = 0; q < 10; q++) Y[0][q >> 2][(q >> 1) & 1][q & 1] += slot[q * 64];
+        for (int q = 0; q < 9; q++) Y[0][q >> 2][(q >> 1) & 1][q & 1] += slot[q * 64];
         wg_store<0, 3, GLB>(Y[0], nt, relu, act, out_glb, li, lk);
     }
 }
 
 // The same 32-channel layer with the M-split pair form inside each K half (WG_KSPLIT_PAIRS): wavefront (h, half) owns BOTH N-tiles
 // for the Winograd M-tile h and the bottom row of N-tile h, over its half of K -- one transform per 8 MFMAs instead of 4, the same
-// ten quads of partial sums to hand over.
+// nine quads of partial sums to hand over.
 template <bool GLB>
 __device__ __forceinline__ void wg_layer_mksplit(float* __restrict__ act, float* __restrict__ out_glb, const float* __restrict__ wt,
                                                  const float* __restrict__ bias, int cin, int cout, int relu, int w, const WgAddrPark& pk)
@@ -540,13 +588,15 @@ __device__ __forceinline__ void wg_layer_mksplit(float* __restrict__ act, float*
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const unsigned r0 = wg_parked(pk, 0, a), r1 = wg_parked(pk, 1, a);
-        RA[0][a] = (h ? r1 : r0) + (unsigned)k0 * WG_KSTEP; RA[1][a] = RA[0][a]; RA[2][a] = wg_parked(pk, 2, a) + (unsigned)k0 * WG_KSTEP;
+        RA[0][a] = (h ? r1 : r0) + (unsigned)k0 * WG_KSTEP; RA[1][a] = RA[0][a];
     }
+    RA[2][0] = wg_parked(pk, 2, 0) + (unsigned)k0 * WG_KSTEP;
 #else
     {
         const unsigned act_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)act + (unsigned)k0 * WG_KSTEP;
 #pragma unroll
-        for (int a = 0; a < 4; a++) { RA[0][a] = wg_row_addr(act_addr, h, a, li, lk); RA[1][a] = RA[0][a]; RA[2][a] = wg_row_addr(act_addr, 2, a, li, lk); }
+        for (int a = 0; a < 4; a++) { RA[0][a] = wg_row_addr(act_addr, h, a, li, lk); RA[1][a] = RA[0][a]; }
+        RA[2][0] = wg_row_addr(act_addr, 2, 0, li, lk);
     }
 #endif
     const __amdgpu_buffer_rsrc_t rs = wg_weights(wt);
@@ -559,28 +609,28 @@ __device__ __forceinline__ void wg_layer_mksplit(float* __restrict__ act, float*
     wg_first_weights<2, 0, 2>(rs, wp, lofs, wstride, W2);
     wg_round<2, 0, 1>(RA, rs, wp, wpb, lofs, kn >> 2, wstride, pstride, half ? nullptr : bias + lk * 4, W2, Y);               // slot 0 = M-tile h
     wgf4 W1[1][2] = { { W2[0][0], W2[0][1] } };
-    wgf4 Yb[1][3][2][2];
-    wg_round_bottom<1>(RA, rs, wpb, wpb, lofs, kn >> 2, wstride, pstride, half ? nullptr : bias + h * 16 + lk * 4, W1, Yb);
-    wgf4* slot = reinterpret_cast<wgf4*>(act + WG_XCH_C * WG_CS) + h * 640 + lane;                   // 10 x 64 float4 per wavefront pair
+    wgf4 Yb[1];
+    wg_round_direct<1>(RA[2][0], rs, wpb, lofs, kn >> 2, wstride, pstride, half ? nullptr : bias + h * 16 + lk * 4, W1, Yb);
+    wgf4* slot = reinterpret_cast<wgf4*>(act + WG_XCH_C * WG_CS) + h * 640 + lane;                   // 9 x 64 float4 per wavefront pair (in slots of 10)
     if (half) {
 #pragma unroll
         for (int q = 0; q < 8; q++) slot[q * 64] = Y[q >> 2][0][(q >> 1) & 1][q & 1];
-        slot[8 * 64] = Yb[0][2][0][0]; slot[9 * 64] = Yb[0][2][0][1];
+        slot[8 * 64] = Yb[0];
     }
     WG_SYNC();                                       // partial sums are in place AND every wavefront has finished reading the input
     if (!half) {
 #pragma unroll
         for (int q = 0; q < 8; q++) Y[q >> 2][0][(q >> 1) & 1][q & 1] += slot[q * 64];
-        Yb[0][2][0][0] += slot[8 * 64]; Yb[0][2][0][1] += slot[9 * 64];
-        wg_store_tile<GLB, 2>(Y[0][0], h, 0, relu, act, out_glb, li, lk);
-        wg_store_tile<GLB, 2>(Y[1][0], h, 1, relu, act, out_glb, li, lk);
-        wg_store_tile<GLB, 1>(Yb[0][2], 2, h, relu, act, out_glb, li, lk);
+        Yb[0] += slot[8 * 64];
+        wg_store_tile<GLB>(Y[0][0], h, 0, relu, act, out_glb, li, lk);
+        wg_store_tile<GLB>(Y[1][0], h, 1, relu, act, out_glb, li, lk);
+        wg_store_row6<GLB>(Yb[0], h, relu, act, out_glb, li, lk);
     }
 }
 
 // One layer with 64 output channels (four N-tiles, four wavefronts): wavefront w owns the N-tile pair w & 1 for ONE of the
-// M-tiles 0, 1 (w >> 1) -- the transform of a step feeds 8 MFMAs, as in the 128-channel layers -- and the bottom-row form of
-// ONE N-tile of its pair: 32 + 8 = 40 matrix instructions per k-step for every wavefront, no partial sums to exchange.
+// M-tiles 0, 1 (w >> 1) -- the transform of a step feeds 8 MFMAs, as in the 128-channel layers -- and row 6 (M-tile 2, the direct form) of
+// ONE N-tile of its pair: 32 + 6 = 38 matrix instructions per k-step for every wavefront, no partial sums to exchange.
 // (One N-tile per wavefront over all M-tiles, the round-2 form, pays 1.8 transform instructions per MFMA instead of 1.0.)
 __device__ __forceinline__ void wg_layer_msplit(float* __restrict__ act, const float* __restrict__ wt, const float* __restrict__ bias,
                                                 int cin, int cout, int relu, int w, const WgAddrPark& pk)
@@ -595,13 +645,15 @@ __device__ __forceinline__ void wg_layer_msplit(float* __restrict__ act, const f
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const unsigned r0 = wg_parked(pk, 0, a), r1 = wg_parked(pk, 1, a);
-        RA[0][a] = h ? r1 : r0; RA[1][a] = RA[0][a]; RA[2][a] = wg_parked(pk, 2, a);
+        RA[0][a] = h ? r1 : r0; RA[1][a] = RA[0][a];
     }
+    RA[2][0] = wg_parked(pk, 2, 0);
 #else
     {
         const unsigned act_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)act;
 #pragma unroll
-        for (int a = 0; a < 4; a++) { RA[0][a] = wg_row_addr(act_addr, h, a, li, lk); RA[1][a] = RA[0][a]; RA[2][a] = wg_row_addr(act_addr, 2, a, li, lk); }
+        for (int a = 0; a < 4; a++) { RA[0][a] = wg_row_addr(act_addr, h, a, li, lk); RA[1][a] = RA[0][a]; }
+        RA[2][0] = wg_row_addr(act_addr, 2, 0, li, lk);
     }
 #endif
     const __amdgpu_buffer_rsrc_t rs = wg_weights(wt);
@@ -614,12 +666,12 @@ __device__ __forceinline__ void wg_layer_msplit(float* __restrict__ act, const f
     wg_first_weights<2, 0, 2>(rs, wp, lofs, wstride, W2);
     wg_round<2, 0, 1>(RA, rs, wp, wpb, lofs, k4 >> 2, wstride, pstride, bias + (2 * pair) * 16 + lk * 4, W2, Y);     // slot 0 = M-tile h
     wgf4 W1[1][2] = { { W2[0][0], W2[0][1] } };
-    wgf4 Yb[1][3][2][2];
-    wg_round_bottom<1>(RA, rs, wpb, wpb, lofs, k4 >> 2, wstride, pstride, bias + (2 * pair + h) * 16 + lk * 4, W1, Yb);
+    wgf4 Yb[1];
+    wg_round_direct<1>(RA[2][0], rs, wpb, lofs, k4 >> 2, wstride, pstride, bias + (2 * pair + h) * 16 + lk * 4, W1, Yb);
     WG_SYNC();                                       // every wavefront has finished reading the layer's input
-    wg_store_tile<false, 2>(Y[0][0], h, 2 * pair, relu, act, nullptr, li, lk);
-    wg_store_tile<false, 2>(Y[1][0], h, 2 * pair + 1, relu, act, nullptr, li, lk);
-    wg_store_tile<false, 1>(Yb[0][2], 2, 2 * pair + h, relu, act, nullptr, li, lk);
+    wg_store_tile<false>(Y[0][0], h, 2 * pair, relu, act, nullptr, li, lk);
+    wg_store_tile<false>(Y[1][0], h, 2 * pair + 1, relu, act, nullptr, li, lk);
+    wg_store_row6<false>(Yb[0], 2 * pair + h, relu, act, nullptr, li, lk);
 }
 
 // N-tiles per wavefront of a layer: 2 (the paired form below) or 1.  The filter tiling follows it (buf_winograd_tile_weights).
@@ -640,14 +692,14 @@ __device__ __forceinline__ void wg_park(const wgf4 (&Y)[2][3][2][2], float (&par
 #pragma unroll
     for (int n = 0; n < 2; n++)
 #pragma unroll
-        for (int q = 0; q < (T == 2 ? 8 : 16); q++)
+        for (int q = 0; q < (T == 2 ? 4 : 16); q++)             // (M-tile 2: the one quad of row 6)
             asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(park[n][T][q]) : "v"(Y[n][T][q >> 3][(q >> 2) & 1][q & 3]));
 }
 
 // One layer with 128 output channels: wavefront w owns the N-tile pair 2w, 2w+1 over the whole K, and the transform of a step
-// feeds 8 MFMAs.  The held outputs (80 registers) wait in accumulation registers; the two Winograd M-tiles share one round
-// (64 accumulators; a round per M-tile -- more passes, the pair's filters streamed a third time -- measured 0.9 % slower), the
-// bottom row is the second.
+// feeds 8 MFMAs.  The held outputs (72 registers) wait in accumulation registers; the two Winograd M-tiles share one round
+// (64 accumulators; a round per M-tile -- more passes, the pair's filters streamed a third time -- measured 0.9 % slower), row 6
+// (M-tile 2, the direct form) is the second.
 __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const float* __restrict__ wt, const float* __restrict__ bias,
                                               int cin, int cout, int relu, int pair, const WgAddrPark& pk)
 {
@@ -665,7 +717,7 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
 #pragma unroll
     for (int t = 0; t < 3; t++)
 #pragma unroll
-        for (int a = 0; a < 4; a++) RA[t][a] = wg_parked(pk, t, a);
+        for (int a = 0; a < (t == 2 ? 1 : 4); a++) RA[t][a] = wg_parked(pk, t, a);
 #else
     wg_addresses(act, 0, li, lk, RA);
 #endif
@@ -678,7 +730,7 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
     wgf4 W1[2][2];
     wg_first_weights<2, 0, 2>(rs, wp, lofs, wstride, W1);
     // The outputs of a finished round wait for the in-place barrier in ACCUMULATION registers (v_accvgpr_write / _read: the unified
-    // file gives a wavefront 256 registers of either kind): left in VGPRs the compiler parked 19 of the 20 quads in scratch memory
+    // file gives a wavefront 256 registers of either kind): left in VGPRs the compiler parked 19 of the then 20 quads in scratch memory
     // (264 KB of HBM traffic per patch); the rounds then run in ~130 VGPRs with no scratch at all.
     float park[2][3][16];
 #if WG_PAIR_NT2
@@ -691,7 +743,9 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
     wg_round<2, 1, 2>(RA, rs, wp, wp, lofs, k4 >> 2, wstride, pstride, bv, W1, Y);
     wg_park<1>(Y, park);
 #endif
-    wg_round_bottom<2>(RA, rs, wp, wp, lofs, k4 >> 2, wstride, pstride, bv, W1, Y);
+    wgf4 Yb[2];
+    wg_round_direct<2>(RA[2][0], rs, wp, lofs, k4 >> 2, wstride, pstride, bv, W1, Yb);
+    Y[0][2][0][0] = Yb[0]; Y[1][2][0][0] = Yb[1];
     wg_park<2>(Y, park);
     WG_SYNC();                                       // every wavefront has finished reading the layer's input
     int lane_s = threadIdx.x & (WAVE - 1);
@@ -701,7 +755,7 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
 #pragma unroll
         for (int t = 0; t < 3; t++)
 #pragma unroll
-            for (int q = 0; q < (t == 2 ? 8 : 16); q++)
+            for (int q = 0; q < (t == 2 ? 4 : 16); q++)
                 asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(Y[n][t][q >> 3][(q >> 2) & 1][q & 3]) : "a"(park[n][t][q]));
         wg_store<0, 3, false>(Y[n], 2 * pair + n, relu, act, nullptr, lane_s & 15, lane_s >> 4);
     }
@@ -922,7 +976,7 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
                     c7[0] / n, c7[1] / n, c7[2] / n, c7[3] / n, b7[0] / n, b7[1] / n, b7[2] / n, b7[3] / n, s7[0] / n, s7[1] / n, s7[2] / n, s7[3] / n);
             fprintf(stderr, "WG_STAMP: %ld workgroups, layers total %.0f cycles per patch, input phase %.0f\n", n, tot / n, pre / n);
             for (int l = 0; l < WG_LAYERS; l++) {
-                const double mf = 40.0 * (P.cin[l] / 4) * (P.cout[l] / 16) / 4;     // MFMAs per wave
+                const double mf = 38.0 * (P.cin[l] / 4) * (P.cout[l] / 16) / 4;     // MFMAs per wave
                 fprintf(stderr, "  layer %d %3d->%3d: MFMAs/wave %5.0f | to barrier %7.0f %7.0f %7.0f %7.0f | wait %6.0f %6.0f %6.0f %6.0f | cycles per MFMA slot %.1f\n",
                         l, P.cin[l], P.cout[l], mf, comp[l][0] / n, comp[l][1] / n, comp[l][2] / n, comp[l][3] / n, wait[l][0] / n, wait[l][1] / n,
                         wait[l][2] / n, wait[l][3] / n, (comp[l][0] + wait[l][0]) / n / (2 * mf));
