@@ -4,6 +4,7 @@
 #include "core.hip"
 #include "radius.hip"
 #include "icp.hip"
+#include "pairstats.hip"
 #include "metrics.hip"
 #include "subsample.hip"
 #include "pointops.hip"

@@ -37,6 +37,7 @@ __global__ void __launch_bounds__(BBOX_THREADS) k_grid_bbox(const float* __restr
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             float v = pts[3 * (size_t)i + c];
+            if (!isfinite(v)) continue;                // (a non-finite coordinate takes no part in the box: its row is binned into a border cell and matches nothing)
             mn[c] = fminf(mn[c], v);
             mx[c] = fmaxf(mx[c], v);
         }
@@ -59,7 +60,7 @@ __global__ void __launch_bounds__(BBOX_THREADS) k_grid_bbox(const float* __restr
         for (int c = 0; c < 3; c++) {
             float a = smn[c][0], z = smx[c][0];
             for (int i = 1; i < BBOX_THREADS / WAVE; i++) { a = fminf(a, smn[c][i]); z = fmaxf(z, smx[c][i]); }
-            if (hi <= lo) { a = 0.f; z = 0.f; }
+            if (hi <= lo || !(a <= z)) { a = 0.f; z = 0.f; }      // (no rows, or no finite coordinate on this axis)
             g.mn[c] = a;
             ext[c] = (double)z - (double)a;
         }

@@ -142,11 +142,13 @@ def stage_summary(counts, P, fmr_ratio=0.05):
                 consensus_precision=mean(ratio(col['cons_true'], col['cons'])))
 
 
-def write_stage_metrics(path, ids, counts, P, summary):
-    """<log root>/stage_metrics.json: the per-pair count rows in data-set order (ids: one label per pair) and the summary dict."""
+def write_stage_metrics(path, ids, counts, P, summary, overlaps=None):
+    """<log root>/stage_metrics.json: the per-pair count rows in data-set order (ids: one label per pair) and the summary dict;
+    with overlaps (the drivers' --by-overlap: one ratio per pair) every pair also carries its `overlap`."""
     import json
     c = np.asarray(counts, np.int64).reshape(-1, len(STAGE_COLUMNS))
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     with open(path, 'w') as f:
         json.dump(dict(columns=list(STAGE_COLUMNS), num_keypts=int(P), summary=summary,
-                       pairs=[dict(id=str(ids[i]), counts=[int(v) for v in c[i]]) for i in range(c.shape[0])]), f, indent=1)
+                       pairs=[dict(id=str(ids[i]), counts=[int(v) for v in c[i]], **({} if overlaps is None else {'overlap': float(overlaps[i])}))
+                              for i in range(c.shape[0])]), f, indent=1)

@@ -218,6 +218,9 @@ def parse_args(argv=None):
                     help='also compute the per-stage ground-truth metrics (repeatability, inlier ratio, FMR, consensus precision): '
                          'summary key "stage", per-pair rows in <log-root>/stage_metrics.json')
     ap.add_argument('--log-root', default=None, help='where --stage-metrics writes stage_metrics.json (default: log_KITTI)')
+    ap.add_argument('--by-overlap', action='store_true',
+                    help='also compute every pair\'s overlap under the ground truth (buffer_amd/pairs.py) and report pair count, DGR recall '
+                         'and, with --stage-metrics, the stage figures per overlap band: summary key "by_overlap"')
     a = ap.parse_args(argv)
     try:
         cfg = preset(a.preset, 'kitti')
@@ -270,11 +273,15 @@ def main(argv=None):
     if rank == 0:
         out = summarize(ds, poses)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
+        overlaps = None
+        if a.by_overlap:
+            from . import pairs
+            out['by_overlap'], overlaps = pairs.overlap_report(ds, poses, dev, 0.3, 1.0, counts, cfg.num_keypts)       # (summarize's thresholds)
         if a.stage_metrics:
             from . import evaluate
             out['stage'] = evaluate.stage_summary(counts, cfg.num_keypts)
             evaluate.write_stage_metrics(os.path.join(a.log_root or 'log_KITTI', 'stage_metrics.json'),
-                                         ['%d %d %d' % f for f in ds.files], counts, cfg.num_keypts, out['stage'])
+                                         ['%d %d %d' % f for f in ds.files], counts, cfg.num_keypts, out['stage'], overlaps)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

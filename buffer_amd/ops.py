@@ -553,6 +553,34 @@ def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='po
     return T, fit, rmse, iters, (nn[:int(src.shape[0])] if nn is not None else None)
 
 
+def pair_stats(points, lengths, pair_src, pair_tgt, T, radius, correspondences=False, cells_per_elem=0):
+    """buf_pair_stats: statistics of P pairs over the C clouds stacked in points f32[sum lengths,3] under given transforms, one cell
+    grid per call, nothing read back.  pair_src / pair_tgt host int[P] (cloud indices), T f64[P,4,4] (device) mapping the source
+    cloud into the target cloud's frame -> (matched int32[P], moments f64[P,10] = sum d2, sum u (3), upper triangle of sum u u^T
+    (6) over the matched target points u, nn int32[sum of the pairs' source rows] or None: row inside the target cloud, -1 = none)."""
+    L = _lib.lib()
+    points = _dev(points, torch.float32, "pair_stats.points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"pair_stats: points {tuple(points.shape)} is not [N,3]")
+    ln, pa, pb = _host_i32(lengths), _host_i32(pair_src), _host_i32(pair_tgt)
+    if pa.shape != pb.shape:
+        raise ValueError(f"pair_stats: {pa.shape[0]} sources but {pb.shape[0]} targets")
+    if int(ln.sum()) != int(points.shape[0]):
+        raise ValueError(f"pair_stats: lengths sum to {int(ln.sum())}, points holds {int(points.shape[0])} rows")
+    Cn, P, dev = int(ln.shape[0]), int(pa.shape[0]), points.device
+    T = _dev(T, torch.float64, "pair_stats.T").reshape(P, 4, 4)
+    ok = (pa >= 0) & (pa < Cn)
+    rows = int(ln[pa[ok]].astype(np.int64).sum())
+    matched = torch.zeros((P,), dtype=torch.int32, device=dev)
+    moments = torch.zeros((P, 10), dtype=torch.float64, device=dev)
+    nn = torch.empty((max(rows, 1),), dtype=torch.int32, device=dev) if correspondences else None
+    nbytes = max(L.buf_pair_stats_ws_bytes(int(points.shape[0]), max(Cn, 1), max(P, 1), rows, int(cells_per_elem)), 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_pair_stats(_ptr(points), _hptr(ln), Cn, _hptr(pa), _hptr(pb), P, _ptr(T), float(radius), int(cells_per_elem),
+                           _ptr(matched), _ptr(moments), _ptr(nn), _ptr(ws), nbytes, _stream()), "buf_pair_stats")
+    return matched, moments, (nn[:rows] if nn is not None else None)
+
+
 METRIC_COLUMNS = ('rep_src', 'rep_tgt', 'nn_inl', 'mutual', 'mutual_inl', 'cons', 'cons_true')      # BUF_METRICS_* of buffer_hip.h
 
 

@@ -113,3 +113,30 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
                              np.eye(4) if init is None else np.asarray(init, np.float64),
                              cr.max_iteration, cr.relative_fitness, cr.relative_rmse)
     return RegistrationResult(T, fit, rmse, corr)
+
+
+def _one_pair_statistics(source, target, max_correspondence_distance, transformation, correspondences):
+    """source / target PointClouds -> pairs.pair_statistics of the one pair (source -> target under `transformation`)"""
+    import torch
+    from buffer_amd import pairs
+    dev = _device()
+    T = np.eye(4) if transformation is None else np.asarray(transformation, np.float64).reshape(4, 4)
+    clouds = [torch.from_numpy(np.asarray(c.points, np.float32).reshape(-1, 3)).to(dev) for c in (source, target)]
+    return T, pairs.pair_statistics(clouds, [(0, 1)], T[None], float(max_correspondence_distance), correspondences=correspondences)
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=None):
+    """open3d evaluate_registration: fitness (matched source points / source points), inlier RMSE and the correspondence set of
+    `transformation` itself, nothing refined (buffer_amd/pairs.py, csrc/pairstats.hip)."""
+    T, st = _one_pair_statistics(source, target, max_correspondence_distance, transformation, True)
+    nn = st['nn'][0]
+    hit = np.flatnonzero(nn >= 0)
+    return RegistrationResult(T, st['overlap'][0], st['inlier_rmse'][0], np.stack([hit, nn[hit]], 1).astype(np.int32))
+
+
+def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation):
+    """open3d get_information_matrix_from_point_clouds -> f64[6,6], order [rotation, translation], over the matched target points
+    (restated from the upstream source as recalled, unpinned)."""
+    from buffer_amd import pairs
+    _, st = _one_pair_statistics(source, target, max_correspondence_distance, transformation, False)
+    return pairs.information_matrix(st['matched'][0], st['sum_u'][0], st['sum_uu'][0], 'open3d')

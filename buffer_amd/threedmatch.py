@@ -242,6 +242,9 @@ def parse_args(argv=None):
     ap.add_argument('--stage-metrics', action='store_true',
                     help='also compute the per-stage ground-truth metrics (repeatability, inlier ratio, FMR, consensus precision): '
                          'summary key "stage", per-pair rows in <log-root>/stage_metrics.json')
+    ap.add_argument('--by-overlap', action='store_true',
+                    help='also compute every pair\'s overlap under the ground truth (buffer_amd/pairs.py) and report pair count, DGR recall '
+                         'and, with --stage-metrics, the stage figures per overlap band: summary key "by_overlap"')
     a = ap.parse_args(argv)
     try:
         cfg = preset(a.preset, 'threedmatch')
@@ -289,10 +292,14 @@ def main(argv=None):
         stats = write_logs(ds, poses, log_root, a.log_name)
         out = summarize(ds, stats, log_root, a.log_name)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
+        overlaps = None
+        if a.by_overlap:
+            from . import pairs
+            out['by_overlap'], overlaps = pairs.overlap_report(ds, poses, dev, 0.3, 15.0, counts, cfg.num_keypts)      # (dgr_success defaults)
         if a.stage_metrics:
             out['stage'] = stage_report([f[0].split(os.sep)[-2] for f in ds.files], counts, cfg.num_keypts)
             evaluate.write_stage_metrics(os.path.join(log_root, 'stage_metrics.json'), [f'{s} {t}' for s, t in ds.files], counts,
-                                         cfg.num_keypts, out['stage'])
+                                         cfg.num_keypts, out['stage'], overlaps)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

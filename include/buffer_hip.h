@@ -464,6 +464,28 @@ int     buf_icp_batched(const float* src, const int* src_lengths_host, const flo
                         int max_iteration, double rel_fitness, double rel_rmse, double* T_out_f64, double* fitness_out,
                         double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream);
 
+/* N4  Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
+ * information matrix of a pair are made of; the evaluation half of an ICP round without the loop).
+ * pts f32[sum lengths_host,3] stacks the C clouds; pair k = (pair_src_host[k], pair_tgt_host[k], T_f64[k]) with T_f64 f64[P,4,4]
+ * (device) mapping the source cloud into the frame of the target cloud.  A cloud may appear in any number of pairs, on either side,
+ * and a pair may name one cloud twice.  ONE cell grid over all C clouds is built per call (radius = the correspondence distance,
+ * cells_per_elem as in buf_grid_build, <= 0 = its default; a share smaller than a cloud's box coarsens the cell edge by 1.25 until it
+ * fits: same results, more candidates per row).
+ * Per source row the arithmetic of buf_icp_batched's correspondence: p = T s in fp64, ((T0*sx + T1*sy) + T2*sz) + T3 per row of T,
+ * rounded to fp32 for the search; nearest row of the target cloud with fp32 d2 = (dx*dx + dy*dy) + dz*dz < radius^2 (strict, radius^2
+ * in fp32), ties to the smaller row; a row whose search point is not finite matches nothing.  A match adds in fp64: 1, |p - u|^2
+ * with the unrounded p and the target point u, u, and the upper triangle of u u^T; u is in the target cloud's own frame.
+ * matched_out int32[P]; moments_out f64[P,10] = sum d2, sum u (x, y, z), sum u u^T (xx, xy, xz, yy, yz, zz); nn_out (nullable)
+ * int32[n_src_rows], pair k owning the next lengths_host[pair_src_host[k]] entries: row inside the target cloud, -1 = no match.
+ * n_src_rows = the sum of the pairs' source lengths.  Sums have a fixed order and there are no float atomics: a pair's results are
+ * the same bits alone, in any batch, in any pair order and across runs.  Nothing is read back.
+ * BUF_EINVAL before any device work for a pair index outside [0, C), radius <= 0 or not finite, negative lengths, null outputs
+ * with P > 0.  P == 0 succeeds and touches nothing; empty clouds and pairs with an empty source give zeros. */
+size_t  buf_pair_stats_ws_bytes(int n_total, int nclouds, int npairs, int n_src_rows, int64_t cells_per_elem);
+int     buf_pair_stats(const float* pts, const int* lengths_host, int nclouds, const int* pair_src_host, const int* pair_tgt_host,
+                       int npairs, const double* T_f64, float radius, int64_t cells_per_elem, int* matched_out,
+                       double* moments_out, int* nn_out /* nullable */, void* ws, size_t ws_bytes, void* stream);
+
 /* N3  Per-stage ground-truth metrics of B registered pairs (a diagnostic beside the registration path: keypoint repeatability,
  * inlier counts of the putative and the mutual matches, the consensus set of the returned pose).  One launch, nothing read back.
  * kp f32[2*B*P,3]: the keypoints in the batched pipeline's layout, pair b owns rows [2bP, 2bP+P) (source) and [(2b+1)P, (2b+2)P)
