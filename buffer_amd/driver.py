@@ -1,0 +1,200 @@
+"""What the three test-set drivers (threedmatch.py, kitti.py, eth.py) and the synthetic stream (stream.py) share: raw clouds -> sample
+dicts -> pipeline inputs, the chunked registration loop, the DGR summary, the common command line and the body of main().
+Host code only; a data-set module keeps its file layout, its ground truth and its own scoring."""
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import evaluate, preprocess
+
+
+# ---------------------------------------------------------------------------------------------------- raw clouds -> samples
+# `consts` below: any object with downsample, voxel_size_0 and max_num_pts (a test set or a Config)
+def pack_pair(raws, seeds, meta, consts):
+    """One pair: the two raw clouds (f32[n,3] device tensors, src then tgt), each through one preprocess.prepare_fragment call
+    (two voxel levels, shuffle keyed by its seed, normals) -> the reference's sample dict of DEVICE tensors: meta +
+    {src,tgt}_fds_pts, {src,tgt}_sds_pts.  `raws` may be lazy: a cloud is taken when its turn comes."""
+    out = dict(meta)
+    for side, raw, seed in zip(('src', 'tgt'), raws, seeds):
+        it = preprocess.prepare_fragment(raw, consts.downsample, consts.voxel_size_0, consts.max_num_pts, seed=seed)
+        out[f'{side}_fds_pts'], out[f'{side}_sds_pts'] = it['fds_pts'], it['sds_pts']
+    return out
+
+
+def pack_pairs(raws, seeds, metas, consts):
+    """pack_pair for B pairs with the normals of all 2B clouds estimated in ONE stacked pass (preprocess.prepare_fragments); pair by
+    pair the result is that of pack_pair.  raws, seeds: 2B entries (src, tgt of pair 0, src, tgt of pair 1, ...); metas: B dicts,
+    read AFTER the stacked pass is queued (a generator keeps the work of making them behind it)."""
+    frs = preprocess.prepare_fragments(raws, consts.downsample, consts.voxel_size_0, consts.max_num_pts, seeds)
+    out = []
+    for k, meta in enumerate(metas):
+        s = dict(meta)
+        s.update(src_fds_pts=frs[2 * k]['fds_pts'], src_sds_pts=frs[2 * k]['sds_pts'],
+                 tgt_fds_pts=frs[2 * k + 1]['fds_pts'], tgt_sds_pts=frs[2 * k + 1]['sds_pts'])
+        out.append(s)
+    return out
+
+
+class PairTestSet:
+    """Base of the test sets.  A subclass supplies `files` (one entry per pair), raw_pair(index) -> the two clouds as read from disk
+    (f32[n,3] numpy), meta(index, device) -> dict(src_id, tgt_id, relt_pose f64[4,4] source -> target) and the voxel constants
+    downsample, voxel_size_0, max_num_pts."""
+
+    def __len__(self):
+        return len(self.files)
+
+    def item(self, index, device, seed=None):
+        """The test branch of the reference's Dataset.__getitem__ on the device -> pack_pair's sample dict.  The two clouds shuffle
+        with seeds 2 * index and 2 * index + 1, or both with `seed`."""
+        meta = self.meta(index, device)               # before any pre-processing launch (KITTI may refine its ground truth here)
+        raws = (torch.from_numpy(raw).to(device) for raw in self.raw_pair(index))
+        return pack_pair(raws, (2 * index, 2 * index + 1) if seed is None else (seed, seed), meta, self)
+
+
+def items_batched(dataset, indices, device):
+    """dataset.item(i, device) for several pairs through pack_pairs; pair by pair the result is that of item()."""
+    idx = list(indices)
+    raws = [torch.from_numpy(raw).to(device) for i in idx for raw in dataset.raw_pair(i)]
+    return pack_pairs(raws, [2 * i + j for i in idx for j in range(2)], (dataset.meta(i, device) for i in idx), dataset)
+
+
+def upload(sample):
+    """sample dict of device tensors (pack_pair) -> the inputs BufferPipeline.register takes
+    (the device-side twin of pyramid.stack_sample)."""
+    src, tgt = sample['src_sds_pts'], sample['tgt_sds_pts']
+    return dict(points=torch.cat([src[:, :3], tgt[:, :3]]).contiguous(), features=torch.cat([src[:, 3:], tgt[:, 3:]]).contiguous(),
+                lengths=np.array([src.shape[0], tgt.shape[0]], np.int32), src_raw=sample['src_fds_pts'], tgt_raw=sample['tgt_fds_pts'])
+
+
+# ---------------------------------------------------------------------------------------------------- registration
+def register_chunks(pipe, chunks, make, gt_of=None):
+    """Chunks of pairs through the device pipeline -> f32[k,4,4] (device) in chunk order.  chunks: lists of pair ids, which also seed
+    the pipeline; make(chunk) -> the chunk's sample dicts.  The chunks are software-pipelined over two HIP streams: making chunk
+    i+1 (reading, pre-processing) and its keypoint stage run beside the CNN kernels of chunk i (BufferPipeline.register_batches;
+    results equal batch-by-batch calls).
+    gt_of(chunk) -> the chunk's ground-truth poses: also the per-stage metric rows (register_batches, metrics_gt=: the ground truth
+    is read when the chunk's clouds are, one metric launch per chunk after its pose recovery) -> (poses, counts int32[k,7])."""
+    dev = pipe.device
+    makers = [(lambda ch=ch: [upload(s) for s in make(ch)]) for ch in chunks]
+    gts = None if gt_of is None else [(lambda ch=ch: gt_of(ch)) for ch in chunks]
+    out = pipe.register_batches(makers, seeds=chunks, metrics_gt=gts)
+    poses = [p for o in out for p in (o if gt_of is None else o[0])]
+    poses = torch.stack(poses) if poses else torch.zeros((0, 4, 4), dtype=torch.float32, device=dev)
+    if gt_of is None:
+        return poses
+    counts = torch.cat([o[1] for o in out]) if out else torch.zeros((0, 7), dtype=torch.int32, device=dev)
+    return poses, counts
+
+
+def register_pairs(pipe, dataset, indices, batch, stage_metrics=False):
+    """This rank's share of the pairs through the device pipeline, `batch` pairs per chunk -> f32[k,4,4] (device), in the order of
+    `indices`.  stage_metrics: also the per-stage metric rows against the data set's ground truth -> (poses, counts int32[k,7] on
+    the device); the poses are the same."""
+    idx = list(indices)
+    return register_chunks(pipe, [idx[lo:lo + batch] for lo in range(0, len(idx), batch)],
+                           lambda ch: items_batched(dataset, ch, pipe.device),
+                           (lambda ch: [dataset.meta(i, pipe.device)['relt_pose'] for i in ch]) if stage_metrics else None)
+
+
+# ---------------------------------------------------------------------------------------------------- scoring
+def dgr_summary(stats, recall_key='recall'):
+    """stats [n,3]: evaluate.dgr_success rows (success, rte, rre) -> dict(pairs, <recall_key>, te, re); te / re are means over the
+    successful pairs, NaN when there is none (test.py:278-284)."""
+    st = np.array(stats, np.float64).reshape(-1, 3)
+    good = st[:, 0] == 1
+    return {'pairs': int(st.shape[0]), recall_key: float(good.mean()) if st.size else 0.0,
+            'te': float(st[good, 1].mean()) if good.any() else float('nan'),
+            're': float(st[good, 2].mean()) if good.any() else float('nan')}
+
+
+def stage_report(scene_of, counts, P, fmr_ratio=0.05):
+    """evaluate.stage_summary of all pairs and per scene (scene_of: one scene name per row of counts, data-set order)
+    -> dict(overall figures..., per_scene={scene: figures})"""
+    counts = np.asarray(counts).reshape(-1, 7)
+    scene_of = np.asarray(list(scene_of), dtype=object)
+    out = evaluate.stage_summary(counts, P, fmr_ratio)
+    out['per_scene'] = {s: evaluate.stage_summary(counts[scene_of == s], P, fmr_ratio) for s in dict.fromkeys(scene_of.tolist())}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- command line and main()
+def add_common_args(ap, driver_name, batch_default, log_root_default, preset_note=''):
+    """the options every driver takes; a driver adds its own and then calls parse_with_preset"""
+    from .config import DRIVER_PRESETS
+    ap.add_argument('--root', required=True)
+    ap.add_argument('--preset', default=DRIVER_PRESETS[driver_name][0],
+                    help='constants and weights (buffer_amd/config.py): ' + ', '.join(DRIVER_PRESETS[driver_name]) + preset_note)
+    ap.add_argument('--batch', type=int, default=batch_default)
+    ap.add_argument('--limits', default=None, help='frozen neighbourhood limits "a,b,c" (default: calibrate like dataloader.py:18-51)')
+    ap.add_argument('--stage-metrics', action='store_true',
+                    help='also compute the per-stage ground-truth metrics (repeatability, inlier ratio, FMR, consensus precision): '
+                         'summary key "stage", per-pair rows in <log-root>/stage_metrics.json')
+    ap.add_argument('--log-root', default=None, help=f'where the logs and stage_metrics.json go (default: {log_root_default})')
+    ap.add_argument('--by-overlap', action='store_true',
+                    help='also compute every pair\'s overlap under the ground truth (buffer_amd/pairs.py) and report pair count, DGR recall '
+                         'and, with --stage-metrics, the stage figures per overlap band: summary key "by_overlap"')
+
+
+def parse_with_preset(ap, argv, driver_name):
+    """-> (args, Config of --preset); a preset of another data set is an argument error"""
+    from .config import preset
+    a = ap.parse_args(argv)
+    try:
+        return a, preset(a.preset, driver_name)
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def init():
+    """a driver's first GPU-touching call, before its data set is built -> (rank, world, device, collective device)"""
+    from . import dist as bdist
+    return bdist.init(int(os.environ.get('LOCAL_RANK', 0)))
+
+
+def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calibrate_pairs, scene_of=None):
+    """The body of a driver's main() once its data set exists: neighbourhood limits (--limits, or calibrated on the first
+    `calibrate_pairs` pairs by rank 0 and broadcast), this rank's shard through register_pairs, gather, and on rank 0 the report:
+    summarize(poses) -> the driver's own figures, the common ones, --by-overlap under the driver's (rte, rre) thresholds and
+    --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
+    ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
+    from . import dist as bdist
+    from .pipeline import BufferPipeline
+    rank, world, dev, cdev = ranks
+    pipe = BufferPipeline(cfg, dev)
+    if a.limits:
+        pipe.limits = [int(x) for x in a.limits.split(',')]
+    else:
+        if rank == 0:                                        # dataloader.py:18-51 on the first pairs
+            host = []
+            for i in range(min(len(ds), calibrate_pairs)):
+                s = ds.item(i, dev)
+                host.append({k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in s.items()})
+            pipe.calibrate(host)
+        pipe.limits = bdist.broadcast_limits(pipe.limits if rank == 0 else [0, 0, 0], device=cdev)
+    ids = bdist.shard_indices(len(ds), rank, world)
+    t0 = time.perf_counter()
+    res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics)
+    poses = bdist.gather_poses(ids, res[0] if a.stage_metrics else res, len(ds), device=cdev)
+    counts = bdist.gather_counts(ids, res[1].to(cdev), len(ds), device=cdev).cpu().numpy() if a.stage_metrics else None
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    poses = poses.cpu().numpy()
+    if rank == 0:
+        out = summarize(poses)
+        out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
+        overlaps = None
+        if a.by_overlap:
+            from . import pairs
+            out['by_overlap'], overlaps = pairs.overlap_report(ds, poses, dev, *dgr_thresholds, counts, cfg.num_keypts)
+        if a.stage_metrics:
+            out['stage'] = (evaluate.stage_summary(counts, cfg.num_keypts) if scene_of is None
+                            else stage_report(scene_of, counts, cfg.num_keypts))
+            evaluate.write_stage_metrics(os.path.join(log_root, 'stage_metrics.json'), labels, counts, cfg.num_keypts, out['stage'],
+                                         overlaps)
+        print(json.dumps(out))
+    if world > 1:
+        torch.distributed.destroy_process_group()
+    return poses if rank == 0 else None

@@ -13,16 +13,17 @@ The reference refines the odometry ground truth with open3d ICP on first use and
 (buffer_amd/icp.py::icp_batched) and fills the cache; --allow-odometry-gt skips the refinement.  The summary reports how many pairs used
 which source (`gt_source`).  Host code is file IO and bookkeeping; voxelisation, normals and registration run on the device."""
 import glob
-import math
+import json
 import os
+import time
 
 import numpy as np
 import torch
 
-from . import preprocess
-from .threedmatch import items_batched, upload  # the same device-sample -> pipeline-input packing
+from . import dist as bdist, driver, evaluate
 
 TEST_DRIVES = (8, 9, 10)                                            # KITTI/test_kitti.txt
+DGR_THRESHOLDS = (0.3, 1.0)                                         # RTE m, RRE degrees (KITTI/test.py:66-88)
 VELO2CAM = np.vstack((np.hstack([np.array([7.533745e-03, -9.999714e-01, -6.166020e-04, 1.480249e-02, 7.280733e-04, -9.998902e-01,
                                            9.998621e-01, 7.523790e-03, 1.480755e-02]).reshape(3, 3),
                                  np.array([-4.069766e-03, -7.631618e-02, -2.717806e-01]).reshape(3, 1)]), [0, 0, 0, 1])).T   # dataset.py:203-213
@@ -53,7 +54,7 @@ def select_pairs(scan_ids, positions, min_dist=10.0, window=100):
     return pairs
 
 
-class KittiTestSet:
+class KittiTestSet(driver.PairTestSet):
     """KITTIDataset(split='test') (dataset.py:44-70): scan pairs about 10 m apart along the trajectory."""
 
     def __init__(self, root, drives=TEST_DRIVES, downsample=0.05, voxel_size_0=0.30, max_num_pts=40000,
@@ -78,9 +79,6 @@ class KittiTestSet:
         if drive not in self._odo:
             self._odo[drive] = np.genfromtxt(os.path.join(self.pc_path, 'poses', '%02d.txt' % drive)).reshape(-1, 12)
         return self._odo[drive]
-
-    def __len__(self):
-        return len(self.files)
 
     def scan(self, drive, t):
         fn = os.path.join(self.pc_path, 'sequences', '%02d' % drive, 'velodyne', '%06d.bin' % t)
@@ -144,103 +142,38 @@ class KittiTestSet:
         drive, t0, t1 = self.files[index]
         return {'src_id': f'{drive:02d}/{t0:06d}', 'tgt_id': f'{drive:02d}/{t1:06d}', 'relt_pose': self.ground_truth(index, device)}
 
-    def item(self, index, device, seed=None):
-        """dataset.py:72-178 (test branch) -> sample dict of device tensors (+ relt_pose)."""
-        drive, t0, t1 = self.files[index]
-        out = self.meta(index, device)
-        for side, t in (('src', t0), ('tgt', t1)):
-            it = preprocess.prepare_fragment(torch.from_numpy(self.scan(drive, t)).to(device), self.downsample,
-                                             self.voxel_size_0, self.max_num_pts, seed=2 * index + (side == 'tgt') if seed is None else seed)
-            out[f'{side}_fds_pts'], out[f'{side}_sds_pts'] = it['fds_pts'], it['sds_pts']
-        return out
-
 
 def register_pairs(pipe, dataset, indices, batch=4, stage_metrics=False):
-    """This rank's share of the pairs through the device pipeline -> f32[k,4,4] (device), in the order of `indices`.
-    stage_metrics: also the per-stage metric rows against the data set's ground truth (BufferPipeline.register_batch,
-    metrics_gt=) -> (poses, counts int32[k,7] on the device); the poses are the same."""
-    dev = pipe.device
-    poses = []
-    idx = list(indices)
-    # batches software-pipelined over two HIP streams: reading and pre-processing the fragments of batch i+1 and its keypoint
-    # stage run beside the CNN kernels of batch i (BufferPipeline.register_batches; results equal batch-by-batch calls)
-    chunks = [idx[lo:lo + batch] for lo in range(0, len(idx), batch)]
-    makers = [(lambda ch=ch: [upload(s) for s in items_batched(dataset, ch, dev)]) for ch in chunks]
-    if not stage_metrics:
-        for ps in pipe.register_batches(makers, seeds=chunks):
-            poses += ps
-        return torch.stack(poses) if poses else torch.zeros((0, 4, 4), dtype=torch.float32, device=dev)
-    # each chunk's ground truth rides along (read when the chunk's fragments are): one metric launch per chunk after its pose recovery
-    gts = [(lambda ch=ch: [dataset.meta(i, dev)['relt_pose'] for i in ch]) for ch in chunks]
-    counts = []
-    for ps, cs in pipe.register_batches(makers, seeds=chunks, metrics_gt=gts):
-        poses += ps
-        counts.append(cs)
-    if not poses:
-        return torch.zeros((0, 4, 4), dtype=torch.float32, device=dev), torch.zeros((0, 7), dtype=torch.int32, device=dev)
-    return torch.stack(poses), torch.cat(counts)
+    """driver.register_pairs at this driver's default batch"""
+    return driver.register_pairs(pipe, dataset, indices, batch, stage_metrics)
 
 
-def summarize(dataset, poses, rte_thresh=0.3, rre_thresh=1.0):
+def summarize(dataset, poses, rte_thresh=DGR_THRESHOLDS[0], rre_thresh=DGR_THRESHOLDS[1]):
     """KITTI/test.py:66-88 (note: 0.3 m / 1 degree in the reference's script)."""
-    st = []
-    for i in range(len(dataset)):
-        T, gt = np.asarray(poses[i], np.float64), dataset.ground_truth(i)
-        rte = np.linalg.norm(T[:3, 3] - gt[:3, 3])
-        rre = np.arccos(np.clip((np.trace(T[:3, :3].T @ gt[:3, :3]) - 1) / 2, -1 + 1e-16, 1 - 1e-16)) * 180 / math.pi
-        st.append([rte < rte_thresh and rre < rre_thresh, rte, rre])
-    st = np.array(st, np.float64).reshape(-1, 3)
-    good = st[:, 0] == 1
+    out = driver.dgr_summary([evaluate.dgr_success(poses[i], dataset.ground_truth(i), rte_thresh, rre_thresh) for i in range(len(dataset))])
     src = list(dataset.gt_source.values())
-    return dict(pairs=int(st.shape[0]), recall=float(good.mean()) if st.size else 0.0,
-                te=float(st[good, 1].mean()) if good.any() else float('nan'), re=float(st[good, 2].mean()) if good.any() else float('nan'),
-                gt_source={k: src.count(k) for k in ('icp-cache', 'icp-device', 'odometry')})
+    out['gt_source'] = {k: src.count(k) for k in ('icp-cache', 'icp-device', 'odometry')}
+    return out
 
 
 def parse_args(argv=None):
     """the command line of main() -> (args, Config of --preset)"""
     import argparse
-
-    from .config import DRIVER_PRESETS, preset
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument('--root', required=True)
-    ap.add_argument('--preset', default=DRIVER_PRESETS['kitti'][0],
-                    help='constants and weights (buffer_amd/config.py): ' + ', '.join(DRIVER_PRESETS['kitti']) +
-                         ' (generalization/ThreeD2KITTI: 3DMatch weights, scale 10)')
-    ap.add_argument('--batch', type=int, default=4)
-    ap.add_argument('--limits', default=None)
+    driver.add_common_args(ap, 'kitti', 4, 'log_KITTI', ' (generalization/ThreeD2KITTI: 3DMatch weights, scale 10)')
     ap.add_argument('--allow-odometry-gt', action='store_true',
                     help='evaluate against raw odometry instead of refining it by ICP where <root>/icp/<drive>_<t0>_<t1>.npy is missing')
     ap.add_argument('--refine-gt', action='store_true',
                     help='only fill the ICP ground-truth cache <root>/icp/ (this rank\'s shard, --batch-icp pairs per call) and exit')
     ap.add_argument('--batch-icp', type=int, default=16)
-    ap.add_argument('--stage-metrics', action='store_true',
-                    help='also compute the per-stage ground-truth metrics (repeatability, inlier ratio, FMR, consensus precision): '
-                         'summary key "stage", per-pair rows in <log-root>/stage_metrics.json')
-    ap.add_argument('--log-root', default=None, help='where --stage-metrics writes stage_metrics.json (default: log_KITTI)')
-    ap.add_argument('--by-overlap', action='store_true',
-                    help='also compute every pair\'s overlap under the ground truth (buffer_amd/pairs.py) and report pair count, DGR recall '
-                         'and, with --stage-metrics, the stage figures per overlap band: summary key "by_overlap"')
-    a = ap.parse_args(argv)
-    try:
-        cfg = preset(a.preset, 'kitti')
-    except ValueError as e:
-        ap.error(str(e))
-    return a, cfg
+    return driver.parse_with_preset(ap, argv, 'kitti')
 
 
 def main(argv=None):
     """python -m buffer_amd.kitti --root <data root> [--preset 3DMatch->KITTI]   (one process per GPU under torchrun).
     Returns the poses f32[n,4,4] (numpy) on rank 0."""
-    import json
-    import time
-
-    import torch.distributed as dist
-
-    from . import dist as bdist
-    from .pipeline import BufferPipeline
     a, cfg = parse_args(argv)
-    rank, world, dev, cdev = bdist.init(int(os.environ.get('LOCAL_RANK', 0)))
+    ranks = rank, world, dev, _ = driver.init()
     ds = KittiTestSet(a.root, downsample=cfg.downsample, voxel_size_0=cfg.voxel_size_0, max_num_pts=cfg.max_num_pts,
                       allow_odometry_gt=a.allow_odometry_gt)
     if a.refine_gt:
@@ -249,43 +182,10 @@ def main(argv=None):
         done = ds.refine_ground_truths(ids, dev, a.batch_icp)
         print(json.dumps(dict(rank=rank, pairs=len(ids), refined=len(done), seconds=time.perf_counter() - t0)))
         if world > 1:
-            dist.destroy_process_group()
+            torch.distributed.destroy_process_group()
         return
-    pipe = BufferPipeline(cfg, dev)
-    if a.limits:
-        pipe.limits = [int(x) for x in a.limits.split(',')]
-    else:
-        if rank == 0:
-            host = []
-            for i in range(min(len(ds), 4)):
-                s = ds.item(i, dev)
-                host.append({k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in s.items()})
-            pipe.calibrate(host)
-        pipe.limits = bdist.broadcast_limits(pipe.limits if rank == 0 else [0, 0, 0], device=cdev)
-    ids = bdist.shard_indices(len(ds), rank, world)
-    t0 = time.perf_counter()
-    res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics)
-    poses = bdist.gather_poses(ids, res[0] if a.stage_metrics else res, len(ds), device=cdev)
-    counts = bdist.gather_counts(ids, res[1].to(cdev), len(ds), device=cdev).cpu().numpy() if a.stage_metrics else None
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    poses = poses.cpu().numpy()
-    if rank == 0:
-        out = summarize(ds, poses)
-        out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
-        overlaps = None
-        if a.by_overlap:
-            from . import pairs
-            out['by_overlap'], overlaps = pairs.overlap_report(ds, poses, dev, 0.3, 1.0, counts, cfg.num_keypts)       # (summarize's thresholds)
-        if a.stage_metrics:
-            from . import evaluate
-            out['stage'] = evaluate.stage_summary(counts, cfg.num_keypts)
-            evaluate.write_stage_metrics(os.path.join(a.log_root or 'log_KITTI', 'stage_metrics.json'),
-                                         ['%d %d %d' % f for f in ds.files], counts, cfg.num_keypts, out['stage'], overlaps)
-        print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
-    return poses if rank == 0 else None
+    return driver.run(a, cfg, ds, ranks, calibrate_pairs=4, dgr_thresholds=DGR_THRESHOLDS, log_root=a.log_root or 'log_KITTI',
+                      summarize=lambda poses: summarize(ds, poses), labels=['%d %d %d' % f for f in ds.files])
 
 
 if __name__ == '__main__':

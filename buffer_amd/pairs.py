@@ -220,7 +220,7 @@ def scene_pairs(fragments, world_poses, voxel=None, radius=None, min_overlap=0.3
 
 
 def write_gt(gt_dir, pairs, n_fragments, force=False, voxel=None, radius=None):
-    """gt.log and gt.info in the formats threedmatch.load_gt_log, evaluate.read_trajectory and evaluate.read_trajectory_info read
+    """gt.log and gt.info in the formats plyio.load_gt_log, evaluate.read_trajectory and evaluate.read_trajectory_info read
     (tab-separated, repr(float)), pairs (dicts of scene_pairs: i, j, T, info) ascending by (i, j), plus gt_overlap.json (per pair
     both directional overlaps, matched counts, inlier RMSE; the voxel / radius used).  Refuses to replace an existing gt.log
     unless force."""
@@ -322,7 +322,7 @@ def main(argv=None):
     import argparse
     import time
 
-    from .threedmatch import read_ply
+    from .plyio import read_ply
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument('--root', required=True)
     ap.add_argument('--scene', required=True)

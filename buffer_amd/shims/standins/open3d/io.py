@@ -6,7 +6,7 @@ from .geometry import PointCloud
 def read_point_cloud(filename, format="auto", remove_nan_points=True, remove_infinite_points=True, print_progress=False):
     """PLY vertex positions -> PointCloud (utils/tools.py:6-7).  A missing/unreadable file gives an EMPTY cloud and a
     warning, like open3d; the reference only reads x, y, z."""
-    from buffer_amd.threedmatch import read_ply
+    from buffer_amd.plyio import read_ply
     pc = PointCloud()
     try:
         pts = read_ply(filename).astype(np.float64)

@@ -9,8 +9,8 @@ import time
 import numpy as np
 import torch
 
-from . import evaluate, preprocess, synth
-from .threedmatch import upload
+from . import evaluate, synth
+from .driver import dgr_summary, pack_pair, pack_pairs, register_chunks
 
 OVERLAPS = (0.75, 0.6, 0.45, 0.3)            # a quarter of the stream at 0.3 (3DLoMatch territory)
 N_SCENES = 8
@@ -22,35 +22,26 @@ def generate(n_pairs, device, seed0=20000, overlaps=OVERLAPS, n_raw=250_000):
 
 
 def prepare(raw, cfg, index):
-    """one raw pair -> the reference's sample dict (device tensors), seeds as ThreeDMatchTestSet.item"""
-    out = {'relt_pose': raw['relt_pose']}
-    for j, side in enumerate(('src', 'tgt')):
-        it = preprocess.prepare_fragment(raw[f'{side}_raw'], cfg.downsample, cfg.voxel_size_0, cfg.max_num_pts, seed=2 * index + j)
-        out[f'{side}_fds_pts'], out[f'{side}_sds_pts'] = it['fds_pts'], it['sds_pts']
-    return out
+    """one raw pair -> the reference's sample dict (device tensors), seeds as PairTestSet.item"""
+    return pack_pair((raw['src_raw'], raw['tgt_raw']), (2 * index, 2 * index + 1), {'relt_pose': raw['relt_pose']}, cfg)
 
 
 def prepare_batch(raws, cfg, indices):
     """prepare() for several raw pairs with the normals of all 2B fragments estimated in one stacked pass (same result)"""
-    frs = preprocess.prepare_fragments([r[f'{side}_raw'] for r in raws for side in ('src', 'tgt')], cfg.downsample,
-                                       cfg.voxel_size_0, cfg.max_num_pts, seeds=[2 * i + j for i in indices for j in range(2)])
-    return [{'relt_pose': r['relt_pose'], 'src_fds_pts': frs[2 * k]['fds_pts'], 'src_sds_pts': frs[2 * k]['sds_pts'],
-             'tgt_fds_pts': frs[2 * k + 1]['fds_pts'], 'tgt_sds_pts': frs[2 * k + 1]['sds_pts']} for k, r in enumerate(raws)]
+    return pack_pairs([r[f'{side}_raw'] for r in raws for side in ('src', 'tgt')], [2 * i + j for i in indices for j in range(2)],
+                      [{'relt_pose': r['relt_pose']} for r in raws], cfg)
 
 
 def run(pipe, raws, batch=32, first_index=0):
     """Timed part: pre-processing + registration of every pair, `batch` pairs per set of stacked launches, batches
-    software-pipelined (BufferPipeline.register_batches: pre-processing and keypoint stage of batch i+1 on the side stream
-    beside the CNN kernels of batch i).  -> (poses f32[n,4,4] device, seconds)."""
+    software-pipelined (driver.register_chunks).  Pair k of `raws` is pair first_index + k of the stream.
+    -> (poses f32[n,4,4] device, seconds)."""
     dev = pipe.device
-    chunks = [list(range(lo, min(lo + batch, len(raws)))) for lo in range(0, len(raws), batch)]
+    ids = range(first_index, first_index + len(raws))
+    chunks = [list(ids[lo:lo + batch]) for lo in range(0, len(raws), batch)]
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    makers = [(lambda ids=ids: [upload(s) for s in prepare_batch([raws[i] for i in ids], pipe.cfg, [first_index + i for i in ids])])
-              for ids in chunks]
-    out = pipe.register_batches(makers, seeds=[[first_index + i for i in ids] for ids in chunks])
-    poses = [p for ps in out for p in ps]
-    res = torch.stack(poses) if poses else torch.zeros((0, 4, 4), device=dev)
+    res = register_chunks(pipe, chunks, lambda ch: prepare_batch([raws[i - first_index] for i in ch], pipe.cfg, ch))
     torch.cuda.synchronize(dev)
     return res, time.perf_counter() - t0
 
@@ -80,8 +71,4 @@ def evaluate_stream(raws, poses, first_index=0):
         nfrag = int(pr.max()) + 1
         _, recall, _, _ = evaluate.evaluate_registration(nfrag, np.array(sc['est']), pr, pr, np.array(sc['gt']), np.array(sc['info']))
         per_scene.append(float(recall))
-    st = np.array([[float(a), b, c] for a, b, c in stats]).reshape(-1, 3)
-    good = st[:, 0] == 1
-    return dict(pairs=n, dgr_recall=float(good.mean()) if n else 0.0, registration_recall=float(np.mean(per_scene)) if per_scene else 0.0,
-                per_scene=per_scene, te=float(st[good, 1].mean()) if good.any() else float('nan'),
-                re=float(st[good, 2].mean()) if good.any() else float('nan'))
+    return dict(dgr_summary(stats, 'dgr_recall'), registration_recall=float(np.mean(per_scene)) if per_scene else 0.0, per_scene=per_scene)

@@ -322,7 +322,7 @@ def make_eth_root(root, scenes=('gazebo_summer', 'wood_autmn'), stations=3, seed
                   spacing=9.0, non_finite_rows=0):
     """A mini ETH test set in the reference's layout (generalization/ThreeD2ETH/dataset.py:34-52): per scene `stations` terrestrial
     scans written as <root>/<scene>/Hokuyo_<k>.ply (f32, each in its own scanner frame) and a tab-separated gt.log (the format
-    threedmatch.load_gt_log parses) with every pair i < j: T_i @ inv(T_j), T_k = world -> scan k, so that inv(gt) maps scan i
+    plyio.load_gt_log parses) with every pair i < j: T_i @ inv(T_j), T_k = world -> scan k, so that inv(gt) maps scan i
     (source) into scan j (target).  Outdoor geometry: sloped ground over a 2*half m square; trunks with canopy clusters and shrubs for
     `wood_*` scenes, gazebo posts and roofs, walls and poles otherwise.  Scanners stand `spacing` m apart on a line, 1.6 m above the
     ground, yaw uniform, tilt <= 2 degrees; each sees up to `max_range` m with a point density falling off as 1/r (overlap is
@@ -330,7 +330,7 @@ def make_eth_root(root, scenes=('gazebo_summer', 'wood_autmn'), stations=3, seed
     reader drops them; so must ETHTestSet).  -> {scene: [T_k f64[4,4]]}.  Host-side numpy only."""
     import os
 
-    from .threedmatch import write_ply
+    from .plyio import write_ply
     rng = np.random.default_rng(seed)
     out = {}
     for scene in scenes:

@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 from buffer_amd import ops, stream  # noqa: E402
 from buffer_amd.config import THREEDMATCH  # noqa: E402
 from buffer_amd.pipeline import BufferPipeline  # noqa: E402
-from buffer_amd.threedmatch import upload  # noqa: E402
+from buffer_amd.driver import upload  # noqa: E402
 from oracle import ransac_o3d  # noqa: E402  (the checker; test infrastructure)
 
 

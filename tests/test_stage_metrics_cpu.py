@@ -166,8 +166,9 @@ def test_stage_metrics_option_parses_and_is_off_by_default(name):
 def test_register_pairs_take_the_flag():
     import inspect
     from buffer_amd import eth, kitti, threedmatch
-    for fn in (threedmatch.register_pairs, kitti.register_pairs, eth.register_pairs):
+    for fn, batch in ((threedmatch.register_pairs, 32), (kitti.register_pairs, 4), (eth.register_pairs, 32)):
         assert inspect.signature(fn).parameters['stage_metrics'].default is False
+        assert inspect.signature(fn).parameters['batch'].default == batch
 
 
 # ---------------------------------------------------------------------------------------------------- gather over gloo

@@ -60,7 +60,7 @@ def cost(a):
 
 def stream_table(a):
     from buffer_amd import stream
-    from buffer_amd.threedmatch import upload
+    from buffer_amd.driver import register_chunks
     dev = torch.device('cuda:0')
     cfg = replace(THREEDMATCH, num_keypts=1500)
     pipe = BufferPipeline(cfg, dev)
@@ -68,11 +68,8 @@ def stream_table(a):
     first = stream.prepare(raws[0], cfg, 0)
     pipe.calibrate([{k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in first.items()}])
     chunks = [list(range(lo, min(lo + 32, a.pairs))) for lo in range(0, a.pairs, 32)]
-    makers = [(lambda ids=ids: [upload(s) for s in stream.prepare_batch([raws[i] for i in ids], cfg, ids)]) for ids in chunks]
-    gts = [[raws[i]['relt_pose'] for i in ids] for ids in chunks]
-    out = pipe.register_batches(makers, seeds=chunks, metrics_gt=gts)
-    poses = torch.stack([p for ps, _ in out for p in ps]).cpu().numpy()
-    counts = torch.cat([c for _, c in out]).cpu().numpy()
+    poses, counts = (x.cpu().numpy() for x in register_chunks(
+        pipe, chunks, lambda ids: stream.prepare_batch([raws[i] for i in ids], cfg, ids), lambda ids: [raws[i]['relt_pose'] for i in ids]))
     ok = np.array([evaluate.dgr_success(poses[k], raws[k]['relt_pose'])[0] for k in range(a.pairs)])
     rows = {'all': np.arange(a.pairs)}
     for j, ov in enumerate(stream.OVERLAPS):

@@ -3,6 +3,7 @@ side stream): where the host thread spends a batch."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from buffer_amd import stream, synth
+from buffer_amd.driver import upload
 from buffer_amd.config import THREEDMATCH
 from buffer_amd.pipeline import BufferPipeline
 dev = torch.device('cuda:0')
@@ -11,7 +12,6 @@ raws = stream.generate(96, dev)
 pipe.calibrate([synth.make_pair(1000)])
 B = 16
 ids = [list(range(i, i + B)) for i in range(0, 96, B)]
-upload = stream.upload
 def maker(idl):
     return lambda: [upload(s) for s in stream.prepare_batch([raws[i] for i in idl], pipe.cfg, idl)]
 stream.run(pipe, raws[:32], batch=B); torch.cuda.synchronize()
