@@ -252,7 +252,8 @@ def test_voxelize_vs_oracle_spt(W, dev):
 
 
 def test_matching_and_pose_vs_reference(W, dev):
-    """mutual 1-NN, cost volume, hypotheses, scoring, refinement -> fixture F5."""
+    """mutual 1-NN, cost volume, hypotheses, scoring, refinement -> fixture F5 (40 matches: below every loop stride of registration.hip;
+    tests/test_pose_recovery_gpu.py takes the pose kernels past them, against float64)."""
     from buffer_amd import ops, registration
     f = load("match_tiny.npz")
     t = lambda a: torch.from_numpy(a).to(dev)
