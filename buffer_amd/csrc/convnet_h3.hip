@@ -33,24 +33,9 @@
 // [hi | lo'][lane][8], 4 KB per (tap, k-step) and wavefront, one step ahead in registers.
 #include "common.h"
 
-// Activation-image layouts (round 5; profiles/r05_h3_lds_layouts.txt).  0 (default, round 4): a tile = 16 CONSECUTIVE positions, rows of
-// 544 B.  One azimuth-wrapped lane per tile then costs an extra LDS cycle in each of the four 16-lane groups of every ds_read_b128 of
-// the dx = +-1 taps (+52 % read cycles; SQ_LDS_BANK_CONFLICT 45 % of SQ_LDS_IDX_ACTIVE).  1: tiles follow the MAP'S ROWS -- tiles
-// 0..6 = (y, x = 0..15), tile 7 = (y = 0..3) x (x = 16..19), tile 8 = (y = 4..6) x (x = 16..19) + 4 idle slots --, rows of 512 B, the
-// 16-byte chunk XOR-keyed: chunk' = chunk ^ key(y, x), key = (x == 19 ? 14 : 2 (x & 7)) ^ 8 (y & 1): every group of every tap reads
-// 16 distinct slots.  2: tiles = (y, x = 1..16) + narrow tiles (x = 17, 18, 19, 0), 544-byte rows, no key, round-4 addressing.
-// 1 and 2 remove the read conflicts (conflict cycles -56 %) with bit-identical outputs and do NOT make the kernel faster (LDS 43 %
-// busy, matrix pipe 73-76 %): kept as switches, 0 stays the default.
-#ifndef H3_ROWTILES
-#define H3_ROWTILES 0
-#endif
-#ifndef H3_S
-#if H3_ROWTILES == 1
-#define H3_S 512u
-#else
+// A tile = 16 CONSECUTIVE positions, rows of 544 B.  Two layouts without the read conflicts of the azimuth-wrapped lanes were built, gave
+// bit-identical outputs and did not make the kernel faster: profiles/r05_h3_lds_layouts.txt.
 #define H3_S 544u                       // bytes per position (136 words = 8 mod 64 banks; 528 measured the same, 560 is 20 % slower)
-#endif
-#endif
 #define H3_LO 256u                      // offset of the lo' plane inside a position's row
 #define H3_NPOS 140
 #define H3_ZERO (H3_NPOS * H3_S)        // the zero row
@@ -71,31 +56,9 @@ typedef __attribute__((address_space(3))) char* h3_lds_p;
 // tile slot (tile t, lane slot m) -> map position (y, x); false: an idle slot of tile 8 (y = 7 is returned: a virtual row)
 __device__ __forceinline__ bool h3_pos(int t, int m, int& y, int& x)
 {
-#if H3_ROWTILES == 1
-    if (t < 7) { y = t; x = m; return true; }
-    y = (t - 7) * 4 + (m >> 2); x = 16 + (m & 3);
-    return y <= 6;
-#elif H3_ROWTILES == 2
-    // rows shifted by one column: tiles 0..6 = (y, x = 1..16), tiles 7 / 8 = (y = 0..3 | 4..6) x (x = 17, 18, 19, 0).  No tap of a
-    // row tile wraps in azimuth (x - 1 .. x + 1 stays inside 0..17), the narrow tiles' four columns are cyclically consecutive, and
-    // with the 544-byte row stride 16 consecutive rows already sit on 16 distinct slots: no key, the round-4 addressing unchanged
-    if (t < 7) { y = t; x = m + 1; return true; }
-    y = (t - 7) * 4 + (m >> 2); x = 17 + (m & 3); x -= x >= 20 ? 20 : 0;
-    return y <= 6;
-#else
     const int p = 16 * t + m;
     y = p / 20; x = p - y * 20;
     return p < H3_NPOS;
-#endif
-}
-// XOR key of the 16-byte chunk index inside a position's 256-byte plane
-__device__ __forceinline__ unsigned h3_key(int y, int x)
-{
-#if H3_ROWTILES == 1
-    return (unsigned)((x == 19 ? 14 : 2 * (x & 7)) ^ (8 * (y & 1)));
-#else
-    return 0u;
-#endif
 }
 
 struct CylH3Params {
@@ -174,34 +137,18 @@ __device__ __forceinline__ void h3_gemm(unsigned lds0, __amdgpu_buffer_rsrc_t rs
     const unsigned lofs = lane * 16u;
     const unsigned tadr = lds0 + H3_TAB + (lane & 15) * 32u + (unsigned)pt0 * 2u;
     unsigned rc[NDW], rn[NDW];
-#if H3_ROWTILES == 1
-    // table entry = row << 5 | key; the lane's k-group (lane >> 4) is XORed into both halves of a packed pair once per tap, the
-    // k-step into the chunk bits at the read: address = lds0 + ((entry ^ k-group ^ 4 k-step) << 4)
-    const unsigned kx = (lane >> 4) * 0x10001u;
-#pragma unroll
-    for (int j = 0; j < NDW; j++) rc[j] = h3_lds32(tadr + 4 * j) ^ kx;
-    auto row = [&](const unsigned (&r)[NDW], int t, int ks) __attribute__((always_inline)) {
-        return ((((t & 1) ? (r[t >> 1] >> 16) : (r[t >> 1] & 0xffffu)) ^ (unsigned)(ks << 2)) << 4) + lds0;
-    };
-#else
     const unsigned kgo = lds0 + (lane >> 4) * 16u;
 #pragma unroll
     for (int j = 0; j < NDW; j++) rc[j] = h3_lds32(tadr + 4 * j);
     auto row = [&](const unsigned (&r)[NDW], int t, int ks) __attribute__((always_inline)) {
         return (((t & 1) ? (r[t >> 1] >> 16) : (r[t >> 1] & 0xffffu)) << 4) + kgo + (unsigned)ks * 64u;
     };
-#endif
-    // weights: the blocks (tap, k-step) of 4 KB, WD blocks ahead in registers.  A block feeds 6 PT matrix instructions (96 PT cycles).
+    // weights: the blocks (tap, k-step) of 4 KB, one block ahead in registers.  A block feeds 6 PT matrix instructions (96 PT cycles).
     // Two blocks ahead for the 2..5-tile wavefronts measured +-0 (85.0 vs 86.0 ms per 320 000 patches): the partner workgroup of the
     // CU covers the fetch; the kernel sits at 73 % matrix-pipe busy at the ~1.8 GHz the chip holds under f16 MFMA load.
-    constexpr int WD = 1;
-    h3u4 Wc[2][2], Wn[2][2], Wnn[2][2];
+    h3u4 Wc[2][2], Wn[2][2];
 #pragma unroll
     for (int q = 0; q < 4; q++) Wc[q >> 1][q & 1] = h3_ldw(rs, wofs + q * 1024u, lofs);
-    if constexpr (WD == 2) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) Wn[q >> 1][q & 1] = h3_ldw(rs, wofs + (9 * KS > 1 ? 4096u : 0u) + q * 1024u, lofs);
-    }
     h3u4 X[3][2];
 #pragma unroll
     for (int g = 0; g < 2; g++) {
@@ -212,21 +159,16 @@ __device__ __forceinline__ void h3_gemm(unsigned lds0, __amdgpu_buffer_rsrc_t rs
     for (int tap = 0; tap < 9; tap++) {
         const unsigned tn = tadr + (unsigned)(tap < 8 ? tap + 1 : 8) * 512u;
 #pragma unroll
-        for (int j = 0; j < NDW; j++) {
-            rn[j] = h3_lds32(tn + 4 * j);
-#if H3_ROWTILES == 1
-            rn[j] ^= kx;
-#endif
-        }
+        for (int j = 0; j < NDW; j++) rn[j] = h3_lds32(tn + 4 * j);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < S; s++) {
             const int pt = s % PT, ks = s / PT, g = s + 2;
-            if (pt == 0) {                                       // the weights WD blocks on (past the end: the last block again)
-                const int nstep = tap * KS + ks + WD;
+            if (pt == 0) {                                       // the weights of the next block (past the end: the last block again)
+                const int nstep = tap * KS + ks + 1;
                 const unsigned wn = wofs + (unsigned)(nstep < 9 * KS ? nstep : 9 * KS - 1) * 4096u;
 #pragma unroll
-                for (int q = 0; q < 4; q++) (WD == 2 ? Wnn : Wn)[q >> 1][q & 1] = h3_ldw(rs, wn + q * 1024u, lofs);
+                for (int q = 0; q < 4; q++) Wn[q >> 1][q & 1] = h3_ldw(rs, wn + q * 1024u, lofs);
             }
             {
                 const unsigned a = g < S ? row(rc, g % PT, g / PT) : row(rn, (g - S) % PT, ((g - S) / PT) % KS);
@@ -247,10 +189,7 @@ __device__ __forceinline__ void h3_gemm(unsigned lds0, __amdgpu_buffer_rsrc_t rs
             __builtin_amdgcn_sched_barrier(0);
             if (pt == PT - 1) {
 #pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    Wc[q >> 1][q & 1] = Wn[q >> 1][q & 1];
-                    if constexpr (WD == 2) Wn[q >> 1][q & 1] = Wnn[q >> 1][q & 1];
-                }
+                for (int q = 0; q < 4; q++) Wc[q >> 1][q & 1] = Wn[q >> 1][q & 1];
             }
         }
         // S steps moved the ring by S mod 3: bring it back so that the next tap starts at slot 0
@@ -279,7 +218,6 @@ __device__ __forceinline__ void h3_store(unsigned lds0, const h3f4 (&am)[2][PT],
         int py, px;
         const bool valid = h3_pos(pt0 + t, li, py, px);          // the lane's position in tile pt0 + t
         const unsigned p = (unsigned)(py * 20 + px);
-        const unsigned key = h3_key(py, px);
 #pragma unroll
         for (int n = 0; n < 2; n++) {
             const int c = 32 * ct + 16 * n + 4 * lk;
@@ -310,8 +248,8 @@ __device__ __forceinline__ void h3_store(unsigned lds0, const h3f4 (&am)[2][PT],
                 h3_split2(v[2], v[3], k2048, h1, l1);
                 const h3u2 hi = { h0, h1 }, lo = { l0, l1 };
                 if (valid) {
-                    // 4 channels = 8 bytes of the plane: chunk (c >> 3) keyed by the position, half (c & 4) inside it
-                    const unsigned a = lds0 + p * H3_S + ((((unsigned)c >> 3) ^ key) << 4) + ((unsigned)c & 4u) * 2u;
+                    // 4 channels = 8 bytes of the plane: chunk (c >> 3), half (c & 4) inside it
+                    const unsigned a = lds0 + p * H3_S + (((unsigned)c >> 3) << 4) + ((unsigned)c & 4u) * 2u;
                     *(__attribute__((address_space(3))) h3u2*)(size_t)a = hi;
                     *(__attribute__((address_space(3))) h3u2*)(size_t)(a + H3_LO) = lo;
                 }
@@ -377,18 +315,8 @@ __global__ void __launch_bounds__(H3_THREADS, 2) k_cyl_net_h3(const float* __res
         const int yy = yy0 + tap / 3 - 1;
         int xx = xx0 + tap % 3 - 1;
         xx += xx < 0 ? 20 : 0; xx -= xx >= 20 ? 20 : 0;
-#if H3_ROWTILES == 1
-        (void)ok;
-        const unsigned row = (t >= 9 || yy < 0 || yy > 6) ? (unsigned)H3_NPOS : (unsigned)(yy * 20 + xx);
-        *(__attribute__((address_space(3))) unsigned short*)(size_t)(lds0 + H3_TAB + 2u * e) = (unsigned short)((row << 5) | h3_key(yy, xx));
-#elif H3_ROWTILES == 2
-        (void)ok;                                                             // (idle slots read the row they would stand for, or zeros)
-        const unsigned row = (t >= 9 || yy < 0 || yy > 6) ? (unsigned)H3_NPOS : (unsigned)(yy * 20 + xx);
-        *(__attribute__((address_space(3))) unsigned short*)(size_t)(lds0 + H3_TAB + 2u * e) = (unsigned short)(row * (H3_S / 16));
-#else
         const unsigned row = (!ok || yy < 0 || yy > 6) ? (unsigned)H3_NPOS : (unsigned)(yy * 20 + xx);
         *(__attribute__((address_space(3))) unsigned short*)(size_t)(lds0 + H3_TAB + 2u * e) = (unsigned short)(row * (H3_S / 16));
-#endif
     }
     for (int i = tid; i < (int)(H3_S / 16); i += H3_THREADS) *(__attribute__((address_space(3))) h3u4*)(size_t)(lds0 + H3_ZERO + 16u * i) = (h3u4){ 0, 0, 0, 0 };
     {   // input x[cin0][140] fp32 -> split rows; a work item = (4 positions, 2 channels), channel pairs fastest (one position's
@@ -407,8 +335,8 @@ __global__ void __launch_bounds__(H3_THREADS, 2) k_cyl_net_h3(const float* __res
                 h3_split(a[j], h, l); hi[0] = h; lo[0] = l;
                 h3_split(b[j], h, l); hi[1] = h; lo[1] = l;
                 h3_watch(amax, a[j]); h3_watch(amax, b[j]);
-                const int pp = 4 * q + j, py = pp / 20;
-                const unsigned ad = lds0 + (unsigned)pp * H3_S + ((((unsigned)cp >> 2) ^ h3_key(py, pp - 20 * py)) << 4) + 4u * ((unsigned)cp & 3u);
+                const int pp = 4 * q + j;
+                const unsigned ad = lds0 + (unsigned)pp * H3_S + (((unsigned)cp >> 2) << 4) + 4u * ((unsigned)cp & 3u);
                 *(__attribute__((address_space(3))) unsigned*)(size_t)ad = __builtin_bit_cast(unsigned, hi);
                 *(__attribute__((address_space(3))) unsigned*)(size_t)(ad + H3_LO) = __builtin_bit_cast(unsigned, lo);
             }
@@ -419,8 +347,8 @@ __global__ void __launch_bounds__(H3_THREADS, 2) k_cyl_net_h3(const float* __res
         }
         const int nz = (cpad - cin0) >> 1;                       // zero channel pairs up to the k-step boundary (48 -> 64)
         for (int i = tid; i < H3_NPOS * nz; i += H3_THREADS) {
-            const int p = i / nz, cp = (cin0 >> 1) + i - p * nz, py = p / 20;
-            const unsigned ad = lds0 + (unsigned)p * H3_S + ((((unsigned)cp >> 2) ^ h3_key(py, p - 20 * py)) << 4) + 4u * ((unsigned)cp & 3u);
+            const int p = i / nz, cp = (cin0 >> 1) + i - p * nz;
+            const unsigned ad = lds0 + (unsigned)p * H3_S + (((unsigned)cp >> 2) << 4) + 4u * ((unsigned)cp & 3u);
             *(__attribute__((address_space(3))) unsigned*)(size_t)ad = 0u;
             *(__attribute__((address_space(3))) unsigned*)(size_t)(ad + H3_LO) = 0u;
         }

@@ -50,15 +50,7 @@
 #define WG_THREADS 256
 #define WG_BUF (WG_MAXC * WG_CS)
 #define WG_KSTEP (16 * WG_CS)  // bytes between k-steps (4 channels)
-#ifndef WG_PIN_FOLD
-#define WG_PIN_FOLD 1         // pin the folded outputs after every pass (0: k_cyl_net_wg leaves them to the compiler, +0.8 %)
-#endif
 #define WG_BLOCKS 16          // filter components per (input, output) channel
-#ifdef WG_EXP_NOBAR
-#define WG_SYNC() __builtin_amdgcn_sched_barrier(0)
-#else
-#define WG_SYNC() __syncthreads()
-#endif
 
 typedef float wgf4 __attribute__((ext_vector_type(4)));
 typedef float wgf2 __attribute__((ext_vector_type(2)));
@@ -74,12 +66,9 @@ struct CylWgParams {
 #endif
 };
 #ifdef WG_STAMP
-__device__ long long* wg_stamp_ptr;
-#define WG_STAMP_IN(SLOT) if ((threadIdx.x & 63) == 0) wg_stamp_ptr[((size_t)blockIdx.x * 4 + threadIdx.x / 64) * 20 + (SLOT)] = __builtin_amdgcn_s_memtime();
 #define WG_STAMP_AT(SLOT) if ((threadIdx.x & 63) == 0) P.stamps[((size_t)blockIdx.x * 4 + w) * 20 + (SLOT)] = __builtin_amdgcn_s_memtime();
 #else
 #define WG_STAMP_AT(SLOT)
-#define WG_STAMP_IN(SLOT)
 #endif
 
 // tile (ty, tx) held by row idx of the Winograd M-tile t = 0, 1 (branch-free)
@@ -235,6 +224,7 @@ __device__ __forceinline__ void wg_pass(unsigned (&RA)[3][4], __amdgpu_buffer_rs
 // -- three accumulator clears and half of the output-transform adds less per N-tile.  The bias (when this wavefront carries
 // it: K-split layers add it once) enters component (1, 1)'s accumulator before pass 1: F_1, F_2, F_3 then carry it once in
 // both columns.
+// FENCE (k_cost_net's rounds): a scheduling fence between a pass and its fold.
 template <int NN, int T0, int T1, unsigned KSTEP = WG_KSTEP, bool FENCE = false>
 __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_after, unsigned lofs, int niter,
                                          int wstride, unsigned pstride, const float* __restrict__ bias_lane, wgf4 (&W)[NN][2], wgf4 (&Y)[NN][3][2][2])
@@ -267,7 +257,7 @@ __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_r
         }
         constexpr int ICHAIN = (INEXT != 0 && wg_chains(I)) ? INEXT : -1;      // the next row component of this round, if any
         wg_pass<I, NN, T0, T1, wg_chains(I - 1), ICHAIN, KSTEP>(RA, rs, wp + I * pstride, INEXT == 0 ? wp_after : wp + (I + 1) * pstride, lofs, niter, wstride, W, acc, D);
-        if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);     // k_cost_net: the fold is not mixed into the next pass's start (spills)
+        if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);     // the fold is not mixed into the pass's end (k_cost_net spills without it)
 #pragma unroll
         for (int n = 0; n < NN; n++)
 #pragma unroll
@@ -284,12 +274,11 @@ __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_r
                 }
                 else if constexpr (I == 2) { Y[n][t][0][0] = f0; Y[n][t][0][1] = f1; }
                 else { Y[n][t][1][0] -= f0; Y[n][t][1][1] -= f1; }
-                // the folded values exist HERE: left free, the compiler sinks these sums below the next pass's loop and carries
-                // the accumulators of this pass (twice the registers) through it instead -- copies and, in k_cost_net, spills
-                if constexpr (FENCE || WG_PIN_FOLD) {
-                    if constexpr (I == 2) asm volatile("" : "+v"(Y[n][t][0][0]), "+v"(Y[n][t][0][1]));
-                    else asm volatile("" : "+v"(Y[n][t][1][0]), "+v"(Y[n][t][1][1]));
-                }
+                // the folded values exist HERE and are pinned: left free, the compiler sinks these sums below the next pass's loop and
+                // carries the accumulators of this pass (twice the registers) through it instead -- copies (+0.8 % on k_cyl_net_wg)
+                // and, in k_cost_net, spills
+                if constexpr (I == 2) asm volatile("" : "+v"(Y[n][t][0][0]), "+v"(Y[n][t][0][1]));
+                else asm volatile("" : "+v"(Y[n][t][1][0]), "+v"(Y[n][t][1][1]));
             }
     };
     run(integral_constant<int, 0>{});
@@ -466,34 +455,19 @@ __device__ __forceinline__ void wg_store_row6(const wgf4& Yr, int nt, int relu, 
     }
 }
 
-template <int T0, int T1, bool GLB>
-__device__ __forceinline__ void wg_store(const wgf4 (&Y)[3][2][2], int nt, int relu, float* __restrict__ act, float* __restrict__ out_glb,
-                                         int li, int lk)
+// All three M-tiles of one N-tile into the activation buffer
+__device__ __forceinline__ void wg_store(const wgf4 (&Y)[3][2][2], int nt, int relu, float* __restrict__ act, int li, int lk)
 {
 #pragma unroll
-    for (int t = T0; t < T1; t++) {
-        if (t == 2) wg_store_row6<GLB>(Y[t][0][0], nt, relu, act, out_glb, li, lk);     // (the one quad of M-tile 2 rides in slot [0][0])
-        else wg_store_tile<GLB>(Y[t], t, nt, relu, act, out_glb, li, lk);
+    for (int t = 0; t < 3; t++) {
+        if (t == 2) wg_store_row6<false>(Y[t][0][0], nt, relu, act, nullptr, li, lk);     // (the one quad of M-tile 2 rides in slot [0][0])
+        else wg_store_tile<false>(Y[t], t, nt, relu, act, nullptr, li, lk);
     }
 }
 
-// Window-row addresses of the lane: 2 Winograd M-tiles x 4 rows and row 5 of M-tile 2 (row 6 is an immediate offset behind it),
-// channel lk of k-step k0
-__device__ __forceinline__ void wg_addresses(const float* act, int k0, int li, int lk, unsigned (&RA)[3][4])
-{
-    const unsigned act_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)act + (unsigned)k0 * WG_KSTEP;
-#pragma unroll
-    for (int t = 0; t < 3; t++)
-#pragma unroll
-        for (int a = 0; a < (t == 2 ? 1 : 4); a++) RA[t][a] = wg_row_addr(act_addr, t, a, li, lk);
-}
-
 // The 9 window-row addresses depend on the lane only (the map's geometry is the same in every layer): formed ONCE per kernel and parked in
-// accumulation registers (round 6, WG_ADDR_PARK); a layer reads them back (one v_accvgpr_read each, plus one add where its K range does not
+// accumulation registers (round 6); a layer reads them back (one v_accvgpr_read each, plus one add where its K range does not
 // start at channel 0) instead of re-deriving tile coordinates and padding selects -- ~110 vector instructions per layer and wavefront.
-#ifndef WG_ADDR_PARK
-#define WG_ADDR_PARK 1
-#endif
 struct WgAddrPark { float a[3][4]; };
 __device__ __forceinline__ void wg_park_addresses(const float* act, int li, int lk, WgAddrPark& pk)
 {
@@ -522,58 +496,14 @@ __device__ __forceinline__ void wg_first_weights(__amdgpu_buffer_rsrc_t rs, unsi
         for (int k = K0; k < K1; k++) W[n][k] = wg_ldw(rs, wp + n * 256 + k * wstride, lofs);
 }
 
-// One layer with 32 output channels (two N-tiles, four wavefronts): wavefront w owns N-tile w & 1 over ALL three M-tiles and the
-// K half w >> 1; the upper half hands its partial sums (36 registers) to the lower one through the rows of the channels >= 64
-// (free: Cin <= 64), which adds them and stores (9 quads: 4 + 4 of the Winograd M-tiles, one of row 6).  Round 2 split the M-tiles {0} | {1, 2} over the wavefront pair instead: 16 against
-// 28 tile-components, i.e. the layer took 28 / 22 of its balanced time -- these two layers are 6.5 % of the MFMAs and were 11 % of
-// the kernel.  The bias rides in the lower half's accumulators.
+// One layer with 32 output channels (two N-tiles, four wavefronts), the M-split pair form inside each half of K: wavefront (h, half)
+// owns BOTH N-tiles for the Winograd M-tile h and the bottom row of N-tile h, over its half of K.  The upper half hands its partial
+// sums (nine quads: 4 + 4 of the Winograd M-tile, one of row 6) to the lower one through the rows of the channels >= 64 (free:
+// Cin <= 64), which adds them and stores; the bias rides in the lower half's accumulators.  (One N-tile per wavefront over all three
+// M-tiles pays a transform per 4 MFMAs instead of 8.  Round 2 split the M-tiles {0} | {1, 2} over the wavefront pair instead: 16
+// against 28 tile-components, the layer took 28 / 22 of its balanced time -- these two layers are 6.5 % of the MFMAs and were 11 %
+// of the kernel.)
 #define WG_XCH_C 64
-template <bool GLB>
-__device__ __forceinline__ void wg_layer_ksplit(float* __restrict__ act, float* __restrict__ out_glb, const float* __restrict__ wt,
-                                                const float* __restrict__ bias, int cin, int cout, int relu, int w, const WgAddrPark& pk)
-{
-    int lane = threadIdx.x & (WAVE - 1);
-    asm volatile("" : "+v"(lane));
-    const int li = lane & 15, lk = lane >> 4;
-    const int nt = w & 1, half = w >> 1;
-    const int k4 = cin >> 2, kn = k4 >> 1, k0 = half * kn, wstride = 256;
-    unsigned RA[3][4];
-#if WG_ADDR_PARK
-#pragma unroll
-    for (int t = 0; t < 3; t++)
-#pragma unroll
-        for (int a = 0; a < (t == 2 ? 1 : 4); a++) RA[t][a] = wg_parked(pk, t, a) + (unsigned)k0 * WG_KSTEP;
-#else
-    wg_addresses(act, k0, li, lk, RA);
-#endif
-    const __amdgpu_buffer_rsrc_t rs = wg_weights(wt);
-    const unsigned wp = (unsigned)nt * (WG_BLOCKS * cin * 16) + (unsigned)k0 * wstride;
-    const unsigned lofs = lane * 16;
-    wgf4 W[1][2];
-    wg_first_weights<1, 0, 2>(rs, wp, lofs, wstride, W);
-    wgf4 Y[1][3][2][2];
-    wg_round<1, 0, 2>(RA, rs, wp, wp, lofs, kn >> 2, wstride, (unsigned)(k4 * wstride), half ? nullptr : bias + nt * 16 + lk * 4, W, Y);
-    wgf4 Yb[1];
-    wg_round_direct<1>(RA[2][0], rs, wp, lofs, kn >> 2, wstride, (unsigned)(k4 * wstride), half ? nullptr : bias + nt * 16 + lk * 4, W, Yb);
-    Y[0][2][0][0] = Yb[0];
-    wgf4* slot = reinterpret_cast<wgf4*>(act + WG_XCH_C * WG_CS) + nt * 640 + lane;                  // 9 x 64 float4 per N-tile (in slots of 10)
-    if (half) {
-#pragma unroll
-        for (int q = 0; q < 9; q++) slot[q * 64] = Y[0][q >> 2][(q >> 1) & 1][q & 1];               // t = q / 4, u, column; t = 2 is one quad
-    }
-    WG_STAMP_IN(18)
-    WG_SYNC();                                       // partial sums are in place AND every wavefront has finished reading the input
-    WG_STAMP_IN(19)
-    if (!half) {
-#pragma unroll
-        for (int q = 0; q < 9; q++) Y[0][q >> 2][(q >> 1) & 1][q & 1] += slot[q * 64];
-        wg_store<0, 3, GLB>(Y[0], nt, relu, act, out_glb, li, lk);
-    }
-}
-
-// The same 32-channel layer with the M-split pair form inside each K half (WG_KSPLIT_PAIRS): wavefront (h, half) owns BOTH N-tiles
-// for the Winograd M-tile h and the bottom row of N-tile h, over its half of K -- one transform per 8 MFMAs instead of 4, the same
-// nine quads of partial sums to hand over.
 template <bool GLB>
 __device__ __forceinline__ void wg_layer_mksplit(float* __restrict__ act, float* __restrict__ out_glb, const float* __restrict__ wt,
                                                  const float* __restrict__ bias, int cin, int cout, int relu, int w, const WgAddrPark& pk)
@@ -584,21 +514,12 @@ __device__ __forceinline__ void wg_layer_mksplit(float* __restrict__ act, float*
     const int h = w & 1, half = w >> 1;
     const int k4 = cin >> 2, kn = k4 >> 1, k0 = half * kn, wstride = 512;
     unsigned RA[3][4];
-#if WG_ADDR_PARK
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const unsigned r0 = wg_parked(pk, 0, a), r1 = wg_parked(pk, 1, a);
         RA[0][a] = (h ? r1 : r0) + (unsigned)k0 * WG_KSTEP; RA[1][a] = RA[0][a];
     }
     RA[2][0] = wg_parked(pk, 2, 0) + (unsigned)k0 * WG_KSTEP;
-#else
-    {
-        const unsigned act_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)act + (unsigned)k0 * WG_KSTEP;
-#pragma unroll
-        for (int a = 0; a < 4; a++) { RA[0][a] = wg_row_addr(act_addr, h, a, li, lk); RA[1][a] = RA[0][a]; }
-        RA[2][0] = wg_row_addr(act_addr, 2, 0, li, lk);
-    }
-#endif
     const __amdgpu_buffer_rsrc_t rs = wg_weights(wt);
     const unsigned wp = (unsigned)k0 * wstride;                            // [pair 0][i][k-step][n2][lane][j]
     const unsigned wpb = wp + (unsigned)h * 256;
@@ -617,7 +538,7 @@ __device__ __forceinline__ void wg_layer_mksplit(float* __restrict__ act, float*
         for (int q = 0; q < 8; q++) slot[q * 64] = Y[q >> 2][0][(q >> 1) & 1][q & 1];
         slot[8 * 64] = Yb[0];
     }
-    WG_SYNC();                                       // partial sums are in place AND every wavefront has finished reading the input
+    __syncthreads();                                 // partial sums are in place AND every wavefront has finished reading the input
     if (!half) {
 #pragma unroll
         for (int q = 0; q < 8; q++) Y[q >> 2][0][(q >> 1) & 1][q & 1] += slot[q * 64];
@@ -641,21 +562,12 @@ __device__ __forceinline__ void wg_layer_msplit(float* __restrict__ act, const f
     const int pair = w & 1, h = w >> 1;
     const int k4 = cin >> 2, wstride = 512;
     unsigned RA[3][4];
-#if WG_ADDR_PARK
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const unsigned r0 = wg_parked(pk, 0, a), r1 = wg_parked(pk, 1, a);
         RA[0][a] = h ? r1 : r0; RA[1][a] = RA[0][a];
     }
     RA[2][0] = wg_parked(pk, 2, 0);
-#else
-    {
-        const unsigned act_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)act;
-#pragma unroll
-        for (int a = 0; a < 4; a++) { RA[0][a] = wg_row_addr(act_addr, h, a, li, lk); RA[1][a] = RA[0][a]; }
-        RA[2][0] = wg_row_addr(act_addr, 2, 0, li, lk);
-    }
-#endif
     const __amdgpu_buffer_rsrc_t rs = wg_weights(wt);
     const unsigned wp = (unsigned)pair * (WG_BLOCKS * cin * 32);           // [pair][i][k-step][n2][lane][j]
     const unsigned wpb = wp + (unsigned)h * 256;                           // the N-tile of the pair whose bottom row is this wavefront's
@@ -668,22 +580,16 @@ __device__ __forceinline__ void wg_layer_msplit(float* __restrict__ act, const f
     wgf4 W1[1][2] = { { W2[0][0], W2[0][1] } };
     wgf4 Yb[1];
     wg_round_direct<1>(RA[2][0], rs, wpb, lofs, k4 >> 2, wstride, pstride, bias + (2 * pair + h) * 16 + lk * 4, W1, Yb);
-    WG_SYNC();                                       // every wavefront has finished reading the layer's input
+    __syncthreads();                                 // every wavefront has finished reading the layer's input
     wg_store_tile<false>(Y[0][0], h, 2 * pair, relu, act, nullptr, li, lk);
     wg_store_tile<false>(Y[1][0], h, 2 * pair + 1, relu, act, nullptr, li, lk);
     wg_store_row6<false>(Yb[0], 2 * pair + h, relu, act, nullptr, li, lk);
 }
 
-// N-tiles per wavefront of a layer: 2 (the paired form below) or 1.  The filter tiling follows it (buf_winograd_tile_weights).
-// Pairs for the 64-channel layers too (two wavefronts per pair, K split between them, partial sums exchanged through the dead
-// half of the buffer) measured 1 % slower, before and after the filter stream became cheap: short K loops, a third barrier.
-#ifndef WG_PAIR_NT2
-#define WG_PAIR_NT2 1         // 128-channel layers: both Winograd M-tiles of a pair in ONE round (0: a round per M-tile, +0.9 %)
-#endif
-#ifndef WG_KSPLIT_PAIRS
-#define WG_KSPLIT_PAIRS 1
-#endif
-__host__ __device__ constexpr int wg_group(int cin, int cout) { return (cout >= 64 || WG_KSPLIT_PAIRS) ? 2 : 1; }
+// N-tiles per wavefront of a layer: every layer form owns N-tile pairs.  The filter tiling follows it (buf_winograd_tile_weights).
+// (For the 64-channel layers, pairs with K split over two wavefronts and the partial sums exchanged through the dead half of the
+// buffer measured 1 % slower than the M split, before and after the filter stream became cheap: short K loops, a third barrier.)
+__host__ __device__ constexpr int wg_group(int cin, int cout) { return 2; }
 
 // Outputs of M-tile T of both N-tiles of a pair -> accumulation registers (see wg_layer_pair)
 template <int T>
@@ -705,22 +611,13 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
 {
     int lane = threadIdx.x & (WAVE - 1);
     asm volatile("" : "+v"(lane));
-    const int li = lane & 15, lk = lane >> 4;
-#ifdef WG_EXP_SAMEW_PAIR
-    const int k4 = cin >> 2, wstride = relu >> 4;
-#else
+    const int lk = lane >> 4;
     const int k4 = cin >> 2, wstride = 512;
-#endif
     unsigned RA[3][4];
-#if WG_ADDR_PARK
-    (void)li;
 #pragma unroll
     for (int t = 0; t < 3; t++)
 #pragma unroll
         for (int a = 0; a < (t == 2 ? 1 : 4); a++) RA[t][a] = wg_parked(pk, t, a);
-#else
-    wg_addresses(act, 0, li, lk, RA);
-#endif
     const __amdgpu_buffer_rsrc_t rs = wg_weights(wt);
     const unsigned wp = (unsigned)pair * (WG_BLOCKS * cin * 32);           // [pair][i][k-step][n2][lane][j]
     const unsigned lofs = lane * 16;
@@ -733,21 +630,14 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
     // file gives a wavefront 256 registers of either kind): left in VGPRs the compiler parked 19 of the then 20 quads in scratch memory
     // (264 KB of HBM traffic per patch); the rounds then run in ~130 VGPRs with no scratch at all.
     float park[2][3][16];
-#if WG_PAIR_NT2
     wg_round<2, 0, 2>(RA, rs, wp, wp, lofs, k4 >> 2, wstride, pstride, bv, W1, Y);     // both Winograd M-tiles in one round
     wg_park<0>(Y, park);
     wg_park<1>(Y, park);
-#else
-    wg_round<2, 0, 1>(RA, rs, wp, wp, lofs, k4 >> 2, wstride, pstride, bv, W1, Y);
-    wg_park<0>(Y, park);
-    wg_round<2, 1, 2>(RA, rs, wp, wp, lofs, k4 >> 2, wstride, pstride, bv, W1, Y);
-    wg_park<1>(Y, park);
-#endif
     wgf4 Yb[2];
     wg_round_direct<2>(RA[2][0], rs, wp, lofs, k4 >> 2, wstride, pstride, bv, W1, Yb);
     Y[0][2][0][0] = Yb[0]; Y[1][2][0][0] = Yb[1];
     wg_park<2>(Y, park);
-    WG_SYNC();                                       // every wavefront has finished reading the layer's input
+    __syncthreads();                                 // every wavefront has finished reading the layer's input
     int lane_s = threadIdx.x & (WAVE - 1);
     asm volatile("" : "+v"(lane_s));                 // the store offsets are formed here, not kept (spilled) from the layer's start
 #pragma unroll
@@ -757,7 +647,7 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
 #pragma unroll
             for (int q = 0; q < (t == 2 ? 4 : 16); q++)
                 asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(Y[n][t][q >> 3][(q >> 2) & 1][q & 3]) : "a"(park[n][t][q]));
-        wg_store<0, 3, false>(Y[n], 2 * pair + n, relu, act, nullptr, lane_s & 15, lane_s >> 4);
+        wg_store(Y[n], 2 * pair + n, relu, act, lane_s & 15, lane_s >> 4);
     }
 }
 
@@ -799,29 +689,20 @@ __device__ __forceinline__ void cyl_net_wg_body(const float* __restrict__ x, con
     __syncthreads();
     WG_STAMP_AT(0)
     WgAddrPark pk;
-#if WG_ADDR_PARK
     {
         int lane0 = threadIdx.x & (WAVE - 1);
         asm volatile("" : "+v"(lane0));
         wg_park_addresses(act, lane0 & 15, lane0 >> 4, pk);
     }
-#endif
 #pragma unroll 1
     for (int l = 0; l < WG_LAYERS; l++) {
         const int cin = P.cin[l], cout = P.cout[l];
         if (cout == 128) wg_layer_pair(act, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-        else if (cout == 64) {
-            wg_layer_msplit(act, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-        }
-#if WG_KSPLIT_PAIRS
+        else if (cout == 64) wg_layer_msplit(act, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
         else if (l < WG_LAYERS - 1) wg_layer_mksplit<false>(act, nullptr, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
         else wg_layer_mksplit<true>(act, y + (size_t)patch * cout * 140, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-#else
-        else if (l < WG_LAYERS - 1) wg_layer_ksplit<false>(act, nullptr, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-        else wg_layer_ksplit<true>(act, y + (size_t)patch * cout * 140, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-#endif
         WG_STAMP_AT(2 * l + 1)
-        WG_SYNC();
+        __syncthreads();
         WG_STAMP_AT(2 * l + 2)
     }
 #ifdef WG_STAMP
@@ -886,30 +767,35 @@ extern "C" int buf_winograd_tile_weights(const float* w_host, int cout, int cin,
 // N-tiles per group in the filter tiling of a layer with these widths (the Python side asks instead of restating the rule)
 extern "C" int buf_winograd_group(int cin, int cout) { return wg_group(cin, cout); }
 
-// x f32[np,48,140] -> y f32[np,32,140]; weights in the Winograd-domain tiling (see CylWgParams).
-static int wg_launch(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
-                     const int* cout_host, const int* relu_host, float* y, const int* only_if, void* stream);
-
-extern "C" int buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
-                                      const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream)
+// The widths k_cyl_net_wg is built for, stated once: what buf_cylindrical_net_wg accepts and buf_cylindrical_net_wg_supports reports.
+static int wg_check_widths(const int* cin, const int* cout)
 {
-    return wg_launch(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, y, nullptr, stream);
+    for (int l = 0; l < WG_LAYERS; l++) {
+        const int ci = cin[l], co = cout[l];
+        BUF_REQUIRE(ci > 0 && ci % 16 == 0 && ci <= WG_MAXC && (co == 32 || co == 64 || co == 128), BUF_EINVAL,
+                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d", l, ci, co);
+        BUF_REQUIRE(co != 128 || ci % 32 == 0, BUF_EINVAL,
+                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (128 output channels need Cin %% 32 == 0)", l, ci, co);
+        BUF_REQUIRE(co != 32 || (ci % 32 == 0 && ci <= 64), BUF_EINVAL,
+                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (32 output channels need Cin = 32 or 64)", l, ci, co);
+        BUF_REQUIRE(l == 0 || ci == cout[l - 1], BUF_EINVAL, "buf_cylindrical_net_wg: layer %d width mismatch", l);
+        // The 32-output layers hand their K-split partial sums over through the rows of the channels 64..95, zero words included
+        // (wg_layer_mksplit); those words are written once at kernel start, so no wider layer may follow.
+        BUF_REQUIRE(l == 0 || cout[l - 1] != 32 || co == 32, BUF_EINVAL,
+                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (only 32-output layers may follow a 32-output layer)", l, ci, co);
+    }
+    BUF_REQUIRE(cout[WG_LAYERS - 1] == 32, BUF_EINVAL, "buf_cylindrical_net_wg: the last layer must have 32 channels");
+    return BUF_OK;
 }
 
 // 0 when the Winograd fp32 kernel is built for this stack of widths (what buf_cylindrical_net_wg would accept), else BUF_EINVAL with the reason
 extern "C" int buf_cylindrical_net_wg_supports(const int* cin_host, const int* cout_host)
 {
     BUF_REQUIRE(cin_host && cout_host, BUF_EINVAL, "buf_cylindrical_net_wg_supports: null argument");
-    for (int l = 0; l < WG_LAYERS; l++) {
-        const int ci = cin_host[l], co = cout_host[l];
-        const bool ok = ci > 0 && ci % 16 == 0 && ci <= WG_MAXC && (co == 32 || co == 64 || co == 128) && (co != 128 || ci % 32 == 0) &&
-                        (co != 32 || (ci % 32 == 0 && ci <= 64)) && (l == 0 || ci == cout_host[l - 1]) && (l == 0 || cout_host[l - 1] != 32 || co == 32);
-        BUF_REQUIRE(ok, BUF_EINVAL, "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d", l, ci, co);
-    }
-    BUF_REQUIRE(cout_host[WG_LAYERS - 1] == 32, BUF_EINVAL, "buf_cylindrical_net_wg: the last layer must have 32 channels");
-    return BUF_OK;
+    return wg_check_widths(cin_host, cout_host);
 }
 
+// x f32[np,48,140] -> y f32[np,32,140]; weights in the Winograd-domain tiling (see CylWgParams).
 static int wg_launch(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
                      const int* cout_host, const int* relu_host, float* y, const int* only_if, void* stream)
 {
@@ -921,19 +807,8 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
         P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
         P.cin[l] = cin_host[l]; P.cout[l] = cout_host[l]; P.relu[l] = relu_host[l];
         BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "buf_cylindrical_net_wg: null weights for layer %d", l);
-        BUF_REQUIRE(P.cin[l] % 16 == 0 && P.cin[l] <= WG_MAXC && (P.cout[l] == 32 || P.cout[l] == 64 || P.cout[l] == 128),
-                    BUF_EINVAL, "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d", l, P.cin[l], P.cout[l]);
-        BUF_REQUIRE(P.cout[l] != 128 || P.cin[l] % 32 == 0, BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (128 output channels need Cin %% 32 == 0)", l, P.cin[l], P.cout[l]);
-        BUF_REQUIRE(P.cout[l] != 32 || (P.cin[l] % 32 == 0 && P.cin[l] <= 64), BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (32 output channels need Cin = 32 or 64)", l, P.cin[l], P.cout[l]);
-        BUF_REQUIRE(l == 0 || P.cin[l] == P.cout[l - 1], BUF_EINVAL, "buf_cylindrical_net_wg: layer %d width mismatch", l);
-        // The 32-output layers hand their K-split partial sums over through the rows of the channels 64..95, zero words included
-        // (wg_layer_mksplit / wg_layer_ksplit); those words are written once at kernel start, so no wider layer may follow.
-        BUF_REQUIRE(l == 0 || P.cout[l - 1] != 32 || P.cout[l] == 32, BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (only 32-output layers may follow a 32-output layer)", l, P.cin[l], P.cout[l]);
     }
-    BUF_REQUIRE(P.cout[WG_LAYERS - 1] == 32, BUF_EINVAL, "buf_cylindrical_net_wg: the last layer must have 32 channels");
+    if (int rc = wg_check_widths(P.cin, P.cout)) return rc;
     P.only_if = only_if;
     size_t lds = sizeof(float) * WG_BUF;
     static LdsGrant grant, grant_rerun;
@@ -944,7 +819,6 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
     bool timed = !only_if && timing_begin((hipStream_t)stream, &span, 2.0 * 140 * macs * npatch, BUF_TIMED_CYL_NET);   // (a masked re-run is not a full launch)
 #ifdef WG_STAMP
     BUF_CHECK_HIP(hipMalloc(&P.stamps, (size_t)npatch * (4 * 20 + 4) * sizeof(long long)));
-    BUF_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(wg_stamp_ptr), &P.stamps, sizeof(P.stamps)));
 #endif
     if (only_if) k_cyl_net_wg_rerun<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
     else k_cyl_net_wg<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
@@ -966,14 +840,6 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
             double dc = 0, dr = 0;
             for (int b = npatch / 2; b < npatch; b++) { const long long* q = h + (size_t)npatch * 80 + (size_t)b * 4; dc += (double)(q[2] - q[0]); dr += (double)(q[3] - q[1]); }
             fprintf(stderr, "  WG_STAMP in-kernel clock: %.0f shader cycles per workgroup over %.0f ticks of the 100 MHz counter -> %.3f GHz\n", dc / n, dr / n, dc / dr * 0.1);
-            double c7[4] = {}, b7[4] = {}, s7[4] = {};
-            for (int b = npatch / 2; b < npatch; b++)
-                for (int w = 0; w < 4; w++) {
-                    const long long* q = h + ((size_t)b * 4 + w) * 20;
-                    c7[w] += (double)(q[18] - q[14]); b7[w] += (double)(q[19] - q[18]); s7[w] += (double)(q[15] - q[19]);
-                }
-            fprintf(stderr, "  last layer per wave: K loops %6.0f %6.0f %6.0f %6.0f | barrier %5.0f %5.0f %5.0f %5.0f | add + store %5.0f %5.0f %5.0f %5.0f\n",
-                    c7[0] / n, c7[1] / n, c7[2] / n, c7[3] / n, b7[0] / n, b7[1] / n, b7[2] / n, b7[3] / n, s7[0] / n, s7[1] / n, s7[2] / n, s7[3] / n);
             fprintf(stderr, "WG_STAMP: %ld workgroups, layers total %.0f cycles per patch, input phase %.0f\n", n, tot / n, pre / n);
             for (int l = 0; l < WG_LAYERS; l++) {
                 const double mf = 38.0 * (P.cin[l] / 4) * (P.cout[l] / 16) / 4;     // MFMAs per wave
@@ -986,4 +852,10 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
     }
 #endif
     return BUF_OK;
+}
+
+extern "C" int buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
+                                      const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream)
+{
+    return wg_launch(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, y, nullptr, stream);
 }

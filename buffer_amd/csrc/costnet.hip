@@ -17,8 +17,8 @@
 // (two workgroups per CU).  Layers 1..5 are unpadded 3 x 3 correlations over (n, l) -- layer 1 collapses k' (3 -> 1): its three
 // k' planes are 96 input channels; 18 -> 16 -> 14 -> 12 -> 10 -> 8; together 92 % of the kernel's matrix instructions in the
 // direct form -- and run in the Winograd F(2x2, 3x3) domain on the pass machinery of csrc/convnet_wg.hip (phase A.2 and cw_layer
-// below: 0.49 of their direct-form MFMAs).  -DCV_L1_DIRECT=1 keeps layer 1 in the direct form (three-row chunks, a sliding
-// window of accumulator rows: 0.83 of the matrix peak executed, and 14 % slower).
+// below: 0.49 of their direct-form MFMAs).  (Layer 1 in the direct form -- three-row chunks, a sliding window of accumulator
+// rows -- executed 0.83 of the matrix peak and was 14 % slower.)
 // All GEMMs run on v_mfma_f32_16x16x4_f32 (fp32), weights (BN folded; [K][Cout] MFMA-tiled, or G g G^T in the Winograd tiling)
 // stream from L2.
 // FLOP accounting: bench.py credits the DENSE algorithmic count of SURVEY 8d (0.160 GFLOP/match); executed: 0.0519 GFLOP.
@@ -107,29 +107,13 @@ __device__ __forceinline__ void cv_gemm_static(cvx4 (&acc)[MT][NT], Loader& L, c
 // LDS regions of phase A inside the bufB half (floats):
 #define CVA_SP 0          // [5][24][36]  source map, azimuth padded circularly by 2 on both sides (column = l + 2)
 #define CVA_TP 4320       // [5][20][36]  target map
-#ifndef CV_L1_DIRECT
-#define CV_L1_DIRECT 0    // 1: layer 1 in the direct form (round 2 / early round 3: three-row chunks, sliding accumulator window)
-#endif
-#ifndef CV_L1_PAIRS
-#define CV_L1_PAIRS 1     // Winograd layer 1: N-tile pairs with K split over the wavefront pair (0: one N-tile per wavefront over all of K)
-#endif
-#if CV_L1_DIRECT
-#define CVA_SM 7920       // [3][20][36]  Sterm[k'][j][o]
-#define CVA_TB 10080      // [3][18][36]  b[o] - Tterm[k'][l'][o]
-#else
 #define CVA_SM 16376      // the two maps sit at the END of the buffer: the six-row chunk of the Winograd layer 1 takes its start
 #define CVA_TB 18536      //   (18536 + 3 * 18 * 36 = 20480 = CV_BUF)
 #define CVA_XC 0          // [96 = (k', c)][CW_CSX]: six layer-0 rows n' of 18 columns in rows of CW_RSX, channel-major
-#ifndef CW_RSX
 #define CW_RSX 18         // (rows of 24 and channels 160 apart -- the two tile rows of an M-tile and the two channels of a half-wave on
 #define CW_CSX 112        //   the four quarters of the 64 banks, conflict-free -- measured +-0 against this compact layout)
-#endif
-#define CVA_XCH (96 * CW_CSX)      // 2 x 8 x 64 float4 of partial sums handed over per chunk (CV_L1_PAIRS)
+#define CVA_XCH (96 * CW_CSX)      // 2 x 8 x 64 float4 of partial sums handed over per chunk
 static_assert(CVA_XCH + 2 * 8 * 64 * 4 <= CVA_SM, "the exchange slots fit between the chunk and the layer-0 maps");
-#endif
-#define CVA_R0 0          // [3][54][36]  chunk of three layer-0 rows (aliases SP/TP once the two small GEMMs are done)
-#define CVA_R1 12024      // second chunk buffer; ends at 17856 <= CV_BUF
-#define CVA_RROW (54 * CV_C32)
 
 // S-term: A[m=(k',j)][(dk,e), c] = S[c][k'+dk][(j+e) mod 20], e = -2..2;  K = (dk*5 + e+2)*32 + c  (30 groups of 16)
 struct SLoader {
@@ -154,39 +138,6 @@ struct TLoader {
         for (int p = 0; p < 4; p++) a[p][0] = v[p];
     }
 };
-
-// layer 1, one dn slab over MT layer-0 rows of the chunk: A[t][m=l''][(dk,dl), c] = R[t][dk*18 + l''+dl][c];  K = (dk*3+dl)*32 + c
-template <int MT>
-struct L1Loader {
-    const float* base;                                   // first row of the chunk this call uses + l''*36 + lk*4
-    __device__ __forceinline__ void load(float (&a)[4][MT], int g) const
-    {
-        const int tap = g >> 1, cg = g & 1, dk = tap / 3, dl = tap - dk * 3;
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            const cvx4 v = *reinterpret_cast<const cvx4*>(base + t * CVA_RROW + (dk * 18 + dl) * CV_C32 + cg * 16);
-#pragma unroll
-            for (int p = 0; p < 4; p++) a[p][t] = v[p];
-        }
-    }
-};
-
-// three layer-0 rows n' = r0 .. r0+2 into a chunk buffer: R[t][pos=(k',l')][o] = relu(Smap[k'][(l'-n') mod 20][o] + Tb[pos][o])
-__device__ __forceinline__ void form_rows(float* __restrict__ R, const float* __restrict__ SM, const float* __restrict__ TB, int r0)
-{
-    for (int i = threadIdx.x; i < 3 * 54 * 8; i += CV_THREADS) {
-        const int t = i / 432, rem = i - t * 432, pos = rem >> 3, c4 = rem & 7;
-        const int kq = pos / 18, lq = pos - kq * 18;
-        int j = lq - (r0 + t);
-        j = j < 0 ? j + 20 : j;
-        const cvx4 sv = *reinterpret_cast<const cvx4*>(SM + (kq * 20 + j) * CV_C32 + c4 * 4);
-        const cvx4 tv = *reinterpret_cast<const cvx4*>(TB + pos * CV_C32 + c4 * 4);
-        cvx4 v;
-#pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = fmaxf(sv[q] + tv[q], 0.f);
-        *reinterpret_cast<cvx4*>(R + (t * 54 + pos) * CV_C32 + c4 * 4) = v;
-    }
-}
 
 // layers 2..9: valid (KW x KW) convolution over an LDS-resident [WIN*WIN][CIN+4] map;  K = (dn*KW + dl)*CIN + c.
 // The tap loop is a runtime loop, the CIN/16 channel groups of a tap are unrolled: inside a tap every LDS and
@@ -334,12 +285,7 @@ __device__ __forceinline__ void cw_layer(float* __restrict__ map, const float* _
 {
     static_assert(MT >= 1 && MT <= 2 && MT2 >= 0 && MT2 <= 1 && RS % 2 == 0 && CS % 2 == 0, "");
     constexpr unsigned KSTEP = 16u * CS;
-#ifdef CW_EXP_SAMEW
-    constexpr int k4 = CIN / 4;
-    const int wstride = (int)(blockDim.x >> 10);              // timing experiment: a run-time zero (every k-step fetches the same KB: L1 hits)
-#else
     constexpr int k4 = CIN / 4, wstride = 256 * NN;
-#endif
     int lane = threadIdx.x & (WAVE - 1);
     asm volatile("" : "+v"(lane));
     const int li = lane & 15, lk = lane >> 4;
@@ -375,17 +321,10 @@ __device__ __forceinline__ void cw_layer(float* __restrict__ map, const float* _
         if constexpr (MT2 > 0) cw_store_tile<HIN, TYPM, RSO, CSO, POSMAJOR>(Y2[n][0], t0 + MT, ng * NN + n, map, li, lk);
     }
 }
-#ifndef CW_NN2
-#define CW_NN2 2          // N-tiles per wavefront in layers 2 and 4 (the filter tiling follows: buf_cost_winograd_group)
-#endif
-#ifndef CW_NN4
-#define CW_NN4 2
-#endif
 #define CW_CS1 272        // channel strides of the maps after layers 1, 2 (= 16 mod 64: the two tile rows of an M-tile leave the
 #define CW_CS2 208        //   banks 16..31 / 48..63 to the half-wave's second channel), 3 and 4 (= 32 mod 64)
 #define CW_CS3 160
 
-#if !CV_L1_DIRECT
 // six layer-0 rows n' = r0 .. r0+5 into the channel-major chunk: X[(k', o)][t * 18 + l'] = relu(Smap[k'][(l'-n') mod 20][o] + Tb[k'][l'][o])
 __device__ __forceinline__ void form_rows_cm(float* __restrict__ X, const float* __restrict__ SM, const float* __restrict__ TB, int r0)
 {
@@ -401,7 +340,6 @@ __device__ __forceinline__ void form_rows_cm(float* __restrict__ X, const float*
         for (int q = 0; q < 4; q++) d[q * CW_CSX] = fmaxf(sv[q] + tv[q], 0.f);
     }
 }
-#endif
 
 #ifdef CV_STAMP
 __device__ long long* cv_stamp_ptr;       // development build (-DCV_STAMP): s_memtime of wavefront 0 at the phase boundaries
@@ -468,66 +406,9 @@ __device__ __forceinline__ void cost_net_body(const float* __restrict__ s_eq, co
                 if (m < 54) TB[m * CV_C32 + u * 16 + li] = b0v[u] - accT[0][u][r];
             }
     }
-    __syncthreads();                         // SM/TB complete; SP/TP dead from here on (chunk buffer R0 takes their place)
+    __syncthreads();                         // SM/TB complete; SP/TP dead from here on (the chunk buffer XC takes their place)
     CV_STAMP_AT(1)
 
-#if CV_L1_DIRECT
-    // ---- phase A.2: layer 1 over chunks of three layer-0 rows; wave w owns N-tile w (16 of the 64 output channels) ----
-    // Row ra = 3j + t of chunk j feeds output row ra - dn through slab dn: accumulators acc5[ra - dn - (3j - 2)] hold the five
-    // live output rows 3j-2 .. 3j+2; rows 3j-2, 3j-1, 3j are complete after chunk j.  Tiles whose output row falls outside 0..15
-    // (chunk 0: t < dn, chunk 5: t > dn) are not computed.
-    {
-        const float b1v = P.bias[1][w * 16 + li];
-        const float* w1 = P.wt[1] + ((size_t)w * 64 + lane) * 4;          // N-tile w of 4; a dn slab = 18 groups
-        cvx4 acc5[5];
-        // the 16 output rows of this wavefront's N-tile wait in registers (64) until the last chunk has been read: the layer-1
-        // map then takes the place of the chunks
-        cvx4 done[16];
-#pragma unroll
-        for (int i = 0; i < 5; i++) acc5[i] = (cvx4){ 0.f, 0.f, 0.f, 0.f };
-        form_rows(bufB + CVA_R0, SM, TB, 0);
-        __syncthreads();
-#define CV_SLAB(DN, T0, T1)                                                                              \
-    {                                                                                                    \
-        constexpr int MT_ = (T1) - (T0);                                                                 \
-        L1Loader<MT_> L;                                                                                 \
-        L.base = Rc + (T0) * CVA_RROW + li * CV_C32 + lk * 4;                                            \
-        cvx4 a_[MT_][1];                                                                                 \
-        _Pragma("unroll") for (int t = 0; t < MT_; t++) a_[t][0] = acc5[(T0) + t - (DN) + 2];            \
-        cv_gemm_static<MT_, 1, 4, 18>(a_, L, w1 + (size_t)(DN) * 18 * 4 * 256, 4);                       \
-        _Pragma("unroll") for (int t = 0; t < MT_; t++) acc5[(T0) + t - (DN) + 2] = a_[t][0];            \
-    }
-        auto chunk = [&](auto jc) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value;
-            const float* Rc = bufB + ((j & 1) ? CVA_R1 : CVA_R0);
-            if (j < 5) form_rows(bufB + ((j & 1) ? CVA_R0 : CVA_R1), SM, TB, 3 * j + 3);     // next chunk, other buffer
-            if constexpr (j == 0)      { CV_SLAB(0, 0, 3) CV_SLAB(1, 1, 3) CV_SLAB(2, 2, 3) }
-            else if constexpr (j == 5) { CV_SLAB(0, 0, 1) CV_SLAB(1, 0, 2) CV_SLAB(2, 0, 3) }
-            else                       { CV_SLAB(0, 0, 3) CV_SLAB(1, 0, 3) CV_SLAB(2, 0, 3) }
-#pragma unroll
-            for (int i = 0; i < 3; i++) {                    // completed output rows 3j-2, 3j-1, 3j
-                constexpr int nb = 3 * j - 2;
-                if (nb + i >= 0 && nb + i < 16) {
-#pragma unroll
-                    for (int r = 0; r < 4; r++) done[(nb + i) & 15][r] = fmaxf(acc5[i][r] + b1v, 0.f);
-                }
-            }
-            acc5[0] = acc5[3]; acc5[1] = acc5[4];
-            acc5[2] = acc5[3] = acc5[4] = (cvx4){ 0.f, 0.f, 0.f, 0.f };
-            __syncthreads();                 // the chunk just read may be overwritten; the next one is complete
-        };
-        chunk(std::integral_constant<int, 0>{}); chunk(std::integral_constant<int, 1>{}); chunk(std::integral_constant<int, 2>{});
-        chunk(std::integral_constant<int, 3>{}); chunk(std::integral_constant<int, 4>{}); chunk(std::integral_constant<int, 5>{});
-#pragma unroll
-        for (int n2 = 0; n2 < 16; n2++)                      // channel-major for the Winograd layers: [64][CW_CS1], rows of 16
-            *reinterpret_cast<cvx4*>(bufA + (w * 16 + li) * CW_CS1 + n2 * 16 + lk * 4) = done[n2];
-        __syncthreads();
-    CV_STAMP_AT(2)
-#undef CV_SLAB
-    }
-
-#else
-#if CV_L1_PAIRS
     // ---- phase A.2: layer 1 in the Winograd domain.  Its 3 x 3 x 3 filter collapses k' (3 -> 1), so it is a 3 x 3 correlation over
     // (n', l') with the three k' planes as input channels (96): 8 x 8 tiles of 2 x 2 outputs.  The 124 KB layer-0 map never
     // exists: four chunks of six rows n' = 4j .. 4j+5 (two tile rows = one M-tile of 16 tiles) are formed channel-major one after
@@ -585,61 +466,15 @@ __device__ __forceinline__ void cost_net_body(const float* __restrict__ s_eq, co
         __syncthreads();
         CV_STAMP_AT(2)
     }
-#else
-    // ---- phase A.2: layer 1 in the Winograd domain.  Its 3 x 3 x 3 filter collapses k' (3 -> 1), so it is a 3 x 3 correlation over
-    // (n', l') with the three k' planes as input channels (96): 8 x 8 tiles of 2 x 2 outputs.  The 124 KB layer-0 map never
-    // exists: four chunks of six rows n' = 4j .. 4j+5 (two tile rows = one M-tile of 16 tiles) are formed channel-major one after
-    // the other; wave w owns N-tile w and holds its 4 x 16 output registers until the last chunk has been read.
-    // 64 tile rows x 16 components x 96 channels = 0.44 of the direct form's matrix instructions (3 456 -> 1 536 per wavefront).
-    {
-        int lane_ = threadIdx.x & (WAVE - 1);
-        asm volatile("" : "+v"(lane_));
-        const int li_ = lane_ & 15, lk_ = lane_ >> 4;
-        float* XC = bufB + CVA_XC;
-        constexpr unsigned KSTEP = 16u * CW_CSX;
-        const __amdgpu_buffer_rsrc_t rs = wg_weights(P.wt[1]);
-        const unsigned wp = (unsigned)w * (96 * 256);                      // [N-tile][i 0..3][k-step 0..23][lane][j]
-        const unsigned lofs = lane_ * 16;
-        unsigned RA[3][4];
-        {
-            const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)XC;
-#pragma unroll
-            for (int a = 0; a < 4; a++) RA[0][a] = RA[1][a] = RA[2][a] = base + 4u * (unsigned)(lk_ * CW_CSX + (2 * (li_ >> 3) + a) * CW_RSX + 2 * (li_ & 7));
-        }
-        wgf4 W[1][2];
-        wg_first_weights<1, 0, 2>(rs, wp, lofs, 256, W);
-        wgf4 Y1[4][1][3][2][2];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            form_rows_cm(XC, SM, TB, 4 * j);
-            __syncthreads();
-            wg_round<1, 0, 1, KSTEP, true>(RA, rs, wp, wp, lofs, 6, 256, 24u * 256u, P.bias[1] + w * 16 + lk_ * 4, W, Y1[j]);
-            __syncthreads();                 // the chunk may be overwritten
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) cw_store_tile<18, 2, 16, CW_CS1, false>(Y1[j][0][0], j, w, bufA, li_, lk_);
-        __syncthreads();
-        CV_STAMP_AT(2)
-    }
-#endif
-#endif
     // ---- phase B: layers 2..6 rewrite the buffer in place; the three tiny last layers hop through its free parts -----------
     //                                 in: size rows stride | tile rows per M-tile | Cin | N-tiles, M-tiles per wavefront | out
-#if CW_NN2 == 4
-    cw_layer<16, 16, CW_CS1, 2, 64, 4, 1, 0, 14, CW_CS2, false>(bufA, P.wt[2], P.bias[2], 0, w);                  // 16x16 -> 14x14, 64 ch: M-tile w, all N-tiles
-#else
     cw_layer<16, 16, CW_CS1, 2, 64, 2, 2, 0, 14, CW_CS2, false>(bufA, P.wt[2], P.bias[2], w & 1, 2 * (w >> 1));   // 16x16 -> 14x14, 64 ch
-#endif
     __syncthreads();
     CV_STAMP_AT(3)
     cw_layer<14, 14, CW_CS2, 2, 64, 2, 2, 1, 12, CW_CS3, false>(bufA, P.wt[3], P.bias[3], w, 0);                  // -> 12x12, 128 ch
     __syncthreads();
     CV_STAMP_AT(4)
-#if CW_NN4 == 4
-    cw_layer<12, 12, CW_CS3, 3, 128, 4, 1, 0, 12, CW_CS3, false>(bufA, P.wt[4], P.bias[4], w & 1, w >> 1);        // -> 10x10 (rows of 12): N-tile quad, one M-tile
-#else
     cw_layer<12, 12, CW_CS3, 3, 128, 2, 2, 0, 12, CW_CS3, false>(bufA, P.wt[4], P.bias[4], w, 0);                 // -> 10x10 (rows of 12)
-#endif
     __syncthreads();
     CV_STAMP_AT(5)
     cw_layer<10, 12, CW_CS3, 4, 128, 1, 1, 0, 0, CV_C64, true>(bufA, P.wt[5], P.bias[5], w, 0);                   // -> 8x8, position-major
@@ -685,10 +520,12 @@ __global__ void __launch_bounds__(CV_THREADS, 2) k_cost_net_rerun(const float* _
     cost_net_body(s_eq, t_eq, P, ind_out, lds);
 }
 
-// N-tiles per group in the Winograd filter tiling of layer l (2..5): what buf_winograd_tile_filters is to be called with
+// N-tiles per group in the Winograd filter tiling of layer l (1..5, the N-tiles a wavefront owns there; 0: not a Winograd layer): what
+// buf_winograd_tile_filters is to be called with
 extern "C" int buf_cost_winograd_group(int layer)
 {
-    return layer == 1 ? (CV_L1_DIRECT ? 0 : (CV_L1_PAIRS ? 2 : 1)) : layer == 2 ? CW_NN2 : layer == 3 ? 2 : layer == 4 ? CW_NN4 : layer == 5 ? 1 : 0;
+    static const int group[6] = { 0, 2, 2, 2, 2, 1 };
+    return layer >= 0 && layer <= 5 ? group[layer] : 0;
 }
 
 static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
@@ -713,7 +550,7 @@ static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const fl
     // 2 * sum(out positions * K * Cout), layers 1..5 with 16 products per 2 x 2 output tile (Winograd) = 0.0519 GFLOP.  The dense algorithmic count of SURVEY 8d is 0.160 GFLOP/match
     // (bench.py reports both; the roofline fraction is taken on the executed count).
     static const double macs_per_match =
-        60.0 * 480 * 32 + 54.0 * 288 * 32 + (CV_L1_DIRECT ? 256.0 * 864 * 64 : 16.0 * 64 * 96 * 64) +
+        60.0 * 480 * 32 + 54.0 * 288 * 32 + 16.0 * 64 * 96 * 64 +
         16.0 * (49.0 * 64 * 64 + 36.0 * 64 * 128 + 25.0 * 128 * 128 + 16.0 * 128 * 64) +        // layers 2..5: 16 components per 2 x 2 tile
         36.0 * 576 * 64 + 16.0 * 576 * 32 + 4.0 * 288 * 32 + 1.0 * 128 * 20;
     TimedSpan span;

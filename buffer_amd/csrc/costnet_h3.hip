@@ -21,9 +21,7 @@
 #define CH_THREADS 256
 #define CH_LDS 81920u
 #define CH_NW 11                       // weight matrices: layer 0 S-term, layer 0 T-term, layers 1..9
-#ifndef CH_PAD
 #define CH_PAD 32u                     // position strides 160 / 288 / 400 / 544 (as H3_S: 8 mod 64 words at 128 channels)
-#endif
 #define CH_S32 (128u + CH_PAD)         // position stride of a 32-channel image (= ch_stride(32))
 
 // region plan (bytes) -- phase A

@@ -90,9 +90,6 @@ __device__ __forceinline__ float max_tree_f32(const float (&v)[N])
 // Cross-wave stage of a round: with the LDS copy of the cloud, one ordered 64-bit key per wavefront and a depth-3 tree of maxima (11 k points:
 // 1.31 -> 1.18 us per round); WITHOUT the copy (13 600 < n <= 16 384: the winner's coordinates are a scalar load) the tree measured 1.85 us per
 // round against 1.52 for the compare-and-branch chain over (distance, tie key) pairs, which stays there (tools/bench_ops.py fps, n = 15 000).
-#ifndef FPS_KEY_REDUCE
-#define FPS_KEY_REDUCE(lds) (lds)
-#endif
 template <int THREADS, int PPT, bool LDSPTS>
 __global__ void __launch_bounds__(THREADS) k_fps(const float* __restrict__ xyz, FpsBatch B, int m, int* __restrict__ idx_out)
 {
@@ -154,16 +151,16 @@ __global__ void __launch_bounds__(THREADS) k_fps(const float* __restrict__ xyz, 
                 win = __ffsll((long long)__ballot(best == wmax && tk == v)) - 1;
             }
             if (lane == win) {
-                if (FPS_KEY_REDUCE(LDSPTS)) skey[buf][w] = ((unsigned long long)__float_as_uint(wmax) << 32) | (unsigned int)~tk;
+                if (LDSPTS) skey[buf][w] = ((unsigned long long)__float_as_uint(wmax) << 32) | (unsigned int)~tk;
                 else { sbest[buf][w] = wmax; stie[buf][w] = tk; }
             }
         } else if (lane == 0) {
-            if (FPS_KEY_REDUCE(LDSPTS)) skey[buf][w] = 0ull;
+            if (LDSPTS) skey[buf][w] = 0ull;
             else { sbest[buf][w] = -1.0f; stie[buf][w] = 0xffffffffu; }
         }
         __syncthreads();
         int old;
-        if (FPS_KEY_REDUCE(LDSPTS)) {
+        if (LDSPTS) {
             unsigned long long kk[NW];
 #pragma unroll
             for (int i = 0; i < NW; i++) kk[i] = skey[buf][i];

@@ -416,11 +416,9 @@ __global__ void __launch_bounds__(QW_WAVES * WAVE) k_grid_query_wave(const CellG
 // (d2, index)).  Cells whose 27-cell set exceeds CAPC candidates, and rows longer than CAP, go to the todo list.
 #define QC_WAVES 4
 #define QC_QPW 16                   // queries per wavefront
-#ifndef QC_CAPC
 // candidates of a 27-cell set the LDS stage holds (mean ~50; larger sets go to the lane-per-query pass): 160 and 192 measure the
 // same at 64 pairs per launch (28 vs 24 wavefronts per CU); 192 leaves fewer rows to that pass
 #define QC_CAPC 192
-#endif
 
 // N queries of ONE cell against its staged candidates, 64 candidates per step: N independent chains of distance test, ballot
 // compaction and bucket count per LDS read

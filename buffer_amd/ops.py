@@ -645,7 +645,7 @@ def mfma_tile_weights(wt, lk_major=False):
 def winograd_tile_weights(w, ng=None, blocks=4):
     """[Cout, Cin, 3, 3] -> the F(2x2, 3x3) filter transform U = G g G^T (fp64, rounded once to fp32) in the A-operand tiling
     of csrc/convnet_wg.hip: [N-group][i][k-step][n2][lk][li][j] = U[i][j][16 (NG g + n2) + li][4 ks + lk], N-groups of NG = 2
-    N-tiles for 64 / 128 output channels and 1 otherwise.  16 * Cout * Cin floats (buf_winograd_tile_weights is the same function
+    N-tiles (a wavefront owns an N-tile pair in every layer).  16 * Cout * Cin floats (buf_winograd_tile_weights is the same function
     on the C side).  ng / blocks: the general form (buf_winograd_tile_filters); blocks = 5 appends g[1] G^T = U_1 - U_2."""
     cout, cin = w.shape[0], w.shape[1]
     assert cin % 4 == 0 and cout % 16 == 0
@@ -846,7 +846,7 @@ class CostVolumeNet:
                 self.wt.append(torch.from_numpy(tiled).to(device))
                 self.bias.append(torch.from_numpy(np.ascontiguousarray(b)).to(device))
                 continue
-            if i == 1 and _lib.lib().buf_cost_winograd_group(1):
+            if i == 1:
                 # layer 1 collapses k' (3 -> 1): a 3 x 3 correlation over (n', l') with the three k' planes as input channels
                 assert tuple(w.shape) == (64, 32, 3, 3, 3), w.shape
                 w2d = np.ascontiguousarray(np.transpose(w, (0, 3, 1, 2, 4)).reshape(64, 96, 3, 3))     # [o][(dk, c)][dn][dl]

@@ -282,7 +282,7 @@ int     buf_patch_voxelize(const float* patches, const float* axis, int npatch, 
  * N-tiles per group (the N-tiles one wavefront owns: its k-steps are contiguous in memory), as buf_winograd_tile_weights lays
  * them out (fp64 on the host; output row 6, whose window ends in the elevation padding, runs in the direct form for its columns
  * 0..15 -- 6 matrix instructions on a full M-tile -- with the six taps formed in registers from U_0, U_1 and U_2).  Cin a multiple of 16 (of 32 for Cout 128), Cout in {32, 64, 128}, last layer 32. */
-int     buf_winograd_group(int cin, int cout);                                                   /* host only: NG of a layer */
+int     buf_winograd_group(int cin, int cout);                                                   /* host only: NG of a layer: 2 for every width */
 int     buf_winograd_tile_weights(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 16*Cout*Cin floats */
 int     buf_winograd_tile_filters(const float* w_host, int cout, int cin, int ng, int nblk, float* out_host);
                                                    /* host only: the same tiling with N-groups of ng and nblk = 4 | 5 blocks -> 4*nblk*Cout*Cin floats */
@@ -338,14 +338,14 @@ int     buf_descriptor_head(const float* y, int npatch, const float* params, flo
  * pointers, BN folded; layers 6..9: weights W[K][Cout] with K = ((dn*KH + dk)*KW + dl)*Cin + c, the last layer (20
  * outputs) zero-padded to 32 columns / biases.  Layers 1..5 run in the Winograd F(2x2,3x3) domain as 3x3 correlations over
  * (n, l): buf_winograd_tile_filters(w2d, Cout, Cin2d, ng, 4, out) with ng = buf_cost_winograd_group(layer) N-tiles per group
- * (16*Cout*Cin2d floats each; a layer whose group is 0 takes the [K][Cout] form), w2d = the (3,1,3) filters [Cout,Cin,3(dn),3(dl)]
+ * (16*Cout*Cin2d floats each), w2d = the (3,1,3) filters [Cout,Cin,3(dn),3(dl)]
  * for layers 2..5 and, for layer 1 (which collapses k: 3 -> 1), [64][dk*32 + c][dn][dl] = W1[o][c][dn][dk][dl], Cin2d = 96.  Layer 0 is linear in cost = S(shifted) - T and is passed SEPARATED
  * (exact up to fp32 re-association): wt_host[0] = Ws[480][32] followed by Wt[288][32],
  *   Ws[(dk*5 + e+2)*32 + c][o] = sum over dl-dn=e of W0[o][c][dn][dk][dl],  Wt[(dk*3 + dl)*32 + c][o] = sum over dn of W0
  * (buffer_amd.ops.separate_cost_layer0).  Every [K][Cout] matrix is stored in the MFMA B-operand tiling: blocks
  * [K/16][Cout/16] of 256 floats, block (g, n) laid out [lk 0..3][li 0..15][p 0..3] = W[16g + 4lk + p][16n + li]
  * (buffer_amd.ops.mfma_tile_weights(w, lk_major=True) is the host-side re-layout). */
-int     buf_cost_winograd_group(int layer);           /* host only: ng of layers 1..5 (0 for the others) */
+int     buf_cost_winograd_group(int layer);           /* host only: ng of layers 1..5 = 2, 2, 2, 2, 1 (0 for the others) */
 int     buf_cost_volume_net(const float* s_eq, const float* t_eq, int m, const float* const* wt_host,
                             const float* const* bias_host, float* ind_out, void* stream);
 /* The same with the row gather of models/BUFFER.py:285-292 (ss_equi = src_equi[s_mids], [:, :, 1:ele_n-1]) fused in:

@@ -321,7 +321,7 @@ def test_winograd_filter_tiling_reproduces_the_convolution():
     assert rc == 0 and np.array_equal(got, ops.winograd_tile_weights(w2))
     assert _lib.lib().buf_winograd_tile_weights(w2.ctypes.data_as(C.c_void_p), 30, 16, got.ctypes.data_as(C.c_void_p)) == -1
     # layers in the paired form (buf_winograd_group == 2): [pair][i][ks][n2][lk][li][j]
-    assert _lib.lib().buf_winograd_group(32, 128) == 2 and _lib.lib().buf_winograd_group(48, 64) == 2 and _lib.lib().buf_winograd_group(64, 32) in (1, 2)
+    assert _lib.lib().buf_winograd_group(32, 128) == 2 and _lib.lib().buf_winograd_group(48, 64) == 2 and _lib.lib().buf_winograd_group(64, 32) == 2
     w3 = np.ascontiguousarray(rng.standard_normal((128, 32, 3, 3)).astype(np.float32))
     t3 = ops.winograd_tile_weights(w3)
     U3 = np.transpose(t3.reshape(4, 4, 8, 2, 4, 16, 4), (1, 6, 0, 3, 5, 2, 4)).reshape(4, 4, 128, 32)
@@ -383,6 +383,44 @@ def test_cnn_entry_points_reject_unsupported_stacks_before_any_device_work():
     assert rc == -1
     rc = L.buf_cylindrical_net_split(x, 2, ptrs, ptrs, ints(48, 64, 64, 128, 128, 64, 64, 64), ok_out, relu, x, None, None)
     assert rc == -1 and b"width mismatch" in L.buf_last_error()
+
+
+def test_cost_winograd_groups_are_the_fixed_table():
+    """N-tiles per wavefront of the cost net's Winograd layers 1..5 (what the filter tiler is called with); 0 for every other layer"""
+    from buffer_amd import _lib
+    L = _lib.lib()
+    assert [L.buf_cost_winograd_group(l) for l in (1, 2, 3, 4, 5)] == [2, 2, 2, 2, 1]
+    assert [L.buf_cost_winograd_group(l) for l in (0, 6, 9)] == [0, 0, 0]
+
+
+def test_fp32_cnn_width_rules_are_the_same_at_both_entry_points():
+    """buf_cylindrical_net_wg_supports and buf_cylindrical_net_wg share one statement of the kernel's width rules: the released stack
+    passes, and each of seven 8-layer stacks that break ONE rule is refused by both with the same reason (no GPU needed: the launcher
+    validates before its first device call; dummy non-null pointers)."""
+    import ctypes as C
+    from buffer_amd import _lib
+    L = _lib.lib()
+    dummy = (C.c_float * 4)()
+    x = C.addressof(dummy)
+    ptrs = (C.c_void_p * 8)(*[x] * 8)
+    relu = (C.c_int * 8)(1, 1, 1, 1, 1, 1, 1, 0)
+    ints = lambda v: (C.c_int * 8)(*v)
+    assert L.buf_cylindrical_net_wg_supports(ints((48, 64, 64, 128, 128, 64, 64, 32)), ints((64, 64, 128, 128, 64, 64, 32, 32))) == 0
+    broken = [   # (cin, cout, the reason)
+        ((40, 64, 64, 128, 128, 64, 64, 32), (64, 64, 128, 128, 64, 64, 32, 32), b"unsupported widths"),      # Cin not a multiple of 16
+        ((48, 48, 64, 128, 128, 64, 64, 32), (48, 64, 128, 128, 64, 64, 32, 32), b"unsupported widths"),      # Cout = 48
+        ((48, 128, 64, 128, 128, 64, 64, 32), (128, 64, 128, 128, 64, 64, 32, 32), b"unsupported widths"),    # Cout = 128 with Cin = 48
+        ((48, 64, 64, 128, 128, 32, 32, 32), (64, 64, 128, 128, 32, 32, 32, 32), b"unsupported widths"),      # Cout = 32 with Cin = 128
+        ((48, 64, 128, 128, 128, 64, 64, 32), (64, 64, 128, 128, 64, 64, 32, 32), b"width mismatch"),         # Cin[2] != Cout[1]
+        ((48, 64, 32, 64, 128, 128, 64, 32), (64, 32, 64, 128, 128, 64, 32, 32), b"unsupported widths"),      # 64 outputs behind 32
+        ((48, 64, 64, 128, 128, 64, 64, 64), (64, 64, 128, 128, 64, 64, 64, 64), b"last layer"),              # last layer 64
+    ]
+    for cin, cout, reason in broken:
+        assert L.buf_cylindrical_net_wg_supports(ints(cin), ints(cout)) == -1, (cin, cout)
+        said = L.buf_last_error()
+        assert reason in said, (cin, cout, said)
+        assert L.buf_cylindrical_net_wg(x, 2, ptrs, ptrs, ints(cin), ints(cout), relu, x, None) == -1, (cin, cout)
+        assert L.buf_last_error() == said, (cin, cout, said, L.buf_last_error())
 
 
 def test_split_gemm_tiling_general_form():

@@ -65,7 +65,7 @@ for co, ci in ((32, 16), (64, 48), (128, 64), (128, 128)):
     w = np.ascontiguousarray(rng.standard_normal((co, ci, 3, 3)).astype(np.float32))
     out = np.full(16 * co * ci, np.nan, np.float32)
     assert L.buf_winograd_tile_weights(w.ctypes.data_as(C.c_void_p), co, ci, out.ctypes.data_as(C.c_void_p)) == 0
-    assert np.isfinite(out).all() and L.buf_winograd_group(ci, co) in ((2,) if co >= 64 else (1, 2))
+    assert np.isfinite(out).all() and L.buf_winograd_group(ci, co) == 2
 assert L.buf_winograd_tile_weights(None, 32, 16, None) == -1 and b'null' in L.buf_last_error()
 assert L.buf_winograd_tile_weights(w.ctypes.data_as(C.c_void_p), 30, 16, out.ctypes.data_as(C.c_void_p)) == -1
 # argument validation of device entry points: every call returns before the first HIP call
