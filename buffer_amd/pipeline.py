@@ -50,68 +50,30 @@ class BufferPipeline:
 
     @torch.no_grad()
     def register(self, inp, seed=0, perms=None, detail=False, metrics_gt=None, tau_kp=None, tau_match=None, dist_th=None):
-        """inp from upload() -> pose f32[4,4] (src -> tgt), device tensor.
+        """inp from upload() -> pose f32[4,4] (src -> tgt), device tensor: register_batch at one pair, the same launches.
         metrics_gt: the pair's ground-truth 4x4 (src -> tgt) -> (pose, counts int32[7] on the device), the pair's row of the
-        per-stage metrics (register_batch); with detail=True the row is out['stage_counts'] instead.  The pose is the same."""
-        cfg = self.cfg
+        per-stage metrics (register_batch).  The pose is the same.
+        detail=True -> (pose, dict): what the stages held for this pair (_pair_detail), the metric row under 'stage_counts'.  A pair
+        answered with the identity because a cloud has no keypoint leaves the dict empty otherwise; one with fewer than 3 mutual
+        matches leaves it without the hypothesis keys."""
         met = None if metrics_gt is None else self._metric_args([metrics_gt], tau_kp, tau_match, dist_th)
-        if self.limits is None:
-            raise RuntimeError('neighbourhood limits not calibrated: call calibrate() or pass limits=')
-        pyr = pyramid.build_pyramid(inp['points'], inp['lengths'], self.limits, cfg)
-        n_src = int(inp['lengths'][0])
-        axis, eps, bottle, skips, _ = self.point.efcnn(pyr, inp['features'])
-        score = self.point.detnet(pyr, bottle, skips)
-        pts0 = pyr['points'][0]
-        out = {}
-        cand_p, cand_a = [], []
-        for lo, hi in ((0, n_src), (n_src, pts0.shape[0])):
-            p = pts0[lo:hi]
-            a = orient_axes(axis[lo:hi], p)
-            keep = ops.compact_greater(score[lo:hi, 0], cfg.keypts_th).long()       # BUFFER.py:255-259
-            if keep.shape[0] == 0:
-                return self._identity(out, detail, met)
-            cand_p.append(p[keep]); cand_a.append(a[keep])
-        # both fragments sampled in one launch, one workgroup per cloud (BUFFER.py:266-271)
-        fps = ops.furthest_point_sample_ragged(torch.cat(cand_p), [c.shape[0] for c in cand_p], cfg.num_keypts).long()
-        kp = [cand_p[i][fps[i]].contiguous() for i in range(2)]
-        ka = [cand_a[i][fps[i]].contiguous() for i in range(2)]
-        raws = (inp['src_raw'], inp['tgt_raw'])
-        if perms is not None:                               # caller-pinned permutations (parity tests)
-            sup = torch.cat([raws[i][perms[i]] for i in range(2)]).contiguous()
-            sup_len = [raws[0].shape[0], raws[1].shape[0]]
-        else:                                               # keyed device permutation, the same one register_batch uses
-            sup, sup_len = ops.permute_clouds(raws, [ops.perm_key(seed, j) for j in range(2)])
-        P = cfg.num_keypts
-        patches = ops.select_patches_batched(sup, sup_len, torch.cat(kp), P, cfg.des_r, cfg.num_points_per_patch)
-        emb = self.desc.embed_patches(patches, torch.cat(ka), want_patches=detail)
-        res = [{k: (v[i * P:(i + 1) * P] if v is not None else None) for k, v in emb.items()} for i in range(2)]
-        s_mids, t_mids = registration.mutual_matching(res[0]['desc'], res[1]['desc'])
-        if s_mids.shape[0] < 3:
-            return self._identity(out, detail, met)
-        ss_kpts, tt_kpts = kp[0][s_mids].contiguous(), kp[1][t_mids].contiguous()
-        e = cfg.ele_n
-        ind = self.inlier(res[0]['equi'][s_mids][:, :, 1:e - 1].contiguous(),
-                          res[1]['equi'][t_mids][:, :, 1:e - 1].contiguous())
-        pose, diag = registration.recover_pose(ind, ss_kpts, tt_kpts, res[0]['R'][s_mids].contiguous(),
-                                               res[1]['R'][t_mids].contiguous(), cfg, seed)
+        st, res = self._stages([inp], [seed], None if perms is None else [perms], met, detail)
         self.check_range()
-        if met is not None:                                 # the batched kernel at B = 1 from this pair's own state (two more 1-NN
-            _, s_idx = ops.knn(res[1]['desc'][None], res[0]['desc'][None], 1)      # launches: mutual_matching keeps no full rows)
-            _, t_idx = ops.knn(res[0]['desc'][None], res[1]['desc'][None], 1)
-            out['stage_counts'] = ops.match_metrics(torch.cat(kp), s_idx[:, :, 0], t_idx[:, :, 0], met['gt'], pose[None], met['tau_kp'],
-                                                    met['tau_match'], met['dist_th'])[0]
-        if detail:
-            out.update(dict(pyr=pyr, axis=axis, eps=eps, score=score, kpts=kp, kaxis=ka, desc=res, s_mids=s_mids,
-                            t_mids=t_mids, ind=ind, **diag))
-            return pose, out
-        return pose if met is None else (pose, out['stage_counts'])
+        (pose,), counts = (res, None) if met is None else res
+        if not detail:
+            return pose if met is None else (pose, counts[0])
+        out = self._pair_detail(st)
+        if met is not None:
+            out['stage_counts'] = counts[0]
+        return pose, out
 
     @torch.no_grad()
     def register_batch(self, inps, seeds=None, perms=None, metrics_gt=None, tau_kp=None, tau_match=None, dist_th=None):
         """Several pairs through ONE set of launches per stage (the MI355X-native form: the pyramid, the VN
         blocks, FPS (one workgroup per cloud), patch selection, voxelisation, both CNNs and the 1-NN search all take the
         stacked batch; only the per-pair pose recovery loops).  inps: list of upload() dicts ->
-        list of pose f32[4,4] device tensors.  Per pair the arithmetic is that of register().
+        list of pose f32[4,4] device tensors.  A pair's result does not depend on what it is stacked with (register() is this
+        path at one pair; tests/pair_chain.py is the independent pair-by-pair chain the tests hold both against).
 
         metrics_gt: the B ground-truth poses (src -> tgt, [B,4,4] or a list of 4x4; host or device) switches the per-stage
         metrics on -> (poses, counts), counts int32[B,7] ON THE DEVICE (columns ops.METRIC_COLUMNS: rep_src, rep_tgt, nn_inl,
@@ -123,10 +85,7 @@ class BufferPipeline:
         tau_kp (repeatability distance) and tau_match (match inlier distance) default to cfg.dist_th, the inlier distance of the
         configuration's data set; dist_th (consensus distance of the returned pose) is cfg.dist_th unless overridden."""
         met = None if metrics_gt is None else self._metric_args(metrics_gt, tau_kp, tau_match, dist_th, len(inps))
-        st = self._keypoints(inps, seeds, perms)
-        if met is not None:
-            st['metrics'] = met
-        res = self._describe_and_match(st)
+        _, res = self._stages(inps, seeds, perms, met)
         self.check_range()
         return res
 
@@ -182,8 +141,17 @@ class BufferPipeline:
         self.check_range()
         return out
 
-    def _keypoints(self, inps, seeds, perms):
-        """pyramid -> point learner -> threshold -> FPS for a stacked batch -> state for _describe_and_match."""
+    def _stages(self, inps, seeds, perms, met=None, detail=False):
+        """the three stages of a stacked batch back to back -> (their state, what _match returns)"""
+        st = self._keypoints(inps, seeds, perms, detail)
+        if met is not None:
+            st['metrics'] = met
+        return st, self._match(self._describe(st))
+
+    def _keypoints(self, inps, seeds, perms, detail=False):
+        """pyramid -> point learner -> threshold -> FPS for a stacked batch -> state for _describe.
+        detail: the stages also leave what register(detail=True) reports under st['detail'] (references only: no launch is added or
+        moved)."""
         cfg, dev = self.cfg, self.device
         B = len(inps)
         if self.limits is None:
@@ -217,32 +185,29 @@ class BufferPipeline:
         gidx = (fps + off[:, None]).reshape(-1)
         st['kp'], st['ka'] = cand_p[gidx].contiguous(), cand_a[gidx].contiguous()           # [2B*P, 3]
         st['cross'] = (st['kp'], st['ka'])
+        if detail:
+            st['detail'] = dict(pyr=pyr, axis=axis, eps=eps, score=score)
         return st
-
-    def _describe_and_match(self, st):
-        """patches -> descriptors -> mutual matches -> cost volume -> per-pair pose recovery."""
-        return self._match(self._describe(st))
 
     def _describe(self, st):
         """patch selection, voxelisation, descriptor CNN and the two 1-NN searches of a stacked batch: everything up to
         the first host round trip of the stage (the match count), enqueued without blocking."""
         cfg, dev = self.cfg, self.device
         inps, seeds, perms, B = st['inps'], st['seeds'], st['perms'], st['B']
-        poses = [None] * B
-        if 'starved' in st:
-            bad = st['starved']
+        if 'starved' in st:                                 # the healthy pairs as a batch of their own, the identity for the others
+            good = [b for b in range(B) if b not in st['starved']]
             met = st.get('metrics')
-            rows = [None] * B
-            for b in (b for b in range(B) if b not in bad):        # redo the healthy pairs one by one
-                pb = perms[b] if perms is not None else None
-                if met is None:
-                    poses[b] = self.register(inps[b], seed=seeds[b], perms=pb)
-                else:
-                    poses[b], rows[b] = self.register(inps[b], seed=seeds[b], perms=pb, metrics_gt=met['gt'][b], tau_kp=met['tau_kp'],
-                                                      tau_match=met['tau_match'], dist_th=met['dist_th'])
-            st['poses'] = [p if p is not None else torch.eye(4, device=dev) for p in poses]
-            if met is not None:
-                st['poses'] = (st['poses'], torch.stack([r if r is not None else self._no_counts() for r in rows]))
+            poses = [torch.eye(4, device=dev) for _ in range(B)]       # ThreeDMatch/test.py:242-245: failed pair -> identity
+            counts = None if met is None else torch.full((B, len(ops.METRIC_COLUMNS)), -1, dtype=torch.int32, device=dev)  # not evaluated
+            if good:
+                res = self._stages([inps[b] for b in good], [seeds[b] for b in good], None if perms is None else [perms[b] for b in good],
+                                   None if met is None else dict(met, gt=met['gt'][good]))[1]
+                sub, rows = (res, None) if met is None else res
+                for b, p in zip(good, sub):
+                    poses[b] = p
+                if met is not None:
+                    counts[good] = rows
+            st['poses'] = poses if met is None else (poses, counts)
             return st
         kp, ka = st['kp'], st['ka']
         P = cfg.num_keypts
@@ -253,7 +218,7 @@ class BufferPipeline:
         else:                                               # one launch shuffles every cloud of the step (keyed per pair seed)
             sup, sup_len = ops.permute_clouds(raws, [ops.perm_key(seeds[b], j) for b in range(B) for j in range(2)])
         patches = ops.select_patches_batched(sup, sup_len, kp, P, cfg.des_r, cfg.num_points_per_patch)   # one grid, one launch
-        emb = self.desc.embed_patches(patches, ka)
+        emb = self.desc.embed_patches(patches, ka, want_patches='detail' in st)
         desc = emb['desc'].view(B, 2, P, -1)
         _, s_idx = ops.knn(desc[:, 1].contiguous(), desc[:, 0].contiguous(), 1)            # BUFFER.py:347: ref = tgt
         _, t_idx = ops.knn(desc[:, 0].contiguous(), desc[:, 1].contiguous(), 1)
@@ -263,7 +228,8 @@ class BufferPipeline:
         return st
 
     def _match(self, st):
-        """mutual matches (first host round trip) -> cost volume -> per-pair pose recovery."""
+        """mutual matches (first host round trip) -> cost volume -> pose recovery of all pairs in one set of launches
+        (-> per-stage metric rows) -> list of B poses, or (poses, counts int32[B,7]) with metrics."""
         if 'poses' in st:
             return st['poses']
         cfg, dev = self.cfg, self.device
@@ -281,9 +247,11 @@ class BufferPipeline:
         ss_all, tt_all = kp[src_row].contiguous(), kp[tgt_row].contiguous()
         sR_all, tR_all = emb['R'][src_row].contiguous(), emb['R'][tgt_row].contiguous()
         # hypotheses, all-vs-all scoring, RANSAC and refinement of all B pairs: one set of launches (csrc/registration.hip,
-        # batched section), bit-identical to the pair-by-pair recover_pose of register()
+        # batched section), bit-identical to the chain of single-pair calls (tests/pair_chain.py)
         all_poses = ops.recover_poses_batched(ind, ss_all, tt_all, sR_all, tR_all, m_counts, seeds, cfg)
         poses = [all_poses[b] for b in range(B)]
+        if 'detail' in st:
+            st['detail'].update(s_mids=s_mid, t_mids=t_mid, ind=ind, rows=(ss_all, tt_all, sR_all, tR_all))
         met = st.get('metrics')
         if met is None:
             return poses
@@ -305,14 +273,20 @@ class BufferPipeline:
         return dict(gt=gt.contiguous(), tau_kp=d if tau_kp is None else float(tau_kp), tau_match=d if tau_match is None else float(tau_match),
                     dist_th=d if dist_th is None else float(dist_th))
 
-    def _no_counts(self):
-        """the count row of a pair that was not evaluated"""
-        return torch.full((len(ops.METRIC_COLUMNS),), -1, dtype=torch.int32, device=self.device)
-
-    def _identity(self, out, detail, met=None):
-        pose = torch.eye(4, device=self.device)       # ThreeDMatch/test.py:242-245: failed pair -> identity
-        if met is not None:
-            out['stage_counts'] = self._no_counts()
-        if detail:
-            return pose, out
-        return pose if met is None else (pose, out['stage_counts'])
+    def _pair_detail(self, st):
+        """register(detail=True): the state the stages left for a batch of ONE pair, in the per-cloud layout the parity tests and
+        bench.py read.  pyr, axis, eps, score: the stacked pair; kpts, kaxis: two [P,3]; desc: two dicts of [P,...] slices of
+        embed_patches (desc, equi, R, rand_axis, x, patches); s_mids, t_mids (int64, ascending s_mids), ind; inlier_num, best,
+        inlier_mask, R_hyp, t_hyp from one hypotheses_score call on the pair's matched rows, the only launches detail adds (the
+        batched recovery keeps these in its workspace; tests/test_pose_recovery_gpu.py pins the two equal)."""
+        if 'detail' not in st:                              # a cloud without a keypoint: no stage was reached
+            return {}
+        cfg, P = self.cfg, self.cfg.num_keypts
+        out = st['detail']
+        out['kpts'], out['kaxis'] = ([st[k][i * P:(i + 1) * P] for i in range(2)] for k in ('kp', 'ka'))
+        out['desc'] = [{k: (v[i * P:(i + 1) * P] if v is not None else None) for k, v in st['emb'].items()} for i in range(2)]
+        rows = out.pop('rows')
+        if out['ind'].shape[0] >= 3:
+            R, t, num, best, mask = ops.hypotheses_score(out['ind'], *rows, cfg.azi_n, cfg.inlier_th)
+            out.update(inlier_num=num, best=best, inlier_mask=mask, R_hyp=R, t_hyp=t)
+        return out

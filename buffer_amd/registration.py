@@ -1,20 +1,9 @@
-"""A12-A16 -- matching and pose recovery on device (models/BUFFER.py:283-333,335-359,382-464)."""
+"""The cost volume network on device (models/BUFFER.py:37-66,291-293).  Mutual matching and pose recovery (A12, A14-A16) are the
+_describe / _match stages of pipeline.py over ops.knn and ops.recover_poses_batched."""
 import numpy as np
-import torch
 
 from . import ops
 from .patch_embedder import _fold_bn
-
-
-def mutual_matching(src_des, tgt_des):
-    """buffer.mutual_matching (BUFFER.py:335-359): 1-NN both ways (csrc/pointops.hip k_knn), mutual check.
-    -> (s_mids, t_mids) int64 device tensors (ascending s_mids, as np.where yields them)."""
-    _, s_idx = ops.knn(tgt_des[None], src_des[None], 1)
-    _, t_idx = ops.knn(src_des[None], tgt_des[None], 1)
-    s_nn, t_nn = s_idx[0, :, 0], t_idx[0, :, 0]
-    ar = torch.arange(s_nn.shape[0], device=s_nn.device)
-    s_mids = torch.nonzero(t_nn[s_nn] == ar).flatten()
-    return s_mids, s_nn[s_mids]
 
 
 class CostVolume:
@@ -45,15 +34,3 @@ class CostVolume:
     def gathered(self, equi, s_rows, t_rows):
         """full maps equi f32[rows,32,7,20] + matched row ids -> expected azimuth shift f32[M] (gather and elevation slice fused)."""
         return self.fused.gathered(equi, s_rows, t_rows)
-
-
-def recover_pose(ind, ss_kpts, tt_kpts, ss_R, tt_R, cfg, seed=0):
-    """BUFFER.py:295-333: hypotheses, all-vs-all scoring, RANSAC on the winner's inliers, refinement.
-    -> (pose f32[4,4] device, dict of diagnostics)."""
-    R, t, num, best, mask = ops.hypotheses_score(ind, ss_kpts, tt_kpts, ss_R, tt_R, cfg.azi_n, cfg.inlier_th)
-    # the winner's inlier list stays on the device (mask -> index list inside the RANSAC entry point): the whole
-    # recovery is enqueued without a host round trip
-    T, info = ops.ransac_kabsch_masked(ss_kpts, tt_kpts, mask, cfg.ransac_hypotheses, seed, cfg.dist_th, cfg.similar_th)
-    if cfg.pose_refine:
-        T, rinfo = ops.post_refine(T, ss_kpts, tt_kpts, cfg.refine_threshold, 20)
-    return T, dict(inlier_num=num, best=best, inlier_mask=mask, ransac_info=info, R_hyp=R, t_hyp=t)

@@ -255,9 +255,10 @@ def test_matching_and_pose_vs_reference(W, dev):
     """mutual 1-NN, cost volume, hypotheses, scoring, refinement -> fixture F5 (40 matches: below every loop stride of registration.hip;
     tests/test_pose_recovery_gpu.py takes the pose kernels past them, against float64)."""
     from buffer_amd import ops, registration
+    from pair_chain import mutual_matching
     f = load("match_tiny.npz")
     t = lambda a: torch.from_numpy(a).to(dev)
-    s_mids, t_mids = registration.mutual_matching(t(f['src_desc']), t(f['tgt_desc']))
+    s_mids, t_mids = mutual_matching(t(f['src_desc']), t(f['tgt_desc']))
     assert np.array_equal(s_mids.cpu().numpy(), f['s_mids']) and np.array_equal(t_mids.cpu().numpy(), f['t_mids'])
     cv = registration.CostVolume(W, dev)
     se, te = t(f['src_equi'])[s_mids][:, :, 1:6].contiguous(), t(f['tgt_equi'])[t_mids][:, :, 1:6].contiguous()

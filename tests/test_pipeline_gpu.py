@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import pair_chain
 from buffer_amd import synth
 from util import assert_neighbors_equal_mod_ties as nbr_eq
 
@@ -63,7 +64,8 @@ def test_register_3dmatch_shape_pair(dev):
 
 
 def test_batched_registration_equals_single(tiny, dev):
-    """register_batch (stacked launches) reproduces register() pair by pair."""
+    """register_batch (stacked launches) and register() (the same path at one pair) reproduce the independent pair-by-pair chain of
+    tests/pair_chain.py."""
     from buffer_amd.pipeline import BufferPipeline
     from dataclasses import replace
     from buffer_amd.config import THREEDMATCH
@@ -71,15 +73,49 @@ def test_batched_registration_equals_single(tiny, dev):
     pipe = BufferPipeline(replace(THREEDMATCH, num_keypts=300), dev)
     pipe.calibrate([tiny])
     inps = [pipe.upload(tiny), pipe.upload(other), pipe.upload(tiny)]
+    chain = [pair_chain.register(pipe, x, seed=i) for i, x in enumerate(inps)]
     single = [pipe.register(x, seed=i) for i, x in enumerate(inps)]
     batch = pipe.register_batch(inps, seeds=[0, 1, 2])
-    for a, b in zip(single, batch):
-        assert torch.equal(a, b)            # same arithmetic per pair, whatever the stacking (was atol 2e-4 in round 1)
+    for want, a, b in zip(chain, single, batch):
+        assert torch.equal(a, want) and torch.equal(b, want)    # same arithmetic per pair, whatever the stacking (was atol 2e-4 in round 1)
+
+
+@pytest.mark.parametrize('pinned', [False, True], ids=['keyed', 'pinned'])
+def test_register_is_the_batch_path_at_one_pair(tiny, dev, pinned):
+    """register() is register_batch at B = 1, and its detail dictionary is that path's own state: the shapes bench.py and the parity
+    tests read, the gather form's ind equal to the dense cost net on the gathered and sliced maps, the hypothesis scores of the one
+    extra hypotheses_score call consistent among themselves."""
+    from buffer_amd.pipeline import BufferPipeline
+    from dataclasses import replace
+    from buffer_amd.config import THREEDMATCH
+    pipe = BufferPipeline(replace(THREEDMATCH, num_keypts=300), dev)
+    pipe.calibrate([tiny])
+    inp = pipe.upload(tiny)
+    seed, perms = 5, None
+    if pinned:
+        rng = np.random.default_rng(7)
+        perms = [torch.from_numpy(rng.permutation(len(tiny[k]))).to(dev) for k in ('src_fds_pts', 'tgt_fds_pts')]
+    want = pipe.register_batch([inp], seeds=[seed], perms=None if perms is None else [perms])[0]
+    pose, d = pipe.register(inp, seed=seed, perms=perms, detail=True)
+    assert torch.equal(pose, want)
+    for i in range(2):
+        assert tuple(d['kpts'][i].shape) == (300, 3) and tuple(d['kaxis'][i].shape) == (300, 3)
+        assert tuple(d['desc'][i]['patches'].shape) == (300, 512, 3)
+        assert set(d['desc'][i]) == {'desc', 'equi', 'R', 'rand_axis', 'x', 'patches'}
+    s_mids, t_mids = d['s_mids'], d['t_mids']
+    assert s_mids.dtype == t_mids.dtype == torch.int64 and s_mids.shape[0] >= 3 and bool((s_mids[1:] > s_mids[:-1]).all())
+    dense = pipe.inlier(d['desc'][0]['equi'][s_mids][:, :, 1:6].contiguous(), d['desc'][1]['equi'][t_mids][:, :, 1:6].contiguous())
+    assert torch.equal(d['ind'], dense)
+    assert int(d['inlier_mask'].sum()) == int(d['inlier_num'][int(d['best'])])
+    assert 'ransac_info' not in d and 'stage_counts' not in d
+    again = pipe.register(inp, seed=seed, perms=perms)
+    assert isinstance(again, torch.Tensor) and torch.equal(again, pose)
 
 
 def test_batch_with_a_keypoint_free_pair_keeps_pinned_permutations(tiny, dev):
     """register_batch's rare path (a cloud without any score above the threshold -> identity for that pair, the others
-    redone one by one) must hand the caller's permutations on, so that the healthy pairs equal register() exactly."""
+    redone as a batch of their own) must hand the caller's permutations on, so that the healthy pairs equal the pair-by-pair chain
+    (tests/pair_chain.py) and register() exactly."""
     from buffer_amd.pipeline import BufferPipeline
     from dataclasses import replace
     from buffer_amd.config import THREEDMATCH
@@ -105,8 +141,9 @@ def test_batch_with_a_keypoint_free_pair_keeps_pinned_permutations(tiny, dev):
     batch = pipe.register_batch(inps, seeds=[3, 4], perms=perms)
     assert torch.equal(batch[starved], torch.eye(4, device=dev))
     healthy = 1 - starved
-    want = pipe.register(inps[healthy], seed=[3, 4][healthy], perms=perms[healthy])
+    want = pair_chain.register(pipe, inps[healthy], seed=[3, 4][healthy], perms=perms[healthy])
     assert torch.equal(batch[healthy], want)
+    assert torch.equal(pipe.register(inps[healthy], seed=[3, 4][healthy], perms=perms[healthy]), want)
 
 
 def test_pipelined_batches_equal_batch_by_batch(tiny, dev):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import pair_chain
 import pose_ref
 from util import assert_close
 
@@ -381,14 +382,8 @@ def _cfgs():
 
 
 def _chain(dev, p, cfg, seed):
-    """registration.recover_pose's chain of single-pair calls"""
-    from buffer_amd import ops
-    ind, ss, tt, ssR, ttR = (_t(a, dev) for a in p)
-    R, t, num, best, mask = ops.hypotheses_score(ind, ss, tt, ssR, ttR, cfg.azi_n, cfg.inlier_th)
-    T, info = ops.ransac_kabsch_masked(ss, tt, mask, cfg.ransac_hypotheses, seed, cfg.dist_th, cfg.similar_th)
-    if cfg.pose_refine:
-        T, _ = ops.post_refine(T, ss, tt, cfg.refine_threshold, 20)
-    return T
+    """the chain of single-pair calls (tests/pair_chain.py)"""
+    return pair_chain.recover_pose(*(_t(a, dev) for a in p), cfg, seed)
 
 
 def _batched(dev, pairs, cfg, seeds):
