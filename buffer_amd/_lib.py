@@ -89,6 +89,7 @@ _SIGNATURES = {
     "buf_split_filter_count": (C.c_longlong, [_i, _i]),
     "buf_split_tile_filters": (_i, [_vp, _i, _i, _vp]),
     "buf_winograd_tile_weights": (_i, [_vp, _i, _i, _vp]),
+    "buf_winograd_f24_tile_weights": (_i, [_vp, _i, _i, _vp]),
     "buf_winograd_group": (_i, [_i, _i]),
     "buf_cost_winograd_group": (_i, [_i]),
     "buf_winograd_tile_filters": (_i, [_vp, _i, _i, _i, _i, _vp]),

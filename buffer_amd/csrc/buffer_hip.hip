@@ -22,5 +22,6 @@
 // main stream: 40-65 % of its launches differed in 16 lanes; with packed ops off: 0 of 1200; beside the fp32-MFMA kernels: 0).  The
 // two fp32-MFMA CNN kernels, whose Winograd transforms the compiler had built on v_pk_add_f32, measured 0.9 % FASTER without them.
 #include "convnet_wg.hip"
+#include "convnet_w24.hip"
 #include "costnet.hip"
 #include "split_safe.hip"

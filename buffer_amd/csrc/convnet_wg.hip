@@ -651,15 +651,9 @@ __device__ __forceinline__ void wg_layer_pair(float* __restrict__ act, const flo
     }
 }
 
-__device__ __forceinline__ void cyl_net_wg_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
+// The patch's input into the activation buffer, the zero words of every channel, and the barrier behind them
+__device__ __forceinline__ void wg_load_input(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ act, int patch)
 {
-    float* act = lds;                                // [128][160]
-    const int patch = blockIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    WG_STAMP_AT(17)
-#ifdef WG_STAMP
-    if (threadIdx.x == 0) { P.stamps[(size_t)gridDim.x * 80 + blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime(); P.stamps[(size_t)gridDim.x * 80 + blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime(); }
-#endif
     {   // input [48][140] -> rows of 22 with the halo columns.  A row is five float4: every load of the patch is issued before the
         // first LDS store (one load at a time, each behind the previous one's stores, took 40 k cycles per patch: 5 % of the kernel)
         const wgf4* src = reinterpret_cast<const wgf4*>(x + (size_t)patch * P.cin[0] * 140);
@@ -687,6 +681,18 @@ __device__ __forceinline__ void cyl_net_wg_body(const float* __restrict__ x, con
     }
     for (int i = threadIdx.x; i < WG_MAXC * 4; i += WG_THREADS) act[(i >> 2) * WG_CS + WG_ZERO + (i & 3)] = 0.f;
     __syncthreads();
+}
+
+__device__ __forceinline__ void cyl_net_wg_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
+{
+    float* act = lds;                                // [128][160]
+    const int patch = blockIdx.x;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    WG_STAMP_AT(17)
+#ifdef WG_STAMP
+    if (threadIdx.x == 0) { P.stamps[(size_t)gridDim.x * 80 + blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime(); P.stamps[(size_t)gridDim.x * 80 + blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime(); }
+#endif
+    wg_load_input(x, P, act, patch);
     WG_STAMP_AT(0)
     WgAddrPark pk;
     {
@@ -795,6 +801,12 @@ extern "C" int buf_cylindrical_net_wg_supports(const int* cin_host, const int* c
     return wg_check_widths(cin_host, cout_host);
 }
 
+// relu_host[l] bit 1 (WG_F24_FLAG): the layer's filter buffer holds the F(2x4) set behind the F(2x2) set and the stack runs in
+// k_cyl_net_w24 (csrc/convnet_w24.hip), which launches it: w24_launch.  Callers that pass 0 / 1 never reach it.
+#define WG_F24_FLAG BUF_CYL_F24
+static inline bool wg_f24_flagged(int relu) { return relu == WG_F24_FLAG || relu == (WG_F24_FLAG | 1); }
+static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
+
 // x f32[np,48,140] -> y f32[np,32,140]; weights in the Winograd-domain tiling (see CylWgParams).
 static int wg_launch(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
                      const int* cout_host, const int* relu_host, float* y, const int* only_if, void* stream)
@@ -810,6 +822,8 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
     }
     if (int rc = wg_check_widths(P.cin, P.cout)) return rc;
     P.only_if = only_if;
+    for (int l = 0; l < WG_LAYERS; l++)
+        if (wg_f24_flagged(relu_host[l])) return w24_launch(x, npatch, P, y, stream);
     size_t lds = sizeof(float) * WG_BUF;
     static LdsGrant grant, grant_rerun;
     if (int rc = only_if ? grant_dynamic_lds((const void*)k_cyl_net_wg_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_wg, lds, grant)) return rc;

@@ -14,7 +14,7 @@
 
 // x f32[np,Cin0,140] -> without head: y_or_equi = y f32[np,32,140]; with head_params (DEVICE f32[545], buf_descriptor_head):
 // desc f32[np,32] and y_or_equi = equi f32[np,32,140].  wt_split_host / wt_wg_host: the filters in the two kernels' tilings
-// (buf_split_tile_filters / buf_winograd_tile_weights), bias_host shared.  flags_ws: DEVICE int32[np] (scratch; after the call
+// (buf_split_tile_filters / buf_winograd_tile_weights; relu_host may carry the fp32 kernel's F(2x4) flag), bias_host shared.  flags_ws: DEVICE int32[np] (scratch; after the call
 // flags_ws[p] != 0 marks the patches that took the fp32 kernel).
 extern "C" int buf_cylindrical_net_split_safe(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                               const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
@@ -29,7 +29,9 @@ extern "C" int buf_cylindrical_net_split_safe(const float* x, int npatch, const 
     if (int rc = buf_cylindrical_net_wg_supports(cin_host, cout_host)) return rc;       // the re-run must exist for these widths
     hipStream_t s = (hipStream_t)stream;
     BUF_CHECK_HIP(hipMemsetAsync(flags_ws, 0, sizeof(int) * (size_t)npatch, s));
-    int rc = h3_launch(x, npatch, wt_split_host, bias_host, cin_host, cout_host, relu_host, head_params ? nullptr : y_or_equi, head_params,
+    int relu_split[WG_LAYERS];                        // the split kernel knows 0 / 1 only: without the fp32 kernel's F(2x4) flag
+    for (int l = 0; l < WG_LAYERS; l++) relu_split[l] = wg_f24_flagged(relu_host[l]) ? (relu_host[l] & 1) : relu_host[l];
+    int rc = h3_launch(x, npatch, wt_split_host, bias_host, cin_host, cout_host, relu_split, head_params ? nullptr : y_or_equi, head_params,
                        desc, head_params ? y_or_equi : nullptr, status_dev, stream, flags_ws);
     if (rc) return rc;
     rc = wg_launch(x, npatch, wt_wg_host, bias_host, cin_host, cout_host, relu_host, y_or_equi, flags_ws, stream);

@@ -658,16 +658,65 @@ def winograd_tile_weights(w, ng=None, blocks=4):
     return np.ascontiguousarray(np.transpose(U, (2, 0, 5, 3, 6, 4, 1)), dtype=np.float32).reshape(-1)
 
 
-class CylindricalNet:
-    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip: per layer U = G g G^T in the kernel's tiling, biases."""
+def winograd_f24_tile_weights(w):
+    """[Cout, Cin, 3, 3] -> the F(2x4, 3x3) filter transform U = G2 g G4^T (fp64, rounded once to fp32; points 0, +-1, +-2, infinity
+    along the azimuth) in the tiling of csrc/convnet_w24.hip: [pair][i][k-step][768] with, per (row component i, k-step), the column
+    components j = 0, 1, 2, 5 of both N-tiles as [n2][lk][li][4] and then j = 3, 4 as [n2][lk][li][2]; value
+    U[i][j][16 (2 pair + n2) + li][4 ks + lk].  24 * Cout * Cin floats, bit for bit what buf_winograd_f24_tile_weights writes (the
+    nine products are summed in its order)."""
+    cout, cin = w.shape[0], w.shape[1]
+    assert cin % 4 == 0 and cout % 32 == 0
+    U = winograd_f24_filters(w)
+    U = U.reshape(4, 6, cout // 32, 2, 16, cin // 4, 4)                              # [i, j, pair, n2, li, ks, lk]
+    U = np.transpose(U, (2, 0, 5, 3, 6, 4, 1))                                       # [pair, i, ks, n2, lk, li, j]
+    lead = U.shape[:3]
+    wide = U[..., [0, 1, 2, 5]].reshape(*lead, 512)
+    narrow = U[..., [3, 4]].reshape(*lead, 256)
+    return np.ascontiguousarray(np.concatenate([wide, narrow], axis=-1), dtype=np.float32).reshape(-1)
 
-    def __init__(self, layers, device):
-        """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu)"""
+
+F24_G2 = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], np.float64)
+F24_G4 = np.array([[.25, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]],
+                  np.float64)
+
+
+def winograd_f24_filters(w):
+    """[Cout, Cin, 3, 3] -> U = G2 g G4^T in float64, [4, 6, Cout, Cin]"""
+    w64 = np.asarray(w, np.float64)
+    U = np.zeros((4, 6) + w64.shape[:2], np.float64)
+    for a in range(3):
+        for b in range(3):
+            U += (F24_G2[:, a][:, None, None, None] * w64[None, None, :, :, a, b]) * F24_G4[:, b][None, :, None, None]
+    return U
+
+
+F24_FLAG = 2          # relu_host[l] bit 1 of buf_cylindrical_net_wg: the layer's buffer holds the F(2x4) set behind the F(2x2) set
+
+
+def cyl_layer_filters(w):
+    """The fp32 kernel's filter buffer of one layer and its F(2x4) flag: layers with 128 output channels run in the F(2x4) form
+    (k_cyl_net_w24) and carry that set behind the F(2x2) one."""
+    wt = winograd_tile_weights(w)
+    if w.shape[0] != 128:
+        return wt, 0
+    return np.concatenate([wt, winograd_f24_tile_weights(w)]), F24_FLAG
+
+
+class CylindricalNet:
+    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip: per layer U = G g G^T in the kernel's
+    tiling (layers with 128 output channels: the F(2x4) set behind it, flagged in the relu word), biases."""
+
+    def __init__(self, layers, device, f24=True):
+        """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  f24 = False: the F(2x2) form in every
+        layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B)."""
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_wg"
+        flags = []
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
-            self.wt.append(torch.from_numpy(winograd_tile_weights(w)).to(device))
+            wt, flag = cyl_layer_filters(w) if f24 else (winograd_tile_weights(w), 0)
+            flags.append(flag)
+            self.wt.append(torch.from_numpy(wt).to(device))
             self.bias.append(torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(device))
             self.cin.append(cin); self.cout.append(cout); self.relu.append(1 if relu else 0)
         n = len(layers)
@@ -675,7 +724,7 @@ class CylindricalNet:
         self._bp = (C.c_void_p * n)(*[t.data_ptr() for t in self.bias])
         self._ci = (C.c_int * n)(*self.cin)
         self._co = (C.c_int * n)(*self.cout)
-        self._re = (C.c_int * n)(*self.relu)
+        self._re = (C.c_int * n)(*[r | f for r, f in zip(self.relu, flags)])
 
     def __call__(self, x):
         """x f32[P,16,420] (or [P,48,140]) -> f32[P,32,7,20]"""
@@ -727,8 +776,10 @@ class CylindricalNetSplit:
         # the fp32 re-run needs the Winograd tiling of the same filters; widths it is not built for keep the raising contract
         self.safe = n == 8 and _lib.lib().buf_cylindrical_net_wg_supports(self._ci, self._co) == 0 and not os.environ.get('BUF_SPLIT_UNSAFE')
         if self.safe:
-            self.wt_wg = [torch.from_numpy(winograd_tile_weights(w)).to(device) for w, _, _ in layers]
+            tiled = [cyl_layer_filters(w) for w, _, _ in layers]
+            self.wt_wg = [torch.from_numpy(wt).to(device) for wt, _ in tiled]
             self._wwp = (C.c_void_p * n)(*[t.data_ptr() for t in self.wt_wg])
+            self._re_safe = (C.c_int * n)(*[r | f for r, (_, f) in zip(self.relu, tiled)])     # (the split kernel itself takes 0 / 1)
 
     def _safe_call(self, x, head):
         L = _lib.lib()
@@ -737,7 +788,7 @@ class CylindricalNetSplit:
         out = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
         desc = torch.empty((P, 32), dtype=torch.float32, device=x.device) if head is not None else None
         self.last_flags = torch.empty((max(P, 1),), dtype=torch.int32, device=x.device)
-        check(L.buf_cylindrical_net_split_safe(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re,
+        check(L.buf_cylindrical_net_split_safe(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe,
                                                _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
                                                _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe")
         return (desc, out) if head is not None else out

@@ -286,6 +286,16 @@ int     buf_winograd_group(int cin, int cout);                                  
 int     buf_winograd_tile_weights(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 16*Cout*Cin floats */
 int     buf_winograd_tile_filters(const float* w_host, int cout, int cin, int ng, int nblk, float* out_host);
                                                    /* host only: the same tiling with N-groups of ng and nblk = 4 | 5 blocks -> 4*nblk*Cout*Cin floats */
+/* The F(2x4, 3x3) form of the layers with 128 output channels (csrc/convnet_w24.hip, kernel k_cyl_net_w24: tiles of 2 x 4 outputs along
+ * the azimuth, 30 instead of 38 matrix instructions per 4 input x 16 output channels in those layers; the other layers as above;
+ * all fp32).  Opt-in per call through relu_host[l]: bit 0 is the ReLU as before, bit 1 (BUF_CYL_F24) says that wt_host[l] holds,
+ * BEHIND the 16*Cout*Cin floats above, the 24*Cout*Cin floats of buf_winograd_f24_tile_weights: U = G2 g G4^T (4 row x 6 column
+ * components; points 0, +-1, +-2, infinity; fp64 on the host) tiled [pair][i][k-step][768] with, per (row component i, k-step),
+ * the column components j = 0, 1, 2, 5 of the pair's two N-tiles as [n2][lk][li][4] and then j = 3, 4 as [n2][lk][li][2].
+ * If any layer carries the bit, every layer with 128 output channels must and no other may (else BUF_EINVAL); with 0 / 1 in
+ * every word nothing beyond the first 16*Cout*Cin floats of a buffer is read. */
+#define BUF_CYL_F24 2
+int     buf_winograd_f24_tile_weights(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 24*Cout*Cin floats; Cout a multiple of 32 */
 int     buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream);
 int     buf_cylindrical_net_wg_supports(const int* cin_host, const int* cout_host);   /* host only: 0 if the kernel is built for these 8 widths */
@@ -319,7 +329,8 @@ int     buf_cylindrical_net_split_head(const float* x, int npatch, const void* c
  * return at once, flagged patches are recomputed in fp32 and overwrite their result (bit-identical to buf_cylindrical_net_wg [+
  * buf_descriptor_head] for those patches).  Same stream, no host round trip; nothing is returned from behind an overflow.
  * head_params null: y_or_equi = y f32[np,32,140]; else desc f32[np,32] and y_or_equi = equi f32[np,32,140].
- * wt_split_host as buf_cylindrical_net_split, wt_wg_host as buf_cylindrical_net_wg, bias_host shared.  Replaces the model's
+ * wt_split_host as buf_cylindrical_net_split, wt_wg_host as buf_cylindrical_net_wg (relu_host may carry BUF_CYL_F24 for it: the
+ * split kernel sees bit 0 only), bias_host shared.  Replaces the model's
  * torch layers of models/patchnet.py:15-85 exactly like the two entry points it combines. */
 int     buf_cylindrical_net_split_safe(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                        const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
