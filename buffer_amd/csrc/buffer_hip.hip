@@ -23,5 +23,6 @@
 // two fp32-MFMA CNN kernels, whose Winograd transforms the compiler had built on v_pk_add_f32, measured 0.9 % FASTER without them.
 #include "convnet_wg.hip"
 #include "convnet_w24.hip"
+#include "convnet_w24k.hip"
 #include "costnet.hip"
 #include "split_safe.hip"

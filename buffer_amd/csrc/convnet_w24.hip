@@ -152,6 +152,8 @@ __device__ __forceinline__ void w24_pass(unsigned (&RA)[4], __amdgpu_buffer_rsrc
 //     output row 0 = F_2,      output row 1 = -F_0 + 2 F_1 - F_3
 // The bias enters column component 1 -- the one A4^T carries into all four columns with weight 1 -- before pass 1.
 // On entry W holds the first two k-steps at wp, on exit those at wp_after.
+// NOBIAS: bias_lane may be null, as in wg_round (the upper K half of w24k_layer_ksplit, csrc/convnet_w24k.hip, carries no bias).
+template <bool NOBIAS = false>
 __device__ __forceinline__ void w24_round(unsigned (&RA)[4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_after, unsigned lofs4, unsigned lofs2,
                                           int niter, unsigned pstride, const float* __restrict__ bias_lane, wgf4 (&W4)[2][2], wgf2 (&W2)[2][2],
                                           wgf4 (&Y)[2][2][4])
@@ -160,7 +162,10 @@ __device__ __forceinline__ void w24_round(unsigned (&RA)[4], __amdgpu_buffer_rsr
     wgf2 D[2][6];
     wgf4 bv[2];
 #pragma unroll
-    for (int n = 0; n < 2; n++) bv[n] = *reinterpret_cast<const wgf4*>(bias_lane + n * 16);
+    for (int n = 0; n < 2; n++) {
+        if constexpr (NOBIAS) bv[n] = bias_lane ? *reinterpret_cast<const wgf4*>(bias_lane + n * 16) : (wgf4){ 0.f, 0.f, 0.f, 0.f };
+        else bv[n] = *reinterpret_cast<const wgf4*>(bias_lane + n * 16);
+    }
     wgf4 acc[2][6];
     float zero = 0.f;
     asm volatile("" : "+v"(zero));                   // (an opaque zero: see wg_round)
@@ -214,7 +219,8 @@ __device__ __forceinline__ void w24_round(unsigned (&RA)[4], __amdgpu_buffer_rsr
 // Output row 6, columns 0..15 of the N-tile pair in the direct form: wg_round_direct's steps and pipeline on the 16-byte parts of the
 // F(2x4) block rows 0..2.  One accumulator per AZIMUTH tap b (the filter rows a = 0, 1 add up in it, K ascending): the taps as formed
 // from the blocks are g[a][b] / (4, -3, 1)[b], and y = 4 acc_0 - 3 acc_1 + acc_2 once at the end; the bias starts in acc_2.
-// On entry W4 holds block 0's first two k-steps.
+// On entry W4 holds block 0's first two k-steps.  NOBIAS: bias_lane may be null.
+template <bool NOBIAS = false>
 __device__ __forceinline__ void w24_round_direct(unsigned row5, __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned lofs, int niter, unsigned pstride,
                                                  const float* __restrict__ bias_lane, wgf4 (&W4)[2][2], wgf4 (&Y)[2])
 {
@@ -239,7 +245,8 @@ __device__ __forceinline__ void w24_round_direct(unsigned row5, __amdgpu_buffer_
     for (int n = 0; n < 2; n++) {
         acc[n][0] = (wgf4){ zero, zero, zero, zero };
         acc[n][1] = (wgf4){ zero, zero, zero, zero };
-        acc[n][2] = *reinterpret_cast<const wgf4*>(bias_lane + n * 16);
+        if constexpr (NOBIAS) acc[n][2] = bias_lane ? *reinterpret_cast<const wgf4*>(bias_lane + n * 16) : (wgf4){ zero, zero, zero, zero };
+        else acc[n][2] = *reinterpret_cast<const wgf4*>(bias_lane + n * 16);
     }
     float G[2][6];
 #define W24_TAPS(SLOT)                                                                                    \
@@ -450,18 +457,46 @@ extern "C" int buf_winograd_f24_tile_weights(const float* w_host, int cout, int 
     return BUF_OK;
 }
 
-// The F(2x4) launch behind wg_launch: P as wg_launch filled it (widths checked, relu[] still with the flag bits).
-static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream)
+// The flag rules of a stack that carries bit 1 or bit 2 somewhere, stated once (widths already checked): what w24_launch enforces before
+// its first device call and buf_cylindrical_net_wg_flags reports.
+static int w24_check_flags(const int* cin, const int* cout, const int* relu)
 {
     for (int l = 0; l < WG_LAYERS; l++) {
-        const bool flag = (P.relu[l] & WG_F24_FLAG) != 0;
-        BUF_REQUIRE(P.relu[l] >= 0 && P.relu[l] <= (WG_F24_FLAG | 1), BUF_EINVAL, "buf_cylindrical_net_wg: layer %d has relu flags %d", l, P.relu[l]);
-        BUF_REQUIRE(flag == (P.cout[l] == 128), BUF_EINVAL,
+        BUF_REQUIRE(relu[l] >= 0 && relu[l] <= (BUF_CYL_F24K | WG_F24_FLAG | 1), BUF_EINVAL,
+                    "buf_cylindrical_net_wg: layer %d has the relu word %d (bit 0: ReLU, bits 1 and 2: the F(2x4) flags, nothing above)", l, relu[l]);
+        BUF_REQUIRE(!(relu[l] & BUF_CYL_F24K) || (cout[l] == 64 && cin[l] % 64 == 0), BUF_EINVAL,
+                    "buf_cylindrical_net_wg: the K-split F(2x4) flag (bit 2) goes only on layers with 64 output channels and Cin %% 64 == 0 "
+                    "(layer %d: %d -> %d, flags %d)", l, cin[l], cout[l], relu[l]);
+        BUF_REQUIRE(((relu[l] & WG_F24_FLAG) != 0) == (cout[l] == 128), BUF_EINVAL,
                     "buf_cylindrical_net_wg: the F(2x4) flag goes on every layer with 128 output channels and on no other (layer %d: %d -> %d, flags %d)",
-                    l, P.cin[l], P.cout[l], P.relu[l]);
-        if (flag) P.wt[l] += W24_SET_F22(P.cin[l]);
-        P.relu[l] &= 1;
+                    l, cin[l], cout[l], relu[l]);
     }
+    return BUF_OK;
+}
+
+// 0 when buf_cylindrical_net_wg would accept these widths with these relu words (host only, no device call), else BUF_EINVAL with the reason
+extern "C" int buf_cylindrical_net_wg_flags(const int* cin_host, const int* cout_host, const int* relu_host)
+{
+    BUF_REQUIRE(cin_host && cout_host && relu_host, BUF_EINVAL, "buf_cylindrical_net_wg_flags: null argument");
+    if (int rc = wg_check_widths(cin_host, cout_host)) return rc;
+    for (int l = 0; l < WG_LAYERS; l++)
+        if (relu_host[l] >= 2) return w24_check_flags(cin_host, cout_host, relu_host);
+    return BUF_OK;
+}
+
+// The F(2x4) launch behind wg_launch: P as wg_launch filled it (widths checked, relu[] still with the flag bits).  Stacks that carry
+// bit 2 (BUF_CYL_F24K: the K-split F(2x4) form of 64-output layers) go on to k_cyl_net_w24k (csrc/convnet_w24k.hip).
+static int w24k_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
+static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream)
+{
+    if (int rc = w24_check_flags(P.cin, P.cout, P.relu)) return rc;
+    bool ksplit = false;
+    for (int l = 0; l < WG_LAYERS; l++) {
+        if (P.relu[l] & WG_F24_FLAG) P.wt[l] += W24_SET_F22(P.cin[l]);
+        ksplit |= (P.relu[l] & BUF_CYL_F24K) != 0;
+        P.relu[l] &= ~WG_F24_FLAG;
+    }
+    if (ksplit) return w24k_launch(x, npatch, P, y, stream);
     size_t lds = sizeof(float) * WG_BUF;
     static LdsGrant grant, grant_rerun;
     if (int rc = P.only_if ? grant_dynamic_lds((const void*)k_cyl_net_w24_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_w24, lds, grant)) return rc;

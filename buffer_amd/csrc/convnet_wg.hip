@@ -802,9 +802,11 @@ extern "C" int buf_cylindrical_net_wg_supports(const int* cin_host, const int* c
 }
 
 // relu_host[l] bit 1 (WG_F24_FLAG): the layer's filter buffer holds the F(2x4) set behind the F(2x2) set and the stack runs in
-// k_cyl_net_w24 (csrc/convnet_w24.hip), which launches it: w24_launch.  Callers that pass 0 / 1 never reach it.
+// k_cyl_net_w24 (csrc/convnet_w24.hip), which launches it: w24_launch.  Bit 2 (BUF_CYL_F24K) likewise for the K-split F(2x4) form of
+// 64-output layers (csrc/convnet_w24k.hip).  Every word above 1 goes to w24_launch, which checks the flag rules; callers that pass
+// 0 / 1 never reach it.
 #define WG_F24_FLAG BUF_CYL_F24
-static inline bool wg_f24_flagged(int relu) { return relu == WG_F24_FLAG || relu == (WG_F24_FLAG | 1); }
+static inline bool wg_f24_flagged(int relu) { return relu >= 2; }
 static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
 
 // x f32[np,48,140] -> y f32[np,32,140]; weights in the Winograd-domain tiling (see CylWgParams).

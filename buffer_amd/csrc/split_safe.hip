@@ -26,10 +26,10 @@ extern "C" int buf_cylindrical_net_split_safe(const float* x, int npatch, const 
     BUF_REQUIRE(x && y_or_equi && flags_ws && wt_split_host && wt_wg_host && bias_host && cin_host && cout_host && relu_host, BUF_EINVAL,
                 "buf_cylindrical_net_split_safe: null argument");
     BUF_REQUIRE(!head_params || desc, BUF_EINVAL, "buf_cylindrical_net_split_safe: head without desc");
-    if (int rc = buf_cylindrical_net_wg_supports(cin_host, cout_host)) return rc;       // the re-run must exist for these widths
+    if (int rc = buf_cylindrical_net_wg_flags(cin_host, cout_host, relu_host)) return rc;       // the re-run must exist for these widths and take these relu words: before any device call
     hipStream_t s = (hipStream_t)stream;
     BUF_CHECK_HIP(hipMemsetAsync(flags_ws, 0, sizeof(int) * (size_t)npatch, s));
-    int relu_split[WG_LAYERS];                        // the split kernel knows 0 / 1 only: without the fp32 kernel's F(2x4) flag
+    int relu_split[WG_LAYERS];                        // the split kernel knows 0 / 1 only: without the fp32 kernel's F(2x4) flags
     for (int l = 0; l < WG_LAYERS; l++) relu_split[l] = wg_f24_flagged(relu_host[l]) ? (relu_host[l] & 1) : relu_host[l];
     int rc = h3_launch(x, npatch, wt_split_host, bias_host, cin_host, cout_host, relu_split, head_params ? nullptr : y_or_equi, head_params,
                        desc, head_params ? y_or_equi : nullptr, status_dev, stream, flags_ws);

@@ -691,30 +691,38 @@ def winograd_f24_filters(w):
 
 
 F24_FLAG = 2          # relu_host[l] bit 1 of buf_cylindrical_net_wg: the layer's buffer holds the F(2x4) set behind the F(2x2) set
+F24K_FLAG = 4         # bit 2: the same for a layer with 64 output channels and Cin % 64 == 0 (the K-split form, k_cyl_net_w24k)
 
 
-def cyl_layer_filters(w):
+def cyl_layer_filters(w, f24k=True):
     """The fp32 kernel's filter buffer of one layer and its F(2x4) flag: layers with 128 output channels run in the F(2x4) form
-    (k_cyl_net_w24) and carry that set behind the F(2x2) one."""
+    (flag 2) and, with f24k, so do the layers with 64 output channels whose Cin is a multiple of 64 (flag 4: the K-split form of
+    k_cyl_net_w24k); both carry that set behind the F(2x2) one."""
     wt = winograd_tile_weights(w)
-    if w.shape[0] != 128:
+    cout, cin = w.shape[0], w.shape[1]
+    if cout == 128:
+        flag = F24_FLAG
+    elif f24k and cout == 64 and cin % 64 == 0:
+        flag = F24K_FLAG
+    else:
         return wt, 0
-    return np.concatenate([wt, winograd_f24_tile_weights(w)]), F24_FLAG
+    return np.concatenate([wt, winograd_f24_tile_weights(w)]), flag
 
 
 class CylindricalNet:
-    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip: per layer U = G g G^T in the kernel's
-    tiling (layers with 128 output channels: the F(2x4) set behind it, flagged in the relu word), biases."""
+    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip / csrc/convnet_w24k.hip: per layer U = G g G^T in
+    the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu word), biases."""
 
-    def __init__(self, layers, device, f24=True):
+    def __init__(self, layers, device, f24=True, f24k=True):
         """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  f24 = False: the F(2x2) form in every
-        layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B)."""
+        layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B); f24k = False: F(2x4) in the 128-output layers
+        only (k_cyl_net_w24)."""
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_wg"
         flags = []
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
-            wt, flag = cyl_layer_filters(w) if f24 else (winograd_tile_weights(w), 0)
+            wt, flag = cyl_layer_filters(w, f24k) if f24 else (winograd_tile_weights(w), 0)
             flags.append(flag)
             self.wt.append(torch.from_numpy(wt).to(device))
             self.bias.append(torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(device))
@@ -757,7 +765,7 @@ class CylindricalNetSplit:
     kernel.  For widths the fp32 kernel is not built for (the released network's are) the old contract stays: `check_range()` raises if
     the status word was set."""
 
-    def __init__(self, layers, device):
+    def __init__(self, layers, device, f24k=True):
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_split"
         for w, b, relu in layers:
@@ -776,7 +784,7 @@ class CylindricalNetSplit:
         # the fp32 re-run needs the Winograd tiling of the same filters; widths it is not built for keep the raising contract
         self.safe = n == 8 and _lib.lib().buf_cylindrical_net_wg_supports(self._ci, self._co) == 0 and not os.environ.get('BUF_SPLIT_UNSAFE')
         if self.safe:
-            tiled = [cyl_layer_filters(w) for w, _, _ in layers]
+            tiled = [cyl_layer_filters(w, f24k) for w, _, _ in layers]
             self.wt_wg = [torch.from_numpy(wt).to(device) for wt, _ in tiled]
             self._wwp = (C.c_void_p * n)(*[t.data_ptr() for t in self.wt_wg])
             self._re_safe = (C.c_int * n)(*[r | f for r, (_, f) in zip(self.relu, tiled)])     # (the split kernel itself takes 0 / 1)

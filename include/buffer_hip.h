@@ -295,6 +295,13 @@ int     buf_winograd_tile_filters(const float* w_host, int cout, int cin, int ng
  * If any layer carries the bit, every layer with 128 output channels must and no other may (else BUF_EINVAL); with 0 / 1 in
  * every word nothing beyond the first 16*Cout*Cin floats of a buffer is read. */
 #define BUF_CYL_F24 2
+/* The same form in layers with 64 output channels and Cin a multiple of 64 (csrc/convnet_w24k.hip, kernel k_cyl_net_w24k: the four
+ * wavefronts split K and exchange partial sums through LDS; 30 instead of 38 matrix instructions there as well).  Bit 2 (BUF_CYL_F24K)
+ * of relu_host[l] says that wt_host[l] holds the 24*Cout*Cin floats of buf_winograd_f24_tile_weights behind its 16*Cout*Cin floats.
+ * Allowed only on such layers, and only in a stack that also satisfies the bit-1 rule above (every layer with 128 output channels
+ * carries bit 1); words above 7 are rejected (BUF_EINVAL).  buf_cylindrical_net_wg_flags reports what a call would accept. */
+#define BUF_CYL_F24K 4
+int     buf_cylindrical_net_wg_flags(const int* cin_host, const int* cout_host, const int* relu_host);   /* host only: 0 if these 8 widths and relu words are accepted */
 int     buf_winograd_f24_tile_weights(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 24*Cout*Cin floats; Cout a multiple of 32 */
 int     buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream);
@@ -329,7 +336,7 @@ int     buf_cylindrical_net_split_head(const float* x, int npatch, const void* c
  * return at once, flagged patches are recomputed in fp32 and overwrite their result (bit-identical to buf_cylindrical_net_wg [+
  * buf_descriptor_head] for those patches).  Same stream, no host round trip; nothing is returned from behind an overflow.
  * head_params null: y_or_equi = y f32[np,32,140]; else desc f32[np,32] and y_or_equi = equi f32[np,32,140].
- * wt_split_host as buf_cylindrical_net_split, wt_wg_host as buf_cylindrical_net_wg (relu_host may carry BUF_CYL_F24 for it: the
+ * wt_split_host as buf_cylindrical_net_split, wt_wg_host as buf_cylindrical_net_wg (relu_host may carry BUF_CYL_F24 / BUF_CYL_F24K for it: the
  * split kernel sees bit 0 only), bias_host shared.  Replaces the model's
  * torch layers of models/patchnet.py:15-85 exactly like the two entry points it combines. */
 int     buf_cylindrical_net_split_safe(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
