@@ -102,6 +102,8 @@ _SIGNATURES = {
     "buf_icp_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "buf_icp_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp,
                              _vp, _sz, _vp]),
+    "buf_gicp_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, C.c_double, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _sz, _vp]),
     "buf_pair_stats_ws_bytes": (_sz, [_i, _i, _i, _i, _i64]),
     "buf_pair_stats": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "buf_match_metrics": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),

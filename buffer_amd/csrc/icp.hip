@@ -1,6 +1,7 @@
-// ICP, point-to-point and point-to-plane, for B pairs per call (open3d registration_icp with
-// TransformationEstimationPointToPoint / TransformationEstimationPointToPlane, restated, unpinned: Kabsch for point-to-point,
-// open3d's 6x6 step for point-to-plane).  Every ICP entry point of buffer_amd/icp.py runs here.
+// ICP, point-to-point, point-to-plane and Generalized (plane-to-plane), for B pairs per call (open3d registration_icp with
+// TransformationEstimationPointToPoint / TransformationEstimationPointToPlane and registration_generalized_icp, restated,
+// unpinned: Kabsch for point-to-point, open3d's 6x6 step for point-to-plane, the Gauss-Newton step of Segal et al. on
+// normal-based covariances for Generalized ICP).  Every ICP entry point of buffer_amd/icp.py runs here.
 //
 // Set-up (once per call):
 //   buf_grid_build   one A2 cell grid over all targets, one element per pair, radius = max_dist
@@ -25,10 +26,13 @@
 #define ICP_WAVES (ICP_TILE / WAVE)
 #define ICP_P2P BUF_ICP_POINT_TO_POINT
 #define ICP_P2L BUF_ICP_POINT_TO_PLANE
+#define ICP_GICP BUF_ICP_GENERALIZED
 
 // record values: [0] matches, [1] sum d2, then
 //   point-to-point: sum P (3), sum Q (3), sum P Q^T (9, row-major) with P = p - a, Q = q - a (a = the pair's anchor)
 //   point-to-plane: upper triangle of J^T J (21, row by row), J^T r (6); J = [p x n, n], r = (p - q) . n
+//   generalized:    upper triangle of J^T M J (21, row by row), J^T M d (6); J = [-[p]x, I], d = p - q,
+//                   M = (C(n_q) + R C(n_s) R^T)^-1 with C(n) = I - (1 - eps) n n^T
 template <int M> struct IcpRec { static constexpr int NV = M == ICP_P2P ? 17 : 29; static constexpr int STRIDE = M == ICP_P2P ? 18 : 30; };
 
 struct IcpState {
@@ -88,13 +92,32 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_setup(const float* __restrict_
     }
 }
 
-template <int M>
+// what only the Generalized ICP instantiation of k_icp_correspond takes (the other two have no such argument)
+struct IcpGicpArgs { const float* src_normals; double w; };              // w = 1 - epsilon
+__device__ __forceinline__ const IcpGicpArgs& icp_gicp_args(const IcpGicpArgs& a) { return a; }
+
+__device__ static void icp_cross(const double* a, const double* b, double* c)
+{
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// row j of a normal array in fp64; a row that is not a unit vector (| |n|^2 - 1 | >= 1e-3, or any component not finite) is zero
+__device__ __forceinline__ void icp_gicp_normal(const float* __restrict__ normals, size_t j, double (&n)[3])
+{
+    n[0] = normals[3 * j]; n[1] = normals[3 * j + 1]; n[2] = normals[3 * j + 2];
+    const double l2 = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+    if (!(fabs(l2 - 1.0) < 1e-3)) { n[0] = 0.0; n[1] = 0.0; n[2] = 0.0; }   // (NaN and inf fail the comparison)
+}
+
+template <int M, typename... G>
 __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __restrict__ grids, const int* __restrict__ table,
                                                            const float4* __restrict__ sorted, const float* __restrict__ src,
                                                            const int* __restrict__ src_off, const int* __restrict__ tile_off, int npairs,
                                                            const float* __restrict__ tgt, const float* __restrict__ tgt_normals, int nt,
                                                            float r2, const double* __restrict__ T, const IcpState* __restrict__ st,
-                                                           int* __restrict__ nn_out, double* __restrict__ slab)
+                                                           int* __restrict__ nn_out, double* __restrict__ slab, G... gicp)
 {
     constexpr int NV = IcpRec<M>::NV;
     __shared__ double part[ICP_WAVES][NV];
@@ -151,6 +174,61 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __r
                 for (int r = 0; r < 3; r++)
 #pragma unroll
                     for (int c = 0; c < 3; c++) v[8 + 3 * r + c] = P[r] * Q[c];
+            } else if constexpr (M == ICP_GICP) {
+                const IcpGicpArgs& ga = icp_gicp_args(gicp...);
+                const double p[3] = { px, py, pz };
+                double nq[3], ns[3];
+                icp_gicp_normal(tgt_normals, (size_t)best, nq);
+                icp_gicp_normal(ga.src_normals, i, ns);
+                // S = C(n_q) + R C(n_s) R^T = (I - w n_q n_q^T) + (R R^T - w m m^T), m = R n_s; upper triangle 00 01 02 11 12 22
+                double m[3], S[6];
+#pragma unroll
+                for (int r = 0; r < 3; r++) m[r] = (Tb[4 * r] * ns[0] + Tb[4 * r + 1] * ns[1]) + Tb[4 * r + 2] * ns[2];
+                {
+                    int k = 0;
+#pragma unroll
+                    for (int r = 0; r < 3; r++)
+#pragma unroll
+                        for (int c = r; c < 3; c++) {
+                            const double rr = (Tb[4 * r] * Tb[4 * c] + Tb[4 * r + 1] * Tb[4 * c + 1]) + Tb[4 * r + 2] * Tb[4 * c + 2];
+                            S[k++] = (((r == c ? 1.0 : 0.0) - ga.w * nq[r] * nq[c]) + rr) - ga.w * m[r] * m[c];
+                        }
+                }
+                // Mm = S^-1 by cofactors (S is symmetric positive definite: both terms are, for eps > 0)
+                const double c00 = S[3] * S[5] - S[4] * S[4], c01 = S[2] * S[4] - S[1] * S[5], c02 = S[1] * S[4] - S[2] * S[3];
+                const double c11 = S[0] * S[5] - S[2] * S[2], c12 = S[1] * S[2] - S[0] * S[4], c22 = S[0] * S[3] - S[1] * S[1];
+                const double idet = 1.0 / ((S[0] * c00 + S[1] * c01) + S[2] * c02);
+                const double Mm[3][3] = { { c00 * idet, c01 * idet, c02 * idet }, { c01 * idet, c11 * idet, c12 * idet },
+                                          { c02 * idet, c12 * idet, c22 * idet } };
+                // with A = -[p]x: row r of M A is p x (row r of M), A^T x is p x x.  MA is formed once and serves all three blocks.
+                double MA[3][3], col[3], AtMA[3][3], Md[3], AtMd[3];
+#pragma unroll
+                for (int r = 0; r < 3; r++) {
+                    icp_cross(p, Mm[r], MA[r]);
+                    Md[r] = (Mm[r][0] * dx + Mm[r][1] * dy) + Mm[r][2] * dz;
+                }
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const double mc[3] = { MA[0][c], MA[1][c], MA[2][c] };
+                    icp_cross(p, mc, col);
+#pragma unroll
+                    for (int r = 0; r < 3; r++) AtMA[r][c] = col[r];
+                }
+                icp_cross(p, Md, AtMd);
+                int k = 2;
+#pragma unroll
+                for (int r = 0; r < 3; r++) {                              // rows 0..2 of H: [A^T M A | A^T M], A^T M = (M A)^T
+#pragma unroll
+                    for (int c = r; c < 3; c++) v[k++] = AtMA[r][c];
+#pragma unroll
+                    for (int c = 0; c < 3; c++) v[k++] = MA[c][r];
+                }
+#pragma unroll
+                for (int r = 0; r < 3; r++)                                // rows 3..5: M
+#pragma unroll
+                    for (int c = r; c < 3; c++) v[k++] = Mm[r][c];
+#pragma unroll
+                for (int r = 0; r < 3; r++) { v[23 + r] = AtMd[r]; v[26 + r] = Md[r]; }
             } else {
                 const size_t j = 3 * (size_t)best;
                 const double nx = tgt_normals[j], ny = tgt_normals[j + 1], nz = tgt_normals[j + 2];
@@ -173,13 +251,6 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __r
 // Kabsch: R maximising tr(R H) over proper rotations, H = sum (p - pc)(q - qc)^T.  One-sided Jacobi on the columns of H
 // (H V = U S), singular values sorted descending; with U3 = U1 x U2 and V3 = V1 x V2 the rotation V diag(1, 1, d) U^T of
 // the det-corrected SVD (d = sign det(V U^T)) is [V1 V2 V1xV2][U1 U2 U1xU2]^T whatever the sign of the third pair.
-__device__ static void icp_cross(const double* a, const double* b, double* c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 __device__ static bool icp_unit(double* a)
 {
     const double l = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
@@ -379,23 +450,24 @@ static IcpWs carve_icp(WsCarver& w, int ns, int nt, int npairs, int method)
 
 extern "C" size_t buf_icp_ws_bytes(int n_src_total, int n_tgt_total, int npairs, int method)
 {
-    if (n_src_total < 0 || n_tgt_total < 0 || npairs <= 0 || (method != ICP_P2P && method != ICP_P2L)) return 0;
+    if (n_src_total < 0 || n_tgt_total < 0 || npairs <= 0 || (method != ICP_P2P && method != ICP_P2L && method != ICP_GICP)) return 0;
     WsCarver w(nullptr, 0);
     carve_icp(w, n_src_total, n_tgt_total, npairs, method);
     return w.used();
 }
 
-template <int M>
+template <int M, typename... G>
 static int icp_rounds(const IcpWs& e, const buf_grid_t& g, const float* src, const float* tgt, const float* tgt_normals, int nt,
                       int npairs, int ntiles, float r2, int max_iteration, double rel_fitness, double rel_rmse, double* T_out,
-                      double* fitness_out, double* rmse_out, int* iters_out, int* nn_out, hipStream_t s)
+                      double* fitness_out, double* rmse_out, int* iters_out, int* nn_out, hipStream_t s, G... gicp)
 {
     for (int r = 0; r <= max_iteration; r++) {
         const bool probe = (r & 7) == 7 && r < max_iteration;
         if (probe) BUF_CHECK_HIP(hipMemsetAsync(e.active, 0, sizeof(int), s));
         if (ntiles > 0)
             k_icp_correspond<M><<<ntiles, ICP_TILE, 0, s>>>((const CellGrid*)g.desc, g.table, (const float4*)g.sorted, src, e.src_off,
-                                                           e.tile_off, npairs, tgt, tgt_normals, nt, r2, T_out, e.st, nn_out, e.slab);
+                                                           e.tile_off, npairs, tgt, tgt_normals, nt, r2, T_out, e.st, nn_out, e.slab,
+                                                           gicp...);
         k_icp_update<M><<<npairs, WAVE, 0, s>>>(e.src_off, e.tile_off, e.slab, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out,
                                                 rmse_out, iters_out, e.st, probe ? e.active : nullptr);
         if (probe) {
@@ -410,45 +482,48 @@ static int icp_rounds(const IcpWs& e, const buf_grid_t& g, const float* src, con
     return BUF_OK;
 }
 
-extern "C" int buf_icp_batched(const float* src, const int* src_lengths_host, const float* tgt, const float* tgt_normals,
-                               const int* tgt_lengths_host, int npairs, int method, float max_dist, const double* T_init,
-                               int max_iteration, double rel_fitness, double rel_rmse, double* T_out, double* fitness_out,
-                               double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream)
+// buf_icp_batched (fn = its name, method 0 / 1) and buf_gicp_batched (method 2, with src_normals and epsilon): one body
+static int icp_run(const char* fn, const float* src, const float* src_normals, const int* src_lengths_host, const float* tgt,
+                   const float* tgt_normals, const int* tgt_lengths_host, int npairs, int method, float max_dist, double epsilon,
+                   const double* T_init, int max_iteration, double rel_fitness, double rel_rmse, double* T_out, double* fitness_out,
+                   double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    BUF_REQUIRE(npairs >= 0, BUF_EINVAL, "buf_icp_batched: npairs=%d", npairs);
-    BUF_REQUIRE(method == ICP_P2P || method == ICP_P2L, BUF_EINVAL, "buf_icp_batched: unknown method %d", method);
-    BUF_REQUIRE(max_dist > 0.f && max_dist <= 3.4e38f, BUF_EINVAL, "buf_icp_batched: max_dist=%g (must be finite and > 0)", (double)max_dist);
-    BUF_REQUIRE(method != ICP_P2L || tgt_normals, BUF_EINVAL, "buf_icp_batched: point-to-plane needs target normals");
-    BUF_REQUIRE(max_iteration >= 0, BUF_EINVAL, "buf_icp_batched: max_iteration=%d", max_iteration);
+    BUF_REQUIRE(npairs >= 0, BUF_EINVAL, "%s: npairs=%d", fn, npairs);
+    BUF_REQUIRE(max_dist > 0.f && max_dist <= 3.4e38f, BUF_EINVAL, "%s: max_dist=%g (must be finite and > 0)", fn, (double)max_dist);
+    BUF_REQUIRE(method != ICP_P2L || tgt_normals, BUF_EINVAL, "%s: point-to-plane needs target normals", fn);
+    BUF_REQUIRE(method != ICP_GICP || (epsilon > 0.0 && epsilon <= 1.0), BUF_EINVAL, "%s: epsilon=%g (must be in (0, 1])", fn, epsilon);
+    BUF_REQUIRE(max_iteration >= 0, BUF_EINVAL, "%s: max_iteration=%d", fn, max_iteration);
     if (npairs == 0) return BUF_OK;
-    BUF_REQUIRE(src_lengths_host && tgt_lengths_host, BUF_EINVAL, "buf_icp_batched: null lengths");
+    BUF_REQUIRE(src_lengths_host && tgt_lengths_host, BUF_EINVAL, "%s: null lengths", fn);
     long long ns = 0, nt = 0, nts = 0;
     for (int b = 0; b < npairs; b++) {
-        BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0, BUF_EINVAL, "buf_icp_batched: negative length in pair %d", b);
+        BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0, BUF_EINVAL, "%s: negative length in pair %d", fn, b);
         ns += src_lengths_host[b];
         nt += tgt_lengths_host[b];
         nts += cdiv(src_lengths_host[b], ICP_TILE);
     }
-    BUF_REQUIRE(ns < 0x7fffffffLL && nt < 0x7fffffffLL, BUF_EINVAL, "buf_icp_batched: %lld / %lld points (int32 indices)", ns, nt);
-    BUF_REQUIRE(ns == 0 || src, BUF_EINVAL, "buf_icp_batched: null src");
-    BUF_REQUIRE(nt == 0 || tgt, BUF_EINVAL, "buf_icp_batched: null tgt");
-    BUF_REQUIRE(T_init && T_out && fitness_out && rmse_out && iters_out && ws, BUF_EINVAL, "buf_icp_batched: null argument");
-    BUF_REQUIRE(npairs <= 65535, BUF_EINVAL, "buf_icp_batched: %d pairs (at most 65535 per call)", npairs);
+    BUF_REQUIRE(ns < 0x7fffffffLL && nt < 0x7fffffffLL, BUF_EINVAL, "%s: %lld / %lld points (int32 indices)", fn, ns, nt);
+    BUF_REQUIRE(ns == 0 || src, BUF_EINVAL, "%s: null src", fn);
+    BUF_REQUIRE(nt == 0 || tgt, BUF_EINVAL, "%s: null tgt", fn);
+    BUF_REQUIRE(method != ICP_GICP || ((ns == 0 || src_normals) && (nt == 0 || tgt_normals)), BUF_EINVAL,
+                "%s: Generalized ICP needs source and target normals", fn);
+    BUF_REQUIRE(T_init && T_out && fitness_out && rmse_out && iters_out && ws, BUF_EINVAL, "%s: null argument", fn);
+    BUF_REQUIRE(npairs <= 65535, BUF_EINVAL, "%s: %d pairs (at most 65535 per call)", fn, npairs);
     const size_t need = buf_icp_ws_bytes((int)ns, (int)nt, npairs, method);
-    BUF_REQUIRE(ws_bytes >= need, BUF_EWORKSPACE, "buf_icp_batched: workspace %zu < %zu bytes", ws_bytes, need);
+    BUF_REQUIRE(ws_bytes >= need, BUF_EWORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
 
     WsCarver w(ws, ws_bytes);
     const IcpWs e = carve_icp(w, (int)ns, (int)nt, npairs, method);
     buf_grid_t g;
     int rc = buf_grid_build(&g, tgt, (int)nt, tgt_lengths_host, npairs, max_dist, 0, e.grid, e.grid_bytes, s);
     if (rc) return rc;
-    rc = upload_offsets(e.src_off, src_lengths_host, npairs, (int)ns, "buf_icp_batched", s);
+    rc = upload_offsets(e.src_off, src_lengths_host, npairs, (int)ns, fn, s);
     if (rc) return rc;
     int* tiles = (int*)malloc(sizeof(int) * (size_t)npairs);
-    BUF_REQUIRE(tiles, BUF_EINVAL, "buf_icp_batched: out of host memory");
+    BUF_REQUIRE(tiles, BUF_EINVAL, "%s: out of host memory", fn);
     for (int b = 0; b < npairs; b++) tiles[b] = cdiv(src_lengths_host[b], ICP_TILE);
-    rc = upload_offsets(e.tile_off, tiles, npairs, (int)nts, "buf_icp_batched", s);
+    rc = upload_offsets(e.tile_off, tiles, npairs, (int)nts, fn, s);
     free(tiles);
     if (rc) return rc;
     k_icp_setup<<<npairs, ICP_TILE, 0, s>>>(src, e.src_off, T_init, T_out, fitness_out, rmse_out, iters_out, e.st);
@@ -457,6 +532,31 @@ extern "C" int buf_icp_batched(const float* src, const int* src_lengths_host, co
     if (method == ICP_P2P)
         return icp_rounds<ICP_P2P>(e, g, src, tgt, nullptr, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
                                    fitness_out, rmse_out, iters_out, nn_out, s);
-    return icp_rounds<ICP_P2L>(e, g, src, tgt, tgt_normals, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
-                               fitness_out, rmse_out, iters_out, nn_out, s);
+    if (method == ICP_P2L)
+        return icp_rounds<ICP_P2L>(e, g, src, tgt, tgt_normals, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
+                                   fitness_out, rmse_out, iters_out, nn_out, s);
+    return icp_rounds<ICP_GICP>(e, g, src, tgt, tgt_normals, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
+                                fitness_out, rmse_out, iters_out, nn_out, s, IcpGicpArgs{ src_normals, 1.0 - epsilon });
+}
+
+extern "C" int buf_icp_batched(const float* src, const int* src_lengths_host, const float* tgt, const float* tgt_normals,
+                               const int* tgt_lengths_host, int npairs, int method, float max_dist, const double* T_init,
+                               int max_iteration, double rel_fitness, double rel_rmse, double* T_out, double* fitness_out,
+                               double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream)
+{
+    // (Generalized ICP has its own entry: this one has no source normals to give it)
+    BUF_REQUIRE(method == ICP_P2P || method == ICP_P2L, BUF_EINVAL, "buf_icp_batched: unknown method %d", method);
+    return icp_run("buf_icp_batched", src, nullptr, src_lengths_host, tgt, tgt_normals, tgt_lengths_host, npairs, method, max_dist, 1.0,
+                   T_init, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out, iters_out, nn_out, ws, ws_bytes, stream);
+}
+
+extern "C" int buf_gicp_batched(const float* src, const float* src_normals, const int* src_lengths_host, const float* tgt,
+                                const float* tgt_normals, const int* tgt_lengths_host, int npairs, float max_dist, double epsilon,
+                                const double* T_init, int max_iteration, double rel_fitness, double rel_rmse, double* T_out,
+                                double* fitness_out, double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes,
+                                void* stream)
+{
+    return icp_run("buf_gicp_batched", src, src_normals, src_lengths_host, tgt, tgt_normals, tgt_lengths_host, npairs, ICP_GICP, max_dist,
+                   epsilon, T_init, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out, iters_out, nn_out, ws, ws_bytes,
+                   stream);
 }

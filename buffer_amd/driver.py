@@ -70,17 +70,30 @@ def upload(sample):
 
 
 # ---------------------------------------------------------------------------------------------------- registration
-def register_chunks(pipe, chunks, make, gt_of=None):
+def register_chunks(pipe, chunks, make, gt_of=None, refine=None):
     """Chunks of pairs through the device pipeline -> f32[k,4,4] (device) in chunk order.  chunks: lists of pair ids, which also seed
     the pipeline; make(chunk) -> the chunk's sample dicts.  The chunks are software-pipelined over two HIP streams: making chunk
     i+1 (reading, pre-processing) and its keypoint stage run beside the CNN kernels of chunk i (BufferPipeline.register_batches;
     results equal batch-by-batch calls).
     gt_of(chunk) -> the chunk's ground-truth poses: also the per-stage metric rows (register_batches, metrics_gt=: the ground truth
-    is read when the chunk's clouds are, one metric launch per chunk after its pose recovery) -> (poses, counts int32[k,7])."""
+    is read when the chunk's clouds are, one metric launch per chunk after its pose recovery) -> (poses, counts int32[k,7]).
+    refine: BufferPipeline.refine_batch's keyword arguments: every chunk's poses are also refined by dense ICP after its pose
+    recovery -> one more last element, dict(poses f32[k,4,4], fitness f64[k], inlier_rmse f64[k], iterations int32[k]) (device);
+    what comes before it is what a call without refine returns, bit for bit."""
     dev = pipe.device
     makers = [(lambda ch=ch: [upload(s) for s in make(ch)]) for ch in chunks]
     gts = None if gt_of is None else [(lambda ch=ch: gt_of(ch)) for ch in chunks]
-    out = pipe.register_batches(makers, seeds=chunks, metrics_gt=gts)
+    if refine is None:
+        return _unrefined(dev, pipe.register_batches(makers, seeds=chunks, metrics_gt=gts), gt_of)
+    out = pipe.register_batches(makers, seeds=chunks, metrics_gt=gts, refine=refine)
+    refs = [o[1] for o in out] or [pipe.refine_batch([], [], **refine)]
+    refined = {k: torch.cat([r[k] for r in refs]) for k in refs[0]}
+    res = _unrefined(dev, [o[0] for o in out], gt_of)
+    return (res if gt_of is not None else (res,)) + (refined,)
+
+
+def _unrefined(dev, out, gt_of):
+    """register_batches' entries -> register_chunks' result without refine"""
     poses = [p for o in out for p in (o if gt_of is None else o[0])]
     poses = torch.stack(poses) if poses else torch.zeros((0, 4, 4), dtype=torch.float32, device=dev)
     if gt_of is None:
@@ -89,14 +102,14 @@ def register_chunks(pipe, chunks, make, gt_of=None):
     return poses, counts
 
 
-def register_pairs(pipe, dataset, indices, batch, stage_metrics=False):
+def register_pairs(pipe, dataset, indices, batch, stage_metrics=False, refine=None):
     """This rank's share of the pairs through the device pipeline, `batch` pairs per chunk -> f32[k,4,4] (device), in the order of
     `indices`.  stage_metrics: also the per-stage metric rows against the data set's ground truth -> (poses, counts int32[k,7] on
-    the device); the poses are the same."""
+    the device); the poses are the same.  refine: register_chunks' -> (..., refined dict) with the unrefined results unchanged."""
     idx = list(indices)
     return register_chunks(pipe, [idx[lo:lo + batch] for lo in range(0, len(idx), batch)],
                            lambda ch: items_batched(dataset, ch, pipe.device),
-                           (lambda ch: [dataset.meta(i, pipe.device)['relt_pose'] for i in ch]) if stage_metrics else None)
+                           (lambda ch: [dataset.meta(i, pipe.device)['relt_pose'] for i in ch]) if stage_metrics else None, refine)
 
 
 # ---------------------------------------------------------------------------------------------------- scoring
@@ -138,9 +151,21 @@ def add_common_args(ap, driver_name, batch_default, log_root_default, preset_not
                          'and, with --stage-metrics, the stage figures per overlap band: summary key "by_overlap"')
 
 
+def add_refine_args(ap):
+    """--refine and its two settings: the dense refinement stage, the same on every driver (parse_with_preset adds them)"""
+    from .ops import ICP_METHODS
+    ap.add_argument('--refine', default=None, choices=sorted(ICP_METHODS),
+                    help='also refine every returned pose by dense ICP on the first-level clouds (BufferPipeline.refine_batch): summary '
+                         'key "refined" = the figures of the refined poses + mean fitness / inlier_rmse / iterations; every other key '
+                         'stays that of the unrefined poses')
+    ap.add_argument('--refine-dist', type=float, default=None, help='correspondence distance of --refine (default: the preset\'s dist_th)')
+    ap.add_argument('--refine-iters', type=int, default=30, help='most ICP iterations of --refine')
+
+
 def parse_with_preset(ap, argv, driver_name):
     """-> (args, Config of --preset); a preset of another data set is an argument error"""
     from .config import preset
+    add_refine_args(ap)
     a = ap.parse_args(argv)
     try:
         return a, preset(a.preset, driver_name)
@@ -159,6 +184,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     `calibrate_pairs` pairs by rank 0 and broadcast), this rank's shard through register_pairs, gather, and on rank 0 the report:
     summarize(poses) -> the driver's own figures, the common ones, --by-overlap under the driver's (rte, rre) thresholds and
     --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
+    --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
+    unrefined poses.
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
     from . import dist as bdist
     from .pipeline import BufferPipeline
@@ -176,15 +203,33 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
         pipe.limits = bdist.broadcast_limits(pipe.limits if rank == 0 else [0, 0, 0], device=cdev)
     ids = bdist.shard_indices(len(ds), rank, world)
     t0 = time.perf_counter()
-    res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics)
+    refine = None
+    if getattr(a, 'refine', None):
+        refine = dict(method=a.refine, max_dist=cfg.dist_th if a.refine_dist is None else a.refine_dist, max_iteration=a.refine_iters)
+    res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics, refine=refine)
+    refined = None
+    if refine is not None:
+        res, refined = (res[:-1] if a.stage_metrics else res[0]), res[-1]
     poses = bdist.gather_poses(ids, res[0] if a.stage_metrics else res, len(ds), device=cdev)
+    if refined is not None:
+        refined = bdist.gather_poses(ids, refined['poses'], len(ds), device=cdev, extra=torch.stack(
+            [refined['fitness'].float(), refined['inlier_rmse'].float(), refined['iterations'].float()], 1))
     counts = bdist.gather_counts(ids, res[1].to(cdev), len(ds), device=cdev).cpu().numpy() if a.stage_metrics else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     poses = poses.cpu().numpy()
     if rank == 0:
+        ref_out = None
+        if refined is not None:                              # first: a summarize() that writes logs leaves those of the unrefined poses
+            stats = refined[1].cpu().numpy().astype(np.float64)
+            ref_out = dict(summarize(refined[0].cpu().numpy()), method=a.refine, max_dist=refine['max_dist'],
+                           max_iteration=a.refine_iters, fitness=float(stats[:, 0].mean()) if len(stats) else 0.0,
+                           inlier_rmse=float(stats[:, 1].mean()) if len(stats) else 0.0,
+                           iterations=float(stats[:, 2].mean()) if len(stats) else 0.0)
         out = summarize(poses)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
+        if ref_out is not None:
+            out['refined'] = ref_out
         overlaps = None
         if a.by_overlap:
             from . import pairs

@@ -1,14 +1,18 @@
 """ICP on the device: the open3d `registration_icp` call that refines KITTI's odometry ground truth (KITTI/dataset.py:95-117:
-point-to-point, threshold 0.20 m, identity init, <= 200 iterations, relative fitness / RMSE 1e-6), and its point-to-plane form.
+point-to-point, threshold 0.20 m, identity init, <= 200 iterations, relative fitness / RMSE 1e-6), its point-to-plane form and
+Generalized ICP (plane-to-plane, Segal et al.; open3d's registration_generalized_icp).
 
 Per iteration: nearest target point inside the correspondence distance for every transformed source point (A2 cell grid:
 column 0 of the distance-sorted neighbour row of csrc/radius.hip), fitness = matched / source points,
 RMSE over the matches, then the update from the matches -- point-to-point: the rigid transform of the centred 3x3
-cross-covariance in fp64, SVD with the det correction; point-to-plane: open3d's 6x6 step -- composed onto the running transform.
+cross-covariance in fp64, SVD with the det correction; point-to-plane: open3d's 6x6 step; generalized: the 6x6 Gauss-Newton step of
+sum d^T (C(n_q) + R C(n_s) R^T)^-1 d with C(n) = I - (1 - epsilon) n n^T (include/buffer_hip.h, N2) -- composed onto the running
+transform.
 open3d's loop, restated; open3d itself is absent here (parity unpinned).
 
 icp_batched runs that loop for many pairs at once in csrc/icp.hip (buf_icp_batched): state, correspondences, sums and updates
-stay on the device; one int is read back every 8 rounds.  icp_point_to_point / icp_point_to_plane are its one-pair forms."""
+stay on the device; one int is read back every 8 rounds.  icp_point_to_point / icp_point_to_plane / icp_generalized are its one-pair
+forms."""
 import numpy as np
 import torch
 
@@ -16,10 +20,12 @@ from . import ops
 
 
 def icp_batched(srcs, tgts, max_dist, inits=None, method='point_to_point', tgt_normals=None, max_iteration=30,
-                relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False):
+                relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False, src_normals=None, epsilon=1e-3):
     """ICP of B pairs in one set of launches (csrc/icp.hip, buf_icp_batched): srcs / tgts lists of f32[n_b,3] / f32[m_b,3]
-    device tensors, inits None or B 4x4 transforms, method 'point_to_point' (Kabsch step) or
-    'point_to_plane' (open3d's step, restated, unpinned; needs tgt_normals, a list of f32[m_b,3]).
+    device tensors, inits None or B 4x4 transforms, method 'point_to_point' (Kabsch step),
+    'point_to_plane' (open3d's step, restated, unpinned; needs tgt_normals, a list of f32[m_b,3]) or 'generalized' (plane-to-plane;
+    needs tgt_normals and src_normals, a list of f32[n_b,3]; epsilon in (0, 1] is the covariance along a normal; a normal row that is
+    not a unit vector counts as no normal, C = I).
     -> list of B dicts: T (f64[4,4] numpy src->tgt), fitness, inlier_rmse, iterations, and correspondences (int32[k,2] numpy,
     pair-local (source row, target row), only with return_correspondences).  Each pair's result does not depend on the
     others of the batch; one small readback per 8 rounds."""
@@ -35,6 +41,14 @@ def icp_batched(srcs, tgts, max_dist, inits=None, method='point_to_point', tgt_n
             raise ValueError("icp_batched: point_to_plane needs tgt_normals (one f32[m,3] per target)")
         if len(tgt_normals) != B or any(tuple(n.shape) != tuple(t.shape) for n, t in zip(tgt_normals, tgts)):
             raise ValueError("icp_batched: tgt_normals must hold one [m,3] array per target, shaped like the target")
+    if method == 'generalized':
+        if src_normals is None or tgt_normals is None:
+            raise ValueError("icp_batched: generalized needs src_normals and tgt_normals (one f32[n,3] per cloud)")
+        for nrm, clouds, what in ((src_normals, srcs, 'src_normals'), (tgt_normals, tgts, 'tgt_normals')):
+            if len(nrm) != B or any(tuple(n.shape) != tuple(c.shape) for n, c in zip(nrm, clouds)):
+                raise ValueError(f"icp_batched: {what} must hold one [n,3] array per cloud, shaped like the cloud")
+        if not (0.0 < float(epsilon) <= 1.0):
+            raise ValueError(f"icp_batched: epsilon={epsilon} (must be in (0, 1])")
     if B == 0:
         return []
     if not all(isinstance(x, torch.Tensor) and x.is_cuda for x in list(srcs) + list(tgts)):
@@ -42,12 +56,14 @@ def icp_batched(srcs, tgts, max_dist, inits=None, method='point_to_point', tgt_n
     dev = srcs[0].device
     src = torch.cat([s.reshape(-1, 3).float() for s in srcs])
     tgt = torch.cat([t.reshape(-1, 3).float() for t in tgts])
-    nrm = torch.cat([n.reshape(-1, 3).float() for n in tgt_normals]) if method == 'point_to_plane' else None
+    nrm = torch.cat([n.reshape(-1, 3).float() for n in tgt_normals]) if method != 'point_to_point' else None
+    snrm = torch.cat([n.reshape(-1, 3).float() for n in src_normals]) if method == 'generalized' else None
     sl = np.array([s.shape[0] for s in srcs], np.int32)
     tl = np.array([t.shape[0] for t in tgts], np.int32)
     T0 = np.stack([np.eye(4) if inits is None else np.asarray(inits[b], np.float64).reshape(4, 4) for b in range(B)])
     T, fit, rmse, iters, nn = ops.icp_batched(src, sl, tgt, tl, max_dist, torch.from_numpy(T0).to(dev), method, nrm, max_iteration,
-                                              relative_fitness, relative_rmse, correspondences=return_correspondences)
+                                              relative_fitness, relative_rmse, correspondences=return_correspondences,
+                                              src_normals=snrm, epsilon=epsilon)
     T, fit, rmse, iters = T.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy()
     nn = nn.cpu().numpy() if nn is not None else None
     s_off, t_off = np.concatenate([[0], np.cumsum(sl)]), np.concatenate([[0], np.cumsum(tl)])
@@ -62,7 +78,8 @@ def icp_batched(srcs, tgts, max_dist, inits=None, method='point_to_point', tgt_n
     return out
 
 
-def _one_pair(src, tgt, max_dist, init, method, tgt_normals, max_iteration, relative_fitness, relative_rmse):
+def _one_pair(src, tgt, max_dist, init, method, tgt_normals, max_iteration, relative_fitness, relative_rmse, src_normals=None,
+              epsilon=1e-3):
     """icp_batched with one pair -> (T f64[4,4] numpy src->tgt, fitness, inlier_rmse, corr int32[k,2] numpy)."""
     if not (isinstance(src, torch.Tensor) and isinstance(tgt, torch.Tensor) and src.is_cuda and tgt.is_cuda):
         raise RuntimeError("icp: expected tensors in device memory (buffer_amd has no CPU path)")
@@ -70,7 +87,7 @@ def _one_pair(src, tgt, max_dist, init, method, tgt_normals, max_iteration, rela
         return (np.eye(4) if init is None else np.asarray(init, np.float64).copy()), 0.0, 0.0, np.zeros((0, 2), np.int32)
     r = icp_batched([src], [tgt], max_dist, None if init is None else [init], method,
                     None if tgt_normals is None else [tgt_normals], max_iteration, relative_fitness, relative_rmse,
-                    return_correspondences=True)[0]
+                    return_correspondences=True, src_normals=None if src_normals is None else [src_normals], epsilon=epsilon)[0]
     return r['T'], r['fitness'], r['inlier_rmse'], r['correspondences']
 
 
@@ -83,3 +100,12 @@ def icp_point_to_point(src, tgt, max_dist, init=None, max_iteration=30, relative
 def icp_point_to_plane(src, tgt, tgt_normals, max_dist, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
     """src f32[n,3], tgt / tgt_normals f32[m,3] (device) -> icp_point_to_point's return shape, point-to-plane step."""
     return _one_pair(src, tgt, max_dist, init, 'point_to_plane', tgt_normals, max_iteration, relative_fitness, relative_rmse)
+
+
+def icp_generalized(src, src_normals, tgt, tgt_normals, max_dist, init=None, max_iteration=30, relative_fitness=1e-6,
+                    relative_rmse=1e-6, epsilon=1e-3):
+    """src / src_normals f32[n,3], tgt / tgt_normals f32[m,3] (device) -> icp_point_to_point's return shape, Generalized ICP step."""
+    if not (0.0 < float(epsilon) <= 1.0):
+        raise ValueError(f"icp_generalized: epsilon={epsilon} (must be in (0, 1])")
+    return _one_pair(src, tgt, max_dist, init, 'generalized', tgt_normals, max_iteration, relative_fitness, relative_rmse, src_normals,
+                     epsilon)

@@ -525,14 +525,15 @@ def post_refine(T_init, src, tgt, thr=0.10, iters=20):
     return T, info
 
 
-ICP_METHODS = {'point_to_point': 0, 'point_to_plane': 1}     # BUF_ICP_POINT_TO_POINT / BUF_ICP_POINT_TO_PLANE
+ICP_METHODS = {'point_to_point': 0, 'point_to_plane': 1, 'generalized': 2}     # BUF_ICP_POINT_TO_POINT / _POINT_TO_PLANE / _GENERALIZED
 
 
 def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='point_to_point', tgt_normals=None, max_iteration=30,
-                relative_fitness=1e-6, relative_rmse=1e-6, correspondences=False):
+                relative_fitness=1e-6, relative_rmse=1e-6, correspondences=False, src_normals=None, epsilon=1e-3):
     """buf_icp_batched: ICP of the pairs stacked in src f32[sum src_lengths,3] / tgt f32[sum tgt_lengths,3] (pair b owns
     src_lengths[b] / tgt_lengths[b] consecutive rows), T_init f64[B,4,4] -> (T f64[B,4,4], fitness f64[B], rmse f64[B],
-    iterations int32[B], nn int32[sum src_lengths] or None: global target row per source point, sum tgt_lengths = no match)."""
+    iterations int32[B], nn int32[sum src_lengths] or None: global target row per source point, sum tgt_lengths = no match).
+    method 'generalized' goes to buf_gicp_batched with src_normals (shaped like src), tgt_normals and epsilon."""
     L = _lib.lib()
     src, tgt = _dev(src, torch.float32, "icp_batched.src"), _dev(tgt, torch.float32, "icp_batched.tgt")
     sl, tl = _host_i32(src_lengths), _host_i32(tgt_lengths)
@@ -547,9 +548,21 @@ def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='po
     nn = torch.empty((max(int(src.shape[0]), 1),), dtype=torch.int32, device=dev) if correspondences else None
     nbytes = max(L.buf_icp_ws_bytes(int(src.shape[0]), int(tgt.shape[0]), max(B, 1), m), 1)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(L.buf_icp_batched(_ptr(src), _hptr(sl), _ptr(tgt), _ptr(nrm), _hptr(tl), B, m, float(max_dist), _ptr(T_init),
-                            int(max_iteration), float(relative_fitness), float(relative_rmse), _ptr(T), _ptr(fit), _ptr(rmse),
-                            _ptr(iters), _ptr(nn), _ptr(ws), nbytes, _stream()), "buf_icp_batched")
+    if method == 'generalized':
+        if src_normals is None or nrm is None:
+            raise ValueError("icp_batched: method 'generalized' needs src_normals and tgt_normals")
+        if not (0.0 < float(epsilon) <= 1.0):
+            raise ValueError(f"icp_batched: epsilon={epsilon} (must be in (0, 1])")
+        snrm = _dev(src_normals, torch.float32, "icp_batched.src_normals")
+        if tuple(snrm.shape) != tuple(src.shape) or tuple(nrm.shape) != tuple(tgt.shape):
+            raise ValueError("icp_batched: src_normals / tgt_normals must be shaped like src / tgt")
+        check(L.buf_gicp_batched(_ptr(src), _ptr(snrm), _hptr(sl), _ptr(tgt), _ptr(nrm), _hptr(tl), B, float(max_dist), float(epsilon),
+                                 _ptr(T_init), int(max_iteration), float(relative_fitness), float(relative_rmse), _ptr(T), _ptr(fit),
+                                 _ptr(rmse), _ptr(iters), _ptr(nn), _ptr(ws), nbytes, _stream()), "buf_gicp_batched")
+    else:
+        check(L.buf_icp_batched(_ptr(src), _hptr(sl), _ptr(tgt), _ptr(nrm), _hptr(tl), B, m, float(max_dist), _ptr(T_init),
+                                int(max_iteration), float(relative_fitness), float(relative_rmse), _ptr(T), _ptr(fit), _ptr(rmse),
+                                _ptr(iters), _ptr(nn), _ptr(ws), nbytes, _stream()), "buf_icp_batched")
     return T, fit, rmse, iters, (nn[:int(src.shape[0])] if nn is not None else None)
 
 

@@ -90,7 +90,41 @@ class BufferPipeline:
         return res
 
     @torch.no_grad()
-    def register_batches(self, batches, seeds=None, metrics_gt=None, tau_kp=None, tau_match=None, dist_th=None):
+    def refine_batch(self, inps, poses, method='generalized', max_dist=None, max_iteration=30, epsilon=1e-3):
+        """Dense refinement of a batch's poses: ONE batched ICP call (icp.py / csrc/icp.hip, all pairs in one set of launches) on the
+        dense first-level clouds of inps (src_raw / tgt_raw), started from `poses` (B src -> tgt 4x4: what register_batch returned, a
+        list or a [B,4,4] tensor), which are converted to f64 on the device -- no pose passes through the host.
+        method: 'generalized' (plane-to-plane, epsilon = the covariance along a normal), 'point_to_plane' or 'point_to_point';
+        max_dist: the correspondence distance, cfg.dist_th unless given.  Normals come from ONE stacked
+        preprocess.estimate_normals(knn=30, orient=False, lengths=) call: of all 2B clouds (sources, then targets) for 'generalized', of
+        the B targets for 'point_to_plane', none for 'point_to_point'.
+        -> dict of device tensors: poses f32[B,4,4], fitness f64[B], inlier_rmse f64[B], iterations int32[B].
+        Host waits: the normal estimation's own round trips and ICP's one int per 8 rounds."""
+        from . import preprocess
+        if method not in ops.ICP_METHODS:
+            raise ValueError(f'refine_batch: unknown method {method!r} (one of {sorted(ops.ICP_METHODS)})')
+        dev, B = self.device, len(inps)
+        if isinstance(poses, (list, tuple)):
+            poses = torch.stack(list(poses)) if B else torch.zeros((0, 4, 4), device=dev)
+        T0 = poses.to(dev, torch.float64).reshape(B, 4, 4).contiguous()
+        if B == 0:
+            return dict(poses=torch.zeros((0, 4, 4), dtype=torch.float32, device=dev), fitness=torch.zeros(0, dtype=torch.float64, device=dev),
+                        inlier_rmse=torch.zeros(0, dtype=torch.float64, device=dev), iterations=torch.zeros(0, dtype=torch.int32, device=dev))
+        srcs, tgts = [i['src_raw'][:, :3] for i in inps], [i['tgt_raw'][:, :3] for i in inps]
+        sl, tl = np.array([s.shape[0] for s in srcs], np.int32), np.array([t.shape[0] for t in tgts], np.int32)
+        src, tgt = torch.cat(srcs).float().contiguous(), torch.cat(tgts).float().contiguous()
+        snrm = tnrm = None
+        if method == 'generalized':
+            nrm = preprocess.estimate_normals(torch.cat([src, tgt]), knn=30, orient=False, lengths=np.concatenate([sl, tl]))
+            snrm, tnrm = nrm[:src.shape[0]].contiguous(), nrm[src.shape[0]:].contiguous()
+        elif method == 'point_to_plane':
+            tnrm = preprocess.estimate_normals(tgt, knn=30, orient=False, lengths=tl)
+        T, fit, rmse, iters, _ = ops.icp_batched(src, sl, tgt, tl, float(self.cfg.dist_th if max_dist is None else max_dist), T0, method,
+                                                 tnrm, int(max_iteration), src_normals=snrm, epsilon=epsilon)
+        return dict(poses=T.float(), fitness=fit, inlier_rmse=rmse, iterations=iters)
+
+    @torch.no_grad()
+    def register_batches(self, batches, seeds=None, metrics_gt=None, tau_kp=None, tau_match=None, dist_th=None, refine=None):
         """A sequence of batches, software-pipelined over two HIP streams: the keypoint stage of batch i+1 (pyramid, point
         learner, FPS -- short kernels, FPS latency-bound on 2B of the 256 CUs) is enqueued on a high-priority side stream
         BEFORE the descriptor / matching stage of batch i goes onto the current stream, so it runs beside the chip-filling
@@ -100,7 +134,11 @@ class BufferPipeline:
         seeds: list of lists -> list of lists of poses.
         metrics_gt: one entry per batch, each the batch's ground-truth poses as in register_batch (or a callable returning them,
         evaluated when the batch is) -> list of (poses, counts int32[B,7] on the device) per batch; the metric kernel of a batch
-        follows its pose recovery on the current stream, so the two-stream overlap is as without it."""
+        follows its pose recovery on the current stream, so the two-stream overlap is as without it.
+        refine: None, or the keyword arguments of refine_batch (method, max_dist, max_iteration, epsilon) -> every list entry becomes
+        (the entry as without refine, refine_batch's dict for the batch): the refinement of batch i is enqueued on the current stream
+        after its pose recovery (and metric kernel), from the poses that entry holds.  The unrefined poses and the metric rows keep
+        their bits; ICP's readbacks block the enqueueing thread, so less of batch i+1 overlaps.  None: no launch, nothing allocated."""
         dev = self.device
         main = torch.cuda.current_stream(dev)
         if not hasattr(self, '_kp_stream'):
@@ -137,7 +175,10 @@ class BufferPipeline:
             # the next batch's keypoint stage goes out NOW: its host round trip (per-cloud candidate counts) waits on the
             # side stream only, while the current stream is busy with the kernels queued above
             nxt = stage1(i + 1) if i + 1 < len(batches) else None
-            out.append(self._match(st))
+            res = self._match(st)
+            if refine is not None:
+                res = (res, self.refine_batch(st['inps'], res if metrics_gt is None else res[0], **refine))
+            out.append(res)
         self.check_range()
         return out
 

@@ -15,6 +15,15 @@ class TransformationEstimationPointToPlane:
         self.kernel = None
 
 
+class TransformationEstimationForGeneralizedICP:
+    """Generalized ICP step (plane-to-plane; csrc/icp.hip, restated, unpinned): covariances I - (1 - epsilon) n n^T from the normals."""
+
+    def __init__(self, epsilon=1e-3, kernel=None):
+        if kernel is not None:
+            raise NotImplementedError("open3d stand-in: robust kernels other than L2 are not provided")
+        self.epsilon, self.kernel = float(epsilon), None
+
+
 class CorrespondenceCheckerBasedOnEdgeLength:
     def __init__(self, similarity_threshold=0.9):
         self.similarity_threshold = float(similarity_threshold)
@@ -112,6 +121,31 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     T, fit, rmse, corr = run(*(torch.from_numpy(np.asarray(c, np.float32)).to(dev) for c in clouds), float(max_correspondence_distance),
                              np.eye(4) if init is None else np.asarray(init, np.float64),
                              cr.max_iteration, cr.relative_fitness, cr.relative_rmse)
+    return RegistrationResult(T, fit, rmse, corr)
+
+
+def registration_generalized_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
+    """Generalized ICP on the device (buffer_amd/icp.py icp_generalized).  A cloud without normals gets them from a copy's
+    estimate_normals() (30-NN) first, as open3d estimates a cloud's covariances itself; the clouds passed in are left as they are.
+    inlier_rmse is Euclidean, as for registration_icp (open3d reports the Mahalanobis residual here)."""
+    import torch
+    from buffer_amd import icp
+    from ..geometry import PointCloud
+    est = estimation_method or TransformationEstimationForGeneralizedICP()
+    if not isinstance(est, TransformationEstimationForGeneralizedICP):
+        raise TypeError("open3d stand-in: registration_generalized_icp takes a TransformationEstimationForGeneralizedICP")
+    cr = criteria or ICPConvergenceCriteria()
+    dev = _device()
+    clouds = []
+    for pcd in (source, target):
+        if not pcd.has_normals() and len(pcd.points) > 0:
+            pcd = PointCloud(pcd.points)
+            pcd.estimate_normals()
+        clouds += [pcd.points, pcd.normals]
+    T, fit, rmse, corr = icp.icp_generalized(*(torch.from_numpy(np.asarray(c, np.float32).reshape(-1, 3)).to(dev) for c in clouds),
+                                             float(max_correspondence_distance),
+                                             np.eye(4) if init is None else np.asarray(init, np.float64),
+                                             cr.max_iteration, cr.relative_fitness, cr.relative_rmse, est.epsilon)
     return RegistrationResult(T, fit, rmse, corr)
 
 

@@ -460,27 +460,41 @@ int     buf_knn_normals(const float* pts, int ns, const int* qidx, int nq, const
 /* N2  ICP (KITTI/dataset.py:95-117 open3d registration_icp; open3d 0.13.0 restated, parity unpinned): B pairs per call.
  * src f32[sum src_lengths_host,3] and tgt f32[sum tgt_lengths_host,3] stack the pairs' clouds (pair b owns src_lengths_host[b]
  * / tgt_lengths_host[b] consecutive rows); tgt_normals f32[*,3] (nullable for point-to-point); T_init_f64 f64[B,4,4] (device).
+ * buf_icp_batched takes methods 0 and 1; buf_gicp_batched is method 2 with its two further arguments, src_normals f32[*,3] and epsilon.
  * method BUF_ICP_POINT_TO_POINT: rigid update = Kabsch with the det correction of the centred cross-covariance (fp64);
  * method BUF_ICP_POINT_TO_PLANE: J^T J x = -J^T r (J = [p x n, n], r = (p - q) . n, absolute coordinates, fp64 Cholesky),
  *   dT = [Rz(x2) Ry(x1) Rx(x0) | x3..5] (open3d TransformVector6dToMatrix4d, restated, unpinned).
+ * method BUF_ICP_GENERALIZED (plane-to-plane, Segal et al.; open3d registration_generalized_icp restated, unpinned): per match, in
+ *   fp64, d = p - q, S = C(n_q) + R C(n_s) R^T with C(n) = I - (1 - epsilon) n n^T (R = the rotation block of the running T), M = S^-1
+ *   (symmetric 3x3, by cofactors), J = [-[p]x | I]; H = sum J^T M J, g = sum J^T M d, H x = -g by the point-to-plane Cholesky and the
+ *   same dT.  A normal row counts if | |n|^2 - 1 | < 1e-3 in fp64 (which a non-finite component fails); any other row is taken as
+ *   zero, C = I: clouds without usable normals take isotropic (point-to-point Gauss-Newton) steps.  epsilon = 1 does the same.
+ *   inlier_rmse stays Euclidean (open3d reports the Mahalanobis residual): the three methods share fitness, rmse and stopping rules.
  * Correspondence of a source point: p = T s in fp64, rounded to fp32; the nearest target point of its pair with fp32 d2 < max_dist^2
  * (buf_grid_query's arithmetic, ties to the lowest index = column 0 of the buf_grid_query row); non-finite points never match.
  * Per pair: fitness = matches / source points, rmse = sqrt(sum d2 / matches) (0 without matches), d2 Euclidean in fp64.
  * The loop of buffer_amd/icp.py::icp_point_to_point: the iteration count is the number of updates applied; a pair stops before an
- * update with fewer than 3 (point-to-point) / 6 (point-to-plane) matches or a system that is not positive definite (T unchanged),
+ * update with fewer than 3 (point-to-point) / 6 (point-to-plane, generalized) matches or a system that is not positive definite (T unchanged),
  * after an update when |d fitness| < rel_fitness and |d rmse| < rel_rmse, and after max_iteration updates.  T_out f64[B,4,4],
  * fitness_out / rmse_out f64[B] and iters_out int32[B] (device) belong to the last correspondence pass, as does nn_out
  * (nullable, int32[sum src_lengths]: global target row of every source point, sum tgt_lengths_host = no match).  An empty pair
  * returns T_init, fitness 0, 0 iterations.  Results are bitwise reproducible and independent of the other pairs of the batch.
  * Synchronises: one int is read back after every 8th round (at most ceil((max_iteration + 1) / 8) readbacks).
- * BUF_EINVAL before any device work for max_dist <= 0 or not finite, point-to-plane without normals, negative lengths. */
+ * BUF_EINVAL before any device work for max_dist <= 0 or not finite, point-to-plane without normals, negative lengths, a method
+ * other than 0 / 1 in buf_icp_batched (it has no source normals: method 2 is buf_gicp_batched), and in buf_gicp_batched a null normal
+ * array or an epsilon outside (0, 1] or not finite.  buf_icp_ws_bytes takes all three methods. */
 #define BUF_ICP_POINT_TO_POINT 0
 #define BUF_ICP_POINT_TO_PLANE 1
+#define BUF_ICP_GENERALIZED 2
 size_t  buf_icp_ws_bytes(int n_src_total, int n_tgt_total, int npairs, int method);
 int     buf_icp_batched(const float* src, const int* src_lengths_host, const float* tgt, const float* tgt_normals,
                         const int* tgt_lengths_host, int npairs, int method, float max_dist, const double* T_init_f64,
                         int max_iteration, double rel_fitness, double rel_rmse, double* T_out_f64, double* fitness_out,
                         double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream);
+int     buf_gicp_batched(const float* src, const float* src_normals, const int* src_lengths_host, const float* tgt,
+                         const float* tgt_normals, const int* tgt_lengths_host, int npairs, float max_dist, double epsilon,
+                         const double* T_init_f64, int max_iteration, double rel_fitness, double rel_rmse, double* T_out_f64,
+                         double* fitness_out, double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream);
 
 /* N4  Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
  * information matrix of a pair are made of; the evaluation half of an ICP round without the loop).

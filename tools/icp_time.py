@@ -2,7 +2,9 @@
 kitti.KittiTestSet refines its ground truth (0.20 m, <= 200 iterations, relative criteria 1e-6): icp.icp_batched at batch 1
 (one pair per call, as icp.icp_point_to_point runs it) and at batch --pairs.  The source scan starts from the true pose
 perturbed by a small error (odometry is close, not exact).  Times are HIP-event spans after a warm-up of every path.
-Prints one JSON line:  python tools/icp_time.py [--pairs 16]"""
+--method point_to_plane / generalized: the same runs with that step; the 30-NN normals they need (targets / all scans, ONE stacked
+preprocess.estimate_normals call) are timed as a span of their own, normals_ms, outside the ICP spans.
+Prints one JSON line:  python tools/icp_time.py [--pairs 16] [--method point_to_point]"""
 import argparse
 import json
 import os
@@ -12,7 +14,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from buffer_amd import icp, synth  # noqa: E402
+from buffer_amd import icp, ops, preprocess, synth  # noqa: E402
 
 
 def _span(fn):
@@ -30,6 +32,8 @@ def main():
     ap.add_argument('--pairs', type=int, default=16)
     ap.add_argument('--max-iteration', type=int, default=200)
     ap.add_argument('--dist', type=float, default=0.20)
+    ap.add_argument('--method', default='point_to_point', choices=sorted(ops.ICP_METHODS))
+    ap.add_argument('--epsilon', type=float, default=1e-3, help='generalized: the covariance along a normal')
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     rng = np.random.default_rng(0)
@@ -45,20 +49,39 @@ def main():
         xyz0 = s['src_raw'] @ M[:3, :3].T + M[:3, 3]
         srcs.append(torch.from_numpy(xyz0.astype(np.float32)).to(dev))
         tgts.append(torch.from_numpy(s['tgt_raw'].astype(np.float32)).to(dev))
-    kw = dict(max_iteration=a.max_iteration)
+    def normals(clouds):
+        """one stacked estimate_normals call -> one array per cloud"""
+        n = [c.shape[0] for c in clouds]
+        return list(torch.split(preprocess.estimate_normals(torch.cat(clouds), knn=30, orient=False, lengths=n), n))
+
+    need = dict(point_to_point=[], point_to_plane=tgts, generalized=srcs + tgts)[a.method]
+    nrm, t_normals = [], 0.0
+    if need:
+        normals(need)                                                        # warm-up
+        nrm, t_normals = _span(lambda: normals(need))
+
+    def extra(lo, hi):
+        """the method's arguments for pairs lo..hi-1"""
+        if a.method == 'point_to_plane':
+            return dict(tgt_normals=nrm[lo:hi])
+        if a.method == 'generalized':
+            return dict(src_normals=nrm[lo:hi], tgt_normals=nrm[len(srcs) + lo:len(srcs) + hi], epsilon=a.epsilon)
+        return {}
+
+    kw = dict(method=a.method, max_iteration=a.max_iteration)
     # warm-up of both paths (code objects, allocator)
-    icp.icp_batched(srcs[:1], tgts[:1], a.dist, max_iteration=3)
-    icp.icp_batched(srcs, tgts, a.dist, max_iteration=3)
+    icp.icp_batched(srcs[:1], tgts[:1], a.dist, **dict(kw, max_iteration=3), **extra(0, 1))
+    icp.icp_batched(srcs, tgts, a.dist, **dict(kw, max_iteration=3), **extra(0, len(srcs)))
 
     one, t_one = [], 0.0
-    for s, t in zip(srcs, tgts):
-        r, ms = _span(lambda: icp.icp_batched([s], [t], a.dist, **kw)[0])
+    for b, (s, t) in enumerate(zip(srcs, tgts)):
+        r, ms = _span(lambda: icp.icp_batched([s], [t], a.dist, **kw, **extra(b, b + 1))[0])
         one.append(r); t_one += ms
-    batch, t_batch = _span(lambda: icp.icp_batched(srcs, tgts, a.dist, **kw))
+    batch, t_batch = _span(lambda: icp.icp_batched(srcs, tgts, a.dist, **kw, **extra(0, len(srcs))))
     it1, itb = [r['iterations'] for r in one], [r['iterations'] for r in batch]
     B = len(srcs)
     print(json.dumps(dict(
-        pairs=B, points_per_scan=int(np.mean([s.shape[0] for s in srcs])), max_dist=a.dist, max_iteration=a.max_iteration,
+        method=a.method, normals_ms=t_normals, pairs=B, points_per_scan=int(np.mean([s.shape[0] for s in srcs])), max_dist=a.dist, max_iteration=a.max_iteration,
         batch1_ms_per_pair=t_one / B, batch1_ms_per_iteration=t_one / max(sum(it1), 1),
         batched_ms_per_pair=t_batch / B, batched_ms_per_pair_iteration=t_batch / max(sum(itb), 1),
         batched_rounds=max(itb) + 1, iterations_batched=itb,
