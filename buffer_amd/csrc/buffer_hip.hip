@@ -5,6 +5,7 @@
 #include "radius.hip"
 #include "icp.hip"
 #include "pairstats.hip"
+#include "posegraph.hip"
 #include "metrics.hip"
 #include "subsample.hip"
 #include "pointops.hip"

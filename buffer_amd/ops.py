@@ -594,6 +594,50 @@ def pair_stats(points, lengths, pair_src, pair_tgt, T, radius, correspondences=F
     return matched, moments, (nn[:rows] if nn is not None else None)
 
 
+PG_MAX_NODES = 128                                                                             # BUF_PG_MAX_NODES
+PG_STATUS = ('NOTHING', 'CONVERGED_STEP', 'CONVERGED_COST', 'MAX_ITER', 'STALLED', 'FAILED')   # BUF_PG_* of buffer_hip.h
+PG_TICK_HZ = 1e8                                                                               # wall_clock64: a constant 100 MHz
+
+
+def pose_graph_optimize(nodes, edges, edge_i, edge_j, Z, info, uncertain, fixed, mu, X_init, max_iterations=100, eps_step=1e-9,
+                        eps_cost=1e-10, tau0=1e-5, want_ticks=False):
+    """buf_pose_graph_optimize: G pose graphs in one launch, nothing read back.  nodes / edges host int[G] (graph g owns nodes[g]
+    consecutive poses and edges[g] consecutive edges), edge_i / edge_j host int[E] (graph-local node ids), Z f64[E,4,4] and info
+    f64[E,6,6] (device), uncertain host u8[E], fixed host int[G], mu host f64[G], X_init f64[N,4,4] (device)
+    -> (X f64[N,4,4], status int32[G,3] = (index into PG_STATUS, solves, accepted), cost f64[G,2] = (initial, final),
+    edge f64[E,2] = (l_e, q_e) at X), all on the device; with want_ticks also int64[G,4]: the kernel's own 100 MHz tick counts of
+    (everything after the input check, factorisations, substitutions, linearisations + assemblies) per graph."""
+    L = _lib.lib()
+    nd, ed, fx = _host_i32(nodes), _host_i32(edges), _host_i32(fixed)
+    ei, ej = _host_i32(edge_i), _host_i32(edge_j)
+    un = np.ascontiguousarray(uncertain, dtype=np.uint8).reshape(-1)
+    mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)
+    G = int(nd.shape[0])
+    if not (ed.shape[0] == G and fx.shape[0] == G and mu.shape[0] == G):
+        raise ValueError(f"pose_graph_optimize: {G} graphs but {ed.shape[0]} edge counts, {fx.shape[0]} fixed nodes, {mu.shape[0]} weights")
+    if (nd < 0).any() or (ed < 0).any():
+        raise ValueError("pose_graph_optimize: negative node or edge count")
+    N, E = int(nd.astype(np.int64).sum()), int(ed.astype(np.int64).sum())
+    if not (ei.shape[0] == E and ej.shape[0] == E and un.shape[0] == E):
+        raise ValueError(f"pose_graph_optimize: {E} edges but {ei.shape[0]} / {ej.shape[0]} node ids, {un.shape[0]} flags")
+    X_init = _dev(X_init, torch.float64, "pose_graph_optimize.X_init").reshape(N, 4, 4)
+    dev = X_init.device
+    Z = _dev(Z, torch.float64, "pose_graph_optimize.Z").reshape(E, 4, 4)
+    info = _dev(info, torch.float64, "pose_graph_optimize.info").reshape(E, 6, 6)
+    X = torch.empty((N, 4, 4), dtype=torch.float64, device=dev)
+    status = torch.zeros((G, 3), dtype=torch.int32, device=dev)
+    cost = torch.zeros((G, 2), dtype=torch.float64, device=dev)
+    edge = torch.zeros((E, 2), dtype=torch.float64, device=dev)
+    nbytes = max(L.buf_pose_graph_ws_bytes(max(G, 1), N, E, min(int(nd.max()) if G else 0, PG_MAX_NODES)), 1)
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_pose_graph_optimize(_hptr(nd), _hptr(ed), G, _hptr(ei), _hptr(ej), _ptr(Z), _ptr(info), _hptr(un), _hptr(fx), _hptr(mu),
+                                    _ptr(X_init), int(max_iterations), float(eps_step), float(eps_cost), float(tau0), _ptr(X), _ptr(status),
+                                    _ptr(cost), _ptr(edge), _ptr(ws), nbytes, _stream()), "buf_pose_graph_optimize")
+    if want_ticks:
+        return X, status, cost, edge, ws[:32 * G].view(torch.int64).reshape(G, 4).clone()
+    return X, status, cost, edge
+
+
 METRIC_COLUMNS = ('rep_src', 'rep_tgt', 'nn_inl', 'mutual', 'mutual_inl', 'cons', 'cons_true')      # BUF_METRICS_* of buffer_hip.h
 
 

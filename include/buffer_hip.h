@@ -556,6 +556,61 @@ int     buf_match_metrics(const float* kp, const int* s_nn, const int* t_nn, int
                           const float* T_est_f32, float tau_kp, float tau_match, float dist_th, int* out_counts,
                           float* out_nn_d2 /* nullable */, void* stream);
 
+/* N5  Pose-graph optimisation with line processes (the multiway registration of Choi, Zhou, Koltun 2015, restated here in full: no
+ * library's conventions are pinned), G graphs per call, ONE launch, nothing read back, all arithmetic fp64 without FMA.
+ * Graph g owns nodes_host[g] consecutive rows of X_init_f64 / X_out_f64 (f64[N_total,4,4], device) and edges_host[g] consecutive
+ * edges: edge_i_host / edge_j_host (graph-local node ids), Z_f64 f64[E,4,4] and info_f64 f64[E,6,6] (device), uncertain_host u8[E];
+ * fixed_host[g] = the node that keeps its pose, mu_host[g] = the line-process weight (0 = line process off).  X_out must not
+ * overlap X_init.
+ * Model.  Node pose X_k = (R_k, p_k) maps fragment k into the world.  Edge e = (i, j, Z, L, u): Z maps fragment j into fragment i (the
+ *   gt.log convention, T_ij = inv(W_i) W_j).  E = Z^-1 X_i^-1 X_j, rigid inverses formed as [R^T, -R^T t]; residual r = [phi; tau],
+ *   phi = Log(R_E), tau = t_E.  Log goes through the quaternion of R_E (Shepperd's branch on the largest of w, x, y, z; w made >= 0)
+ *   and phi = 2 atan2(|v|, w) v / |v| (2 v where |v| = 0): a few ulp on all of [0, pi].  L is the symmetric 6x6 information matrix in the
+ *   order [rotation, translation] (the 'open3d' convention of pairs.information_matrix over the matched points of fragment j in j's
+ *   frame); q = r^T L r.
+ * Line process.  An uncertain edge of a graph with mu > 0 has l = (mu / (mu + q))^2 and the cost term mu q / (mu + q)
+ *   (= l q + mu (sqrt(l) - 1)^2); every other edge has l = 1 and the cost term q.  F = the sum of the cost terms.
+ * Jacobians, for the update X_k <- X_k (Exp(a_k), b_k), i.e. R <- R Exp(a), p <- p + R b; Exp(a) = I + (sin t / t) [a]x +
+ *   ((sin(t/2) / (t/2))^2 / 2) [a]x^2, t = |a|.  With M = X_j^-1 X_i = (R_M, p_M), P = [phi]x and Jri = I + P/2 + P^2/12 (the series
+ *   is cut there: part of the contract):
+ *     J_i = [[-Jri R_M, 0], [-R_E [p_M]x R_M, -R_E R_M]]        J_j = [[Jri, 0], [0, R_E]]
+ * Normal equations.  H = sum l_e J^T L J, g = sum l_e J^T L r with l_e frozen at the linearisation point (IRLS); the six rows and
+ *   columns of the fixed node are removed.
+ * Loop (Levenberg-Marquardt, Nielsen's damping).  lambda0 = tau0 * max diag H; a graph without a free node, without an edge or with
+ *   lambda0 not > 0 returns X_init with status NOTHING.  lambda = lambda0, nu = 2.  Every solve factors H + lambda I by Cholesky and
+ *   sets delta = -(H + lambda I)^-1 g; a pivot that is not positive and finite makes the solve a rejected one.  max |delta| <=
+ *   eps_step stops with CONVERGED_STEP, delta not applied.  Otherwise X' = X (Exp(a), b) per free node, F' = the cost at X' and
+ *   rho = (F - F') / (delta^T (lambda delta - g)).  Accepted when rho > 0 and F' is finite: X <- X', lambda <- lambda * max(1/3,
+ *   1 - (2 rho - 1)^3), nu <- 2, and F - F' <= eps_cost * F (the F before the step) stops with CONVERGED_COST.  Otherwise rejected:
+ *   lambda <- lambda nu, nu <- 2 nu, and lambda > 1e30 * lambda0 stops with STALLED.  max_iterations counts solves; using them up
+ *   gives MAX_ITER (max_iterations == 0: the costs and the edge outputs at X_init).  A graph with a non-finite value in its Z, info
+ *   or X_init returns X_init with status FAILED, NaN costs and NaN edge outputs, and does not disturb the other graphs of the call.
+ * Outputs (device).  X_out f64[N_total,4,4]; status_out int32[G,3] = status (BUF_PG_*), solves, accepted steps; cost_out f64[G,2] =
+ *   F at X_init, F at X_out; edge_out f64[E,2] = (l_e, q_e) at X_out.
+ * Shape on the device.  One workgroup per graph runs the whole loop.  Its threads linearise one edge each into a per-edge record;
+ *   every node row of H and g is then gathered over the node's incident edges in ascending edge order; H is a dense square of
+ *   6 (n - 1) in the workspace, factored by a blocked Cholesky with an LDS panel; every sum is a fixed-shape tree.  No float atomics:
+ *   a graph's results are the same bits alone, in any batch, in any graph order and across runs.  At most BUF_PG_MAX_NODES nodes per
+ *   graph: more gives BUF_ECAPACITY before any device work.
+ * BUF_EINVAL before any device work for negative counts, an edge index outside its graph, i == j, fixed outside its graph, mu < 0
+ * or not finite, eps_step / eps_cost / tau0 not finite and > 0, max_iterations < 0, and a null required pointer with work to do.
+ * ngraphs == 0 succeeds and touches nothing.  buf_pose_graph_ws_bytes: max_nodes = the largest graph of the call (0 bytes for a
+ * negative count, ngraphs == 0 or max_nodes above the capacity). */
+#define BUF_PG_MAX_NODES        128
+#define BUF_PG_NOTHING          0
+#define BUF_PG_CONVERGED_STEP   1
+#define BUF_PG_CONVERGED_COST   2
+#define BUF_PG_MAX_ITER         3
+#define BUF_PG_STALLED          4
+#define BUF_PG_FAILED           5
+size_t  buf_pose_graph_ws_bytes(int ngraphs, int nodes_total, int edges_total, int max_nodes);
+int     buf_pose_graph_optimize(const int* nodes_host, const int* edges_host, int ngraphs, const int* edge_i_host,
+                                const int* edge_j_host, const double* Z_f64, const double* info_f64,
+                                const unsigned char* uncertain_host, const int* fixed_host, const double* mu_host,
+                                const double* X_init_f64, int max_iterations, double eps_step, double eps_cost, double tau0,
+                                double* X_out_f64, int* status_out, double* cost_out, double* edge_out, void* ws, size_t ws_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
