@@ -378,7 +378,7 @@ extern "C" int buf_vn_gather_block(const float* q_pts, const float* s_pts, const
     BUF_REQUIRE(mode != 6 || cin == 1, BUF_EINVAL, "buf_vn_gather_block: mode '6' needs one input vector channel");
     BUF_REQUIRE(scale != 0.f, BUF_EINVAL, "buf_vn_gather_block: scale == 0");
     if (nq == 0) return BUF_OK;
-    BUF_REQUIRE(q_pts && s_pts && feats && idx && wf && wd && out, BUF_EINVAL, "buf_vn_gather_block: null argument");
+    BUF_REQUIRE(q_pts && idx && wf && wd && out && (ns == 0 || (s_pts && feats)), BUF_EINVAL, "buf_vn_gather_block: null argument");      // (ns == 0: every slot is a shadow, no support row is read)
     int cinp = cin + (mode == 6 ? 3 : 1);
     size_t lds = sizeof(float) * 2 * (size_t)cout * cinp;
     long long total = (long long)nq * cout;
@@ -401,6 +401,18 @@ extern "C" int buf_vn_gather_block(const float* q_pts, const float* s_pts, const
 // mode '1' through the hoisted contraction; ws: f32[ns * 6 * cout] (buf_vn_gather_pre_ws_bytes)
 extern "C" size_t buf_vn_gather_pre_ws_bytes(int ns, int cout) { return sizeof(float) * 6 * (size_t)(ns > 0 ? ns : 1) * (size_t)(cout > 0 ? cout : 1); }
 
+// LDS of the two launches of the hoisted form: both weight matrices (k_vn_linear_pre) and the [VG6_PTS][k] slot stage (k_vn_gather_pre)
+static size_t vn_pre_weight_lds(int cin, int cout) { return sizeof(float) * 2 * (size_t)cout * ((size_t)cin + 1); }
+static size_t vn_pre_stage_lds(int k) { return sizeof(float4) * (size_t)VG6_PTS * (size_t)k; }
+
+// 1: buf_vn_gather_block_pre takes these sizes (each stage within the 48 KiB of LDS a launch gets without opting in); 0: the caller
+// runs mode '1' on buf_vn_gather_block, which has no limit on k
+extern "C" int buf_vn_gather_pre_supported(int k, int cin, int cout)
+{
+    if (k <= 0 || cin <= 0 || cout <= 0) return 0;
+    return vn_pre_weight_lds(cin, cout) <= 48 * 1024 && vn_pre_stage_lds(k) <= 48 * 1024 ? 1 : 0;
+}
+
 extern "C" int buf_vn_gather_block_pre(const float* q_pts, const float* s_pts, const float* feats, const int* idx,
                                        int nq, int ns, int k, int cin, int cout, float scale,
                                        const float* wf, const float* wd, const float* bn_scale, const float* bn_shift,
@@ -409,18 +421,19 @@ extern "C" int buf_vn_gather_block_pre(const float* q_pts, const float* s_pts, c
     BUF_REQUIRE(nq >= 0 && ns >= 0 && k > 0 && cin > 0 && cout > 0, BUF_EINVAL, "buf_vn_gather_block_pre: bad sizes");
     BUF_REQUIRE(scale != 0.f, BUF_EINVAL, "buf_vn_gather_block_pre: scale == 0");
     if (nq == 0) return BUF_OK;
-    BUF_REQUIRE(q_pts && s_pts && feats && idx && wf && wd && out, BUF_EINVAL, "buf_vn_gather_block_pre: null argument");
+    BUF_REQUIRE(q_pts && idx && wf && wd && out && (ns == 0 || (s_pts && feats)), BUF_EINVAL, "buf_vn_gather_block_pre: null argument");      // (ns == 0: every slot is a shadow, no support row is read)
     BUF_REQUIRE(ws && ws_bytes >= buf_vn_gather_pre_ws_bytes(ns, cout), BUF_EWORKSPACE, "buf_vn_gather_block_pre: workspace of %zu bytes, need %zu",
                 ws_bytes, buf_vn_gather_pre_ws_bytes(ns, cout));
-    const size_t lds = sizeof(float) * 2 * (size_t)cout * (cin + 1);
+    // both LDS checks come before the first launch: a refused call leaves nothing queued
+    const size_t lds = vn_pre_weight_lds(cin, cout);
     BUF_REQUIRE(lds <= 48 * 1024, BUF_EINVAL, "buf_vn_gather_block_pre: weights of %zu bytes exceed the 48 KiB of LDS a launch gets without opting in", lds);
+    const size_t lds_g = vn_pre_stage_lds(k);
+    BUF_REQUIRE(lds_g <= 48 * 1024, BUF_EINVAL, "buf_vn_gather_block_pre: k=%d too large for the LDS stage", k);
     const VnParams P = make_params(wf, wd, bn_scale, bn_shift, slope);
     TimedSpan span;
     bool timed = timing_begin((hipStream_t)stream, &span, 4.0 * nq * k + 12.0 * nq + 12.0 * nq * cin + 12.0 * nq * cout, BUF_TIMED_VN_GATHER);
     if (ns > 0)
         k_vn_linear_pre<<<cdiv((long long)ns * 2 * cout, 256), 256, lds, (hipStream_t)stream>>>(feats, ns, cin, cout, P, (float*)ws);
-    const size_t lds_g = sizeof(float4) * (size_t)VG6_PTS * k;
-    BUF_REQUIRE(lds_g <= 48 * 1024, BUF_EINVAL, "buf_vn_gather_block_pre: k=%d too large for the LDS stage", k);
     k_vn_gather_pre<<<cdiv(nq, VG6_PTS), 256, lds_g, (hipStream_t)stream>>>(q_pts, s_pts, (const float*)ws, idx, nq, ns, k, cin, cout, scale, P, out);
     if (timed) timing_end((hipStream_t)stream, &span);
     BUF_LAUNCH_CHECK();

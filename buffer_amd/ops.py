@@ -343,8 +343,9 @@ def vn_gather_block(layer, q_pts, s_pts, feats, idx, mode, scale=1.0):
     ns = s_pts.shape[0]
     cin = feats.shape[1] // 3
     out = torch.empty((nq, 3 * layer.cout), dtype=torch.float32, device=feats.device)
-    if int(mode) == 1 and not os.environ.get('BUF_VN_GATHER_DIRECT'):
-        # the channel contraction once per support point instead of once per neighbour slot (csrc/vn.hip, round 4)
+    if int(mode) == 1 and not os.environ.get('BUF_VN_GATHER_DIRECT') and L.buf_vn_gather_pre_supported(k, cin, layer.cout):
+        # the channel contraction once per support point instead of once per neighbour slot (csrc/vn.hip, round 4); a neighbour
+        # limit past its LDS stage (k > 96) runs on the direct kernel below, which takes any k
         wsb = L.buf_vn_gather_pre_ws_bytes(ns, layer.cout)
         ws = torch.empty((wsb,), dtype=torch.uint8, device=feats.device)
         PF_BYTES[0] += 48.0 * layer.cout * ns               # PF[j] = [Wf f_j | Wd f_j]: 2 * cout vectors of 12 B per support row, written once and read back

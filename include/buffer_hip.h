@@ -213,7 +213,11 @@ int     buf_vn_gather_block(const float* q_pts, const float* s_pts, const float*
                             float slope, float* out, void* stream);
 /* The same for mode '1' with the channel contraction hoisted out of the neighbour loop (csrc/vn.hip: the feature part of both
  * VN-linear maps is formed once per SUPPORT point, a neighbour slot adds the delta column): 4-5 x fewer operations in the resnet
- * blocks, results within half an ulp of a partial sum of buf_vn_gather_block.  ws: buf_vn_gather_pre_ws_bytes(ns, cout) bytes. */
+ * blocks, results within half an ulp of a partial sum of buf_vn_gather_block.  ws: buf_vn_gather_pre_ws_bytes(ns, cout) bytes.
+ * buf_vn_gather_pre_supported: 1 when the slot stage (16 * 32 * k bytes: k <= 96) and the weight stage (8 * cout * (cin + 1) bytes)
+ * each fit the 48 KiB of LDS of a launch, else 0: buf_vn_gather_block_pre then returns BUF_EINVAL with nothing launched, and mode 1
+ * of buf_vn_gather_block (any k) is the path to take. */
+int     buf_vn_gather_pre_supported(int k, int cin, int cout);
 size_t  buf_vn_gather_pre_ws_bytes(int ns, int cout);
 int     buf_vn_gather_block_pre(const float* q_pts, const float* s_pts, const float* feats, const int* idx,
                                 int nq, int ns, int k, int cin, int cout, float scale,
