@@ -110,6 +110,8 @@ _SIGNATURES = {
     "buf_pose_graph_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "buf_pose_graph_optimize": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double,
                                      _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "buf_fpfh_ws_bytes": (_sz, [_i]),
+    "buf_fpfh": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "buf_match_metrics": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "buf_row_linear": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "buf_segment_instance_norm_ws_bytes": (_sz, [_i, _i]),

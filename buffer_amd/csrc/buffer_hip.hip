@@ -27,3 +27,4 @@
 #include "convnet_w24k.hip"
 #include "costnet.hip"
 #include "split_safe.hip"
+#include "fpfh.hip"

@@ -162,11 +162,22 @@ def add_refine_args(ap):
     ap.add_argument('--refine-iters', type=int, default=30, help='most ICP iterations of --refine')
 
 
+def add_descriptor_args(ap):
+    """--descriptor: the learned path or the classical baseline, the same on every driver (parse_with_preset adds it)"""
+    ap.add_argument('--descriptor', default='buffer', choices=('buffer', 'fpfh'),
+                    help='buffer: the learned path (default).  fpfh: the classical baseline on the same pairs, thresholds and logs -- FPFH on '
+                         'the second-level clouds, mutual matches, RANSAC (buffer_amd/fpfh.py); no calibration, no --stage-metrics; the '
+                         'summary carries "descriptor"')
+
+
 def parse_with_preset(ap, argv, driver_name):
     """-> (args, Config of --preset); a preset of another data set is an argument error"""
     from .config import preset
     add_refine_args(ap)
+    add_descriptor_args(ap)
     a = ap.parse_args(argv)
+    if a.descriptor == 'fpfh' and a.stage_metrics:
+        ap.error('--stage-metrics measures the stages of the learned path: not available with --descriptor fpfh')
     try:
         return a, preset(a.preset, driver_name)
     except ValueError as e:
@@ -184,16 +195,22 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     `calibrate_pairs` pairs by rank 0 and broadcast), this rank's shard through register_pairs, gather, and on rank 0 the report:
     summarize(poses) -> the driver's own figures, the common ones, --by-overlap under the driver's (rte, rre) thresholds and
     --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
+    --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor").
     --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
     unrefined poses.
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
     from . import dist as bdist
     from .pipeline import BufferPipeline
     rank, world, dev, cdev = ranks
-    pipe = BufferPipeline(cfg, dev)
-    if a.limits:
-        pipe.limits = [int(x) for x in a.limits.split(',')]
+    fpfh = getattr(a, 'descriptor', 'buffer') == 'fpfh'
+    if fpfh:
+        from .fpfh import FpfhRegistration
+        pipe = FpfhRegistration(cfg, dev)                    # has no neighbourhood limits: nothing to calibrate
     else:
+        pipe = BufferPipeline(cfg, dev)
+    if a.limits and not fpfh:
+        pipe.limits = [int(x) for x in a.limits.split(',')]
+    elif not fpfh:
         if rank == 0:                                        # dataloader.py:18-51 on the first pairs
             host = []
             for i in range(min(len(ds), calibrate_pairs)):
@@ -228,6 +245,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
                            iterations=float(stats[:, 2].mean()) if len(stats) else 0.0)
         out = summarize(poses)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
+        if fpfh:
+            out['descriptor'] = 'fpfh'
         if ref_out is not None:
             out['refined'] = ref_out
         overlaps = None

@@ -1,0 +1,136 @@
+"""The classical baseline beside the learned path: FPFH descriptors (csrc/fpfh.hip, buf_fpfh), mutual nearest-neighbour matching
+in descriptor space, 3-point correspondence RANSAC (buf_ransac_kabsch) and an optional ICP step -- in open3d terms
+compute_fpfh_feature followed by registration_ransac_based_on_feature_matching.  open3d is absent here: the descriptor is restated
+from its published form (include/buffer_hip.h, N6; parity unpinned).
+
+    compute_fpfh        descriptors of one or several stacked clouds: one cell grid, one radius query, one launch pair
+    match               (mutual) 1-NN matches of two descriptor sets through ops.knn (d = 33: the exact fp32 scan)
+    FpfhRegistration    register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
+                        clouds and normals of driver.upload's dicts
+"""
+import numpy as np
+import torch
+
+from . import ops
+
+
+def compute_fpfh(points, normals, radius, max_nn=100, lengths=None):
+    """points, normals f32[n,3] (device; several clouds stacked when `lengths` int[nc] is given) -> FPFH f64[n,33]: the neighbours
+    of a point are the max_nn nearest inside `radius` within its own cloud, itself included (open3d's KDTreeSearchParamHybrid).
+    One CellGrid over the stacked clouds, one query with k = max_nn, one buf_fpfh call for all clouds."""
+    points = ops._dev(points, torch.float32, "compute_fpfh.points")
+    n = int(points.shape[0])
+    lens = np.array([n], np.int32) if lengths is None else np.asarray(lengths, np.int32).reshape(-1)
+    if int(lens.sum()) != n:
+        raise ValueError(f"compute_fpfh: lengths sum to {int(lens.sum())}, points holds {n} rows")
+    if not (2 <= int(max_nn) <= 128):
+        raise ValueError(f"compute_fpfh: max_nn={max_nn} (2..128)")
+    if n == 0:
+        return torch.zeros((0, 33), dtype=torch.float64, device=points.device)
+    grid = ops.CellGrid(points, lens, float(radius))
+    nbr = grid.query(points, lens, int(max_nn), q_order=grid.order)
+    return ops.fpfh(points, normals, nbr, int(max_nn))
+
+
+def match(fa, fb, mutual=True):
+    """fa f64|f32[na,d], fb [nb,d] (device) -> int32[m,2] rows (i, j): j = the nearest row of fb to fa[i] (ops.knn on the fp32
+    casts, Euclidean, ties to the lowest row), ascending i.  mutual: only the rows whose i is also the nearest row of fa to fb[j]."""
+    a, b = fa.float().contiguous(), fb.float().contiguous()
+    if a.shape[0] == 0 or b.shape[0] == 0:
+        return torch.zeros((0, 2), dtype=torch.int32, device=a.device)
+    ab = ops.knn(b[None], a[None], 1)[1].reshape(-1)
+    i = torch.arange(a.shape[0], device=a.device)
+    if mutual:
+        ba = ops.knn(a[None], b[None], 1)[1].reshape(-1)
+        i = i[ba[ab] == i]
+    return torch.stack([i, ab[i]], 1).to(torch.int32).contiguous()
+
+
+def ransac_on_matches(src, tgt, corr, nhyp, seed, max_dist, edge_similarity):
+    """src f32[ns,3], tgt f32[nt,3], corr int32[m,2] (device) -> pose f32[4,4] src -> tgt: ops.ransac_kabsch over the matched rows
+    (the kernel indexes both clouds with one list, so the rows are gathered first); fewer than 3 matches give the identity."""
+    if corr.shape[0] < 3:
+        return torch.eye(4, dtype=torch.float32, device=src.device)
+    c = corr.long()
+    idx = torch.arange(corr.shape[0], dtype=torch.int32, device=src.device)
+    return ops.ransac_kabsch(src[c[:, 0]].contiguous(), tgt[c[:, 1]].contiguous(), idx, nhyp=int(nhyp), seed=int(seed) & ops._MASK64,
+                             max_dist=float(max_dist), edge_similarity=float(edge_similarity))[0]
+
+
+class FpfhRegistration:
+    """FPFH + mutual matching + RANSAC (+ ICP) with BufferPipeline's calling convention.  radius = radius_factor * cfg.voxel_size_0
+    (the usual 5 voxels), RANSAC inlier distance = dist_factor * cfg.voxel_size_0, cfg.ransac_hypotheses hypotheses."""
+
+    def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9):
+        self.cfg, self.device = cfg, torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('FpfhRegistration runs on a HIP device only (no CPU path)')
+        self.radius = float(radius_factor) * cfg.voxel_size_0
+        self.max_nn, self.max_dist, self.edge_similarity = int(max_nn), float(dist_factor) * cfg.voxel_size_0, float(edge_similarity)
+        self.limits = None                   # the neighbourhood limits of the learned path: nothing to calibrate here
+
+    def calibrate(self, samples):
+        return self.limits
+
+    @staticmethod
+    def _clouds(inp):
+        ns = int(inp['lengths'][0])
+        return inp['points'][:ns], inp['points'][ns:], inp['features'][:ns, :3], inp['features'][ns:, :3]
+
+    @torch.no_grad()
+    def register_batch(self, inps, seeds=None, metrics_gt=None):
+        """inps: list of driver.upload dicts -> list of pose f32[4,4] device tensors (src -> tgt), pair b seeded with seeds[b]."""
+        if metrics_gt is not None:
+            raise NotImplementedError('FpfhRegistration: the per-stage metrics belong to the learned path (keypoints, patches)')
+        B = len(inps)
+        if B == 0:
+            return []
+        seeds = list(range(B)) if seeds is None else list(seeds)
+        pts = torch.cat([i['points'] for i in inps]).float().contiguous()
+        nrm = torch.cat([i['features'][:, :3] for i in inps]).float().contiguous()
+        lens = np.concatenate([np.asarray(i['lengths'], np.int32).reshape(2) for i in inps])
+        F = compute_fpfh(pts, nrm, self.radius, self.max_nn, lens)
+        off = np.concatenate([[0], np.cumsum(lens)])
+        out = []
+        for b in range(B):
+            s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
+            corr = match(F[s0:t0], F[t0:t1], True)
+            out.append(ransac_on_matches(pts[s0:t0], pts[t0:t1], corr, self.cfg.ransac_hypotheses, seeds[b], self.max_dist,
+                                         self.edge_similarity))
+        return out
+
+    @torch.no_grad()
+    def refine_batch(self, inps, poses, method='point_to_plane', max_dist=None, max_iteration=30, epsilon=1e-3):
+        """One batched ICP call (ops.icp_batched, the device form BufferPipeline.refine_batch uses) on the same second-level clouds
+        and their normals, started from `poses` -> BufferPipeline.refine_batch's dict."""
+        if method not in ops.ICP_METHODS:
+            raise ValueError(f'refine_batch: unknown method {method!r} (one of {sorted(ops.ICP_METHODS)})')
+        dev, B = self.device, len(inps)
+        if isinstance(poses, (list, tuple)):
+            poses = torch.stack(list(poses)) if B else torch.zeros((0, 4, 4), device=dev)
+        T0 = poses.to(dev, torch.float64).reshape(B, 4, 4).contiguous()
+        if B == 0:
+            return dict(poses=torch.zeros((0, 4, 4), dtype=torch.float32, device=dev), fitness=torch.zeros(0, dtype=torch.float64, device=dev),
+                        inlier_rmse=torch.zeros(0, dtype=torch.float64, device=dev), iterations=torch.zeros(0, dtype=torch.int32, device=dev))
+        cl = [self._clouds(i) for i in inps]
+        sl, tl = np.array([c[0].shape[0] for c in cl], np.int32), np.array([c[1].shape[0] for c in cl], np.int32)
+        src, tgt = torch.cat([c[0] for c in cl]).float().contiguous(), torch.cat([c[1] for c in cl]).float().contiguous()
+        snrm = torch.cat([c[2] for c in cl]).float().contiguous() if method == 'generalized' else None
+        tnrm = torch.cat([c[3] for c in cl]).float().contiguous() if method != 'point_to_point' else None
+        T, fit, rmse, iters, _ = ops.icp_batched(src, sl, tgt, tl, float(self.cfg.dist_th if max_dist is None else max_dist), T0, method,
+                                                 tnrm, int(max_iteration), src_normals=snrm, epsilon=epsilon)
+        return dict(poses=T.float(), fitness=fit, inlier_rmse=rmse, iterations=iters)
+
+    @torch.no_grad()
+    def register_batches(self, batches, seeds=None, metrics_gt=None, refine=None):
+        """BufferPipeline.register_batches' shapes: batches = lists of upload dicts (or callables returning one) -> per batch the list
+        of poses, or with refine=dict(method, max_dist, max_iteration) the tuple (poses, refine_batch's dict)."""
+        if metrics_gt is not None:
+            raise NotImplementedError('FpfhRegistration: the per-stage metrics belong to the learned path (keypoints, patches)')
+        seeds = [None] * len(batches) if seeds is None else seeds
+        out = []
+        for b, s in zip(batches, seeds):
+            inps = b() if callable(b) else b
+            res = self.register_batch(inps, s)
+            out.append(res if refine is None else (res, self.refine_batch(inps, res, **refine)))
+        return out

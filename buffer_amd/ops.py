@@ -567,6 +567,25 @@ def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='po
     return T, fit, rmse, iters, (nn[:int(src.shape[0])] if nn is not None else None)
 
 
+def fpfh(points, normals, nbr, max_nn=100, return_spfh=False):
+    """buf_fpfh: FPFH descriptors of the points f32[n,3] with normals f32[n,3] from their sorted radius rows nbr int32[n,k]
+    (CellGrid.query: padded with values >= n; column 0 is the point itself) -> f64[n,33] (, the SPFH table f64[n,33]).  The rows may
+    belong to several stacked clouds: a row stays inside its cloud."""
+    L = _lib.lib()
+    points, normals = _dev(points, torch.float32, "fpfh.points"), _dev(normals, torch.float32, "fpfh.normals")
+    nbr = _dev(nbr, torch.int32, "fpfh.nbr")
+    if points.dim() != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+        raise ValueError(f"fpfh: points {tuple(points.shape)} and normals {tuple(normals.shape)} are not both [N,3]")
+    n = int(points.shape[0])
+    if nbr.dim() != 2 or nbr.shape[0] != n:
+        raise ValueError(f"fpfh: nbr {tuple(nbr.shape)} is not [{n},k]")
+    out = torch.empty((n, 33), dtype=torch.float64, device=points.device)
+    spfh = torch.empty((n, 33), dtype=torch.float64, device=points.device)
+    check(L.buf_fpfh(_ptr(points), _ptr(normals), n, _ptr(nbr), int(nbr.shape[1]), int(max_nn), _ptr(out), _ptr(spfh), None, 0,
+                     _stream()), "buf_fpfh")
+    return (out, spfh) if return_spfh else out
+
+
 def pair_stats(points, lengths, pair_src, pair_tgt, T, radius, correspondences=False, cells_per_elem=0):
     """buf_pair_stats: statistics of P pairs over the C clouds stacked in points f32[sum lengths,3] under given transforms, one cell
     grid per call, nothing read back.  pair_src / pair_tgt host int[P] (cloud indices), T f64[P,4,4] (device) mapping the source

@@ -8,6 +8,11 @@ class KDTreeSearchParamKNN:
         self.knn = int(knn)
 
 
+class KDTreeSearchParamRadius:
+    def __init__(self, radius):
+        self.radius = float(radius)
+
+
 class KDTreeSearchParamHybrid:
     def __init__(self, radius, max_nn):
         self.radius, self.max_nn = float(radius), int(max_nn)

@@ -62,14 +62,8 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance,
-                                                estimation_method=None, ransac_n=3, checkers=(), criteria=None, seed=0):
-    """models/BUFFER.py:318-326 -> buf_ransac_kabsch (csrc/registration.hip): a fixed budget of seeded 3-point
-    hypotheses, each pre-checked by the edge-length and distance checkers, Kabsch, ranked by inlier count then RMSE
-    within `max_correspondence_distance`.  `criteria.max_iteration` caps the budget (default budget 4096);
-    `confidence` early termination does not apply to a batch that is evaluated at once."""
-    import torch
-    from buffer_amd import ops
+def _ransac_settings(max_correspondence_distance, estimation_method, ransac_n, checkers, criteria):
+    """what the two RANSAC entry points accept -> (edge similarity, hypothesis budget); everything else is refused"""
     from buffer_amd.config import THREEDMATCH
     est = estimation_method or TransformationEstimationPointToPoint(False)
     if est.with_scaling or int(ransac_n) != 3:
@@ -86,6 +80,18 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
     nhyp = THREEDMATCH.ransac_hypotheses
     if criteria is not None:
         nhyp = max(1, min(nhyp, criteria.max_iteration))
+    return edge, nhyp
+
+
+def registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance,
+                                                estimation_method=None, ransac_n=3, checkers=(), criteria=None, seed=0):
+    """models/BUFFER.py:318-326 -> buf_ransac_kabsch (csrc/registration.hip): a fixed budget of seeded 3-point
+    hypotheses, each pre-checked by the edge-length and distance checkers, Kabsch, ranked by inlier count then RMSE
+    within `max_correspondence_distance`.  `criteria.max_iteration` caps the budget (default budget 4096);
+    `confidence` early termination does not apply to a batch that is evaluated at once."""
+    import torch
+    from buffer_amd import ops
+    edge, nhyp = _ransac_settings(max_correspondence_distance, estimation_method, ransac_n, checkers, criteria)
     dev = _device()
     src = torch.from_numpy(np.asarray(source.points, np.float32)).to(dev)
     tgt = torch.from_numpy(np.asarray(target.points, np.float32)).to(dev)
@@ -94,6 +100,71 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
         return RegistrationResult()
     T, info = ops.ransac_kabsch(src, tgt, torch.from_numpy(corr).to(dev), nhyp=nhyp, seed=seed,
                                 max_dist=float(max_correspondence_distance), edge_similarity=edge)
+    T = T.cpu().numpy().astype(np.float64)
+    p = np.asarray(source.points)[corr[:, 0]] @ T[:3, :3].T + T[:3, 3]
+    d = np.linalg.norm(p - np.asarray(target.points)[corr[:, 1]], axis=1)
+    inl = d < max_correspondence_distance
+    return RegistrationResult(T, inl.mean() if len(inl) else 0.0, float(np.sqrt((d[inl] ** 2).mean())) if inl.any() else 0.0,
+                              corr[inl])
+
+
+class Feature:
+    """open3d.pipelines.registration.Feature: `data` f64[dimension, num], one column per point"""
+
+    def __init__(self, data=None):
+        self.data = np.zeros((0, 0), np.float64) if data is None else np.ascontiguousarray(data, dtype=np.float64)
+
+    def dimension(self):
+        return int(self.data.shape[0])
+
+    def num(self):
+        return int(self.data.shape[1])
+
+    def resize(self, dim, n):
+        self.data = np.zeros((int(dim), int(n)), np.float64)
+
+    def __repr__(self):
+        return f"Feature class with dimension = {self.dimension()} and num = {self.num()}"
+
+
+def compute_fpfh_feature(input, search_param):
+    """open3d compute_fpfh_feature -> Feature with data f64[33, n] (buffer_amd/fpfh.py compute_fpfh, csrc/fpfh.hip; restated from
+    the published algorithm, unpinned: include/buffer_hip.h N6 lists the deviations).  The neighbourhood is
+    KDTreeSearchParamHybrid(radius, max_nn) with max_nn <= 128; the cloud needs normals."""
+    import torch
+    from buffer_amd import fpfh
+    from ..geometry import KDTreeSearchParamHybrid
+    if not input.has_normals():
+        raise RuntimeError("[Open3D Error] Failed because input point cloud has no normal.")
+    if not isinstance(search_param, KDTreeSearchParamHybrid):
+        raise NotImplementedError("open3d stand-in: compute_fpfh_feature takes a KDTreeSearchParamHybrid(radius, max_nn) neighbourhood only")
+    dev = _device()
+    pts = torch.from_numpy(np.asarray(input.points, np.float32).reshape(-1, 3)).to(dev)
+    nrm = torch.from_numpy(np.asarray(input.normals, np.float32).reshape(-1, 3)).to(dev)
+    return Feature(fpfh.compute_fpfh(pts, nrm, search_param.radius, search_param.max_nn).cpu().numpy().T)
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
+                                                  max_correspondence_distance, estimation_method=None, ransac_n=3, checkers=(),
+                                                  criteria=None, seed=0):
+    """open3d registration_ransac_based_on_feature_matching: 1-NN matches of the source features among the target features
+    (buffer_amd/fpfh.py match; mutual_filter keeps the mutual ones, without open3d's fall-back to all matches when fewer than
+    ransac_n are mutual), then the RANSAC of registration_ransac_based_on_correspondence on them, with the same refusals."""
+    import torch
+    from buffer_amd import fpfh
+    edge, nhyp = _ransac_settings(max_correspondence_distance, estimation_method, ransac_n, checkers, criteria)
+    if source_feature.num() != len(source.points) or target_feature.num() != len(target.points):
+        raise ValueError("open3d stand-in: a feature set does not have one column per point of its cloud")
+    dev = _device()
+    src = torch.from_numpy(np.asarray(source.points, np.float32).reshape(-1, 3)).to(dev)
+    tgt = torch.from_numpy(np.asarray(target.points, np.float32).reshape(-1, 3)).to(dev)
+    fa = torch.from_numpy(np.ascontiguousarray(source_feature.data.T)).to(dev)
+    fb = torch.from_numpy(np.ascontiguousarray(target_feature.data.T)).to(dev)
+    corr_dev = fpfh.match(fa, fb, bool(mutual_filter))
+    corr = corr_dev.cpu().numpy()
+    if len(corr) < 3:
+        return RegistrationResult()
+    T = fpfh.ransac_on_matches(src, tgt, corr_dev, nhyp, seed, float(max_correspondence_distance), edge)
     T = T.cpu().numpy().astype(np.float64)
     p = np.asarray(source.points)[corr[:, 0]] @ T[:3, :3].T + T[:3, 3]
     d = np.linalg.norm(p - np.asarray(target.points)[corr[:, 1]], axis=1)

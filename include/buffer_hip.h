@@ -60,7 +60,9 @@ int         buf_device_count(void);
 #define BUF_TIMED_DESC_HEAD      9   /* A11 tail: work = (2*32*140*4 + 128) bytes per patch */
 #define BUF_TIMED_CYL_NET_SPLIT  10  /* A11 dense, split-f16 form (buf_cylindrical_net_split): work = dense flops, as id 1 */
 #define BUF_TIMED_COST_NET_SPLIT 11  /* A13, split-f16 form */
-#define BUF_TIMED_NKERNELS       12
+#define BUF_TIMED_SPFH           12  /* N6 k_spfh: work = n * (24 + 4*k_nbr + 24*K + 264) bytes, K = min(max_nn, k_nbr) (an upper bound: rows are shorter) */
+#define BUF_TIMED_FPFH           13  /* N6 k_fpfh: work = n * K * 264 bytes, the SPFH gather at full rows (an upper bound as well) */
+#define BUF_TIMED_NKERNELS       14
 void        buf_timing_enable(int on);
 long long   buf_timing_collect(double* total_ms, double* total_bytes);
 long long   buf_timing_collect_kernel(int kernel_id, double* total_ms, double* total_work);
@@ -499,6 +501,33 @@ int     buf_gicp_batched(const float* src, const float* src_normals, const int* 
                          const float* tgt_normals, const int* tgt_lengths_host, int npairs, float max_dist, double epsilon,
                          const double* T_init_f64, int max_iteration, double rel_fitness, double rel_rmse, double* T_out_f64,
                          double* fitness_out, double* rmse_out, int* iters_out, int* nn_out, void* ws, size_t ws_bytes, void* stream);
+
+/* N6  FPFH descriptors (Rusu, Blodow, Beetz 2009; open3d compute_fpfh_feature with KDTreeSearchParamHybrid restated from its
+ * published form, parity unpinned: this text is the specification).  One call for any number of stacked clouds.
+ * pts, normals f32[n,3]; nbr int32[n,k_nbr] = a buf_grid_query row per point (ascending by (d2, index), padded with values >= n:
+ * the rows stay inside a point's cloud, so no lengths are needed); fpfh_out f64[n,33]; spfh_out f64[n,33] (nullable: the table is
+ * then kept in ws, buf_fpfh_ws_bytes(n) bytes; with spfh_out given no workspace is read).
+ * Row of point i: the entries < n (and >= 0) among the first min(max_nn, k_nbr) columns, m_i of them.  Column 0 is taken to be the
+ *   point itself and is skipped, whatever it holds (open3d's k = 1..).  m_i < 2: both output rows of i are zero.
+ * Pair feature of (i, j), all fp64 on the fp32 inputs promoted, no FMA, dot products as (x + y) + z:
+ *   d = p_j - p_i, L = sqrt(d . d); L == 0: f = (0, 0, 0).  a1 = n_i . d / L, a2 = n_j . d / L.  If |a1| < |a2| (open3d tests
+ *   acos|a1| > acos|a2|: the same decision without the transcendental): (n1, n2, d) = (n_j, n_i, -d), f2 = -a2; else (n1, n2) =
+ *   (n_i, n_j), f2 = a1.  v = d x n1; |v| == 0: f = (0, 0, 0); else v /= |v|, w = n1 x v, f1 = v . n2, f0 = atan2(w . n2, n1 . n2).
+ * Bins: x0 = 11 (f0 + pi) / (2 pi), x1 = 11 (f1 + 1) / 2, x2 = 11 (f2 + 1) / 2; bin(x) = 0 if !(x >= 0), 10 if x >= 11, else (int)x
+ *   (NaN and -inf: bin 0, +inf: bin 10).  Feature c counts in slot 11 c + bin; a zero feature is binned too (slots 5, 16, 27).
+ * SPFH: integer counts, spfh[i][s] = count * (100.0 / (m_i - 1)).  (open3d adds the increment 100 / (m_i - 1) once per pair: the
+ *   product differs from that sum by rounding only and can be tested exactly.)
+ * FPFH: acc[s] = sum over the row's columns 1.. in column order of spfh[j][s] * w_ij with w_ij = 1.0 / d2_ij (formed once per
+ *   neighbour; open3d divides by d2 per slot: rounding only), d2 = d . d as above; j is skipped unless 0 < d2 < inf.  For each block
+ *   of 11 slots S_c = the sum of acc over the block in ascending slot order; S_c != 0: the block is multiplied by 100.0 / S_c.
+ *   fpfh[i][s] = acc[s] + spfh[i][s].
+ * No float atomics, every sum has a fixed order: a point's rows are the same bits alone, in any batch and on reruns.
+ * BUF_EINVAL before any device work for n < 0, k_nbr < 1, max_nn < 2 or > 128, a null input or fpfh_out with n > 0, and, when
+ * spfh_out is null, a workspace that is null or smaller than buf_fpfh_ws_bytes(n).  n == 0 succeeds and touches nothing. */
+size_t  buf_fpfh_ws_bytes(int n);
+int     buf_fpfh(const float* pts, const float* normals, int n, const int* nbr, int k_nbr, int max_nn,
+                 double* fpfh_out /* f64[n,33] */, double* spfh_out /* f64[n,33], nullable = use ws */,
+                 void* ws, size_t ws_bytes, void* stream);
 
 /* N4  Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
  * information matrix of a pair are made of; the evaluation half of an ICP round without the loop).
