@@ -28,3 +28,4 @@
 #include "costnet.hip"
 #include "split_safe.hip"
 #include "fpfh.hip"
+#include "fgr.hip"

@@ -168,6 +168,9 @@ def add_descriptor_args(ap):
                     help='buffer: the learned path (default).  fpfh: the classical baseline on the same pairs, thresholds and logs -- FPFH on '
                          'the second-level clouds, mutual matches, RANSAC (buffer_amd/fpfh.py); no calibration, no --stage-metrics; the '
                          'summary carries "descriptor"')
+    ap.add_argument('--estimator', default='ransac', choices=('ransac', 'fgr'),
+                    help='the pose estimator of --descriptor fpfh.  ransac: seeded 3-point hypotheses (default).  fgr: Fast Global Registration '
+                         'on the same matches, one batched call per chunk (buffer_amd/fgr.py); the summary carries "estimator"')
 
 
 def parse_with_preset(ap, argv, driver_name):
@@ -178,6 +181,8 @@ def parse_with_preset(ap, argv, driver_name):
     a = ap.parse_args(argv)
     if a.descriptor == 'fpfh' and a.stage_metrics:
         ap.error('--stage-metrics measures the stages of the learned path: not available with --descriptor fpfh')
+    if a.estimator != 'ransac' and a.descriptor != 'fpfh':
+        ap.error(f'--estimator {a.estimator} chooses the estimator of the classical baseline: it needs --descriptor fpfh')
     try:
         return a, preset(a.preset, driver_name)
     except ValueError as e:
@@ -195,7 +200,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     `calibrate_pairs` pairs by rank 0 and broadcast), this rank's shard through register_pairs, gather, and on rank 0 the report:
     summarize(poses) -> the driver's own figures, the common ones, --by-overlap under the driver's (rte, rre) thresholds and
     --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
-    --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor").
+    --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor" and
+    "estimator", --estimator choosing its RANSAC or its Fast Global Registration).
     --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
     unrefined poses.
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
@@ -205,7 +211,7 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     fpfh = getattr(a, 'descriptor', 'buffer') == 'fpfh'
     if fpfh:
         from .fpfh import FpfhRegistration
-        pipe = FpfhRegistration(cfg, dev)                    # has no neighbourhood limits: nothing to calibrate
+        pipe = FpfhRegistration(cfg, dev, estimator=getattr(a, 'estimator', 'ransac'))     # no neighbourhood limits: nothing to calibrate
     else:
         pipe = BufferPipeline(cfg, dev)
     if a.limits and not fpfh:
@@ -247,6 +253,7 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
         if fpfh:
             out['descriptor'] = 'fpfh'
+            out['estimator'] = getattr(a, 'estimator', 'ransac')
         if ref_out is not None:
             out['refined'] = ref_out
         overlaps = None

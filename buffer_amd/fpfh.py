@@ -5,13 +5,16 @@ from its published form (include/buffer_hip.h, N6; parity unpinned).
 
     compute_fpfh        descriptors of one or several stacked clouds: one cell grid, one radius query, one launch pair
     match               (mutual) 1-NN matches of two descriptor sets through ops.knn (d = 33: the exact fp32 scan)
-    FpfhRegistration    register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
+    FpfhRegistration    estimator='ransac' (default) or 'fgr' (buffer_amd/fgr.py: one batched Fast Global Registration call per
+                        batch on the concatenated match lists); register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
                         clouds and normals of driver.upload's dicts
 """
 import numpy as np
 import torch
 
 from . import ops
+
+ESTIMATORS = ('ransac', 'fgr')
 
 
 def compute_fpfh(points, normals, radius, max_nn=100, lengths=None):
@@ -59,12 +62,17 @@ def ransac_on_matches(src, tgt, corr, nhyp, seed, max_dist, edge_similarity):
 
 class FpfhRegistration:
     """FPFH + mutual matching + RANSAC (+ ICP) with BufferPipeline's calling convention.  radius = radius_factor * cfg.voxel_size_0
-    (the usual 5 voxels), RANSAC inlier distance = dist_factor * cfg.voxel_size_0, cfg.ransac_hypotheses hypotheses."""
+    (the usual 5 voxels), RANSAC inlier distance = dist_factor * cfg.voxel_size_0, cfg.ransac_hypotheses hypotheses.
+    estimator='fgr': Fast Global Registration instead of the RANSAC, on the same matches and seeds, with the paper's delta = the same
+    dist_factor * cfg.voxel_size_0 in the clouds' units and open3d's defaults otherwise."""
 
-    def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9):
+    def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac'):
         self.cfg, self.device = cfg, torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('FpfhRegistration runs on a HIP device only (no CPU path)')
+        if estimator not in ESTIMATORS:
+            raise ValueError(f'FpfhRegistration: unknown estimator {estimator!r} (one of {ESTIMATORS})')
+        self.estimator = estimator
         self.radius = float(radius_factor) * cfg.voxel_size_0
         self.max_nn, self.max_dist, self.edge_similarity = int(max_nn), float(dist_factor) * cfg.voxel_size_0, float(edge_similarity)
         self.limits = None                   # the neighbourhood limits of the learned path: nothing to calibrate here
@@ -91,6 +99,8 @@ class FpfhRegistration:
         lens = np.concatenate([np.asarray(i['lengths'], np.int32).reshape(2) for i in inps])
         F = compute_fpfh(pts, nrm, self.radius, self.max_nn, lens)
         off = np.concatenate([[0], np.cumsum(lens)])
+        if self.estimator == 'fgr':
+            return self._fgr_batch(pts, lens, off, F, seeds)
         out = []
         for b in range(B):
             s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
@@ -98,6 +108,22 @@ class FpfhRegistration:
             out.append(ransac_on_matches(pts[s0:t0], pts[t0:t1], corr, self.cfg.ransac_hypotheses, seeds[b], self.max_dist,
                                          self.edge_similarity))
         return out
+
+    def _fgr_batch(self, pts, lens, off, F, seeds):
+        """the matches of every pair (pair by pair, as the RANSAC path matches), then ONE fgr_batched call for the batch"""
+        from . import fgr
+        B = len(lens) // 2
+        corrs = []
+        for b in range(B):
+            s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
+            corrs.append(match(F[s0:t0], F[t0:t1], True))
+        # the pairs' clouds alternate in pts (src, tgt, src, ...): the kernel takes the two sides stacked apart
+        src = torch.cat([pts[int(off[2 * b]):int(off[2 * b + 1])] for b in range(B)])
+        tgt = torch.cat([pts[int(off[2 * b + 1]):int(off[2 * b + 2])] for b in range(B)])
+        res = fgr.fast_global_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
+                                           seeds=[int(s) & ops._MASK64 for s in seeds], maximum_correspondence_distance=self.max_dist,
+                                           delta_absolute=True)
+        return list(res['poses'].float().unbind(0))
 
     @torch.no_grad()
     def refine_batch(self, inps, poses, method='point_to_plane', max_dist=None, max_iteration=30, epsilon=1e-3):

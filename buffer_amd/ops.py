@@ -586,6 +586,49 @@ def fpfh(points, normals, nbr, max_nn=100, return_spfh=False):
     return (out, spfh) if return_spfh else out
 
 
+FGR_STATUS = ('NOTHING', 'OK', 'FAILED')                                                        # BUF_FGR_* of buffer_hip.h
+FGR_MAX_TUPLES = 4096
+
+
+def fgr_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, seeds=None, tuple_scale=0.95, max_tuples=1000, trial_factor=100,
+                mu_start=1.0, delta=0.025, delta_absolute=False, division_factor=1.4, decrease_every=4, iterations=64,
+                return_rows=False):
+    """buf_fgr_batched: Fast Global Registration of the pairs stacked in src f32[sum src_lengths,3] / tgt f32[sum tgt_lengths,3] on
+    the correspondences corr int32[sum corr_lengths,2] ((src row, tgt row) inside the pair's own clouds), pair b drawing its tuples
+    with seeds[b] (default b) -> (T f64[B,4,4] src -> tgt, info int32[B,4] = (index into FGR_STATUS, tuples kept, trials examined,
+    updates applied), rows int32[B,3*max_tuples,2] or None: the kept correspondences, tail -1, weights f64[B,3*max_tuples] or None:
+    their line-process weights at the last linearisation, tail NaN), all on the device; two launches, nothing read back."""
+    L = _lib.lib()
+    src, tgt = _dev(src, torch.float32, "fgr_batched.src"), _dev(tgt, torch.float32, "fgr_batched.tgt")
+    corr = _dev(corr, torch.int32, "fgr_batched.corr")
+    sl, tl, cl = _host_i32(src_lengths), _host_i32(tgt_lengths), _host_i32(corr_lengths)
+    B, dev = int(sl.shape[0]), src.device
+    if tl.shape[0] != B or cl.shape[0] != B:
+        raise ValueError(f"fgr_batched: {B} source lengths but {tl.shape[0]} target and {cl.shape[0]} correspondence lengths")
+    for name, t, ln, w in (("src", src, sl, 3), ("tgt", tgt, tl, 3), ("corr", corr, cl, 2)):
+        if t.dim() != 2 or t.shape[1] != w:
+            raise ValueError(f"fgr_batched: {name} {tuple(t.shape)} is not [N,{w}]")
+        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
+            raise ValueError(f"fgr_batched: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    if not (1 <= int(max_tuples) <= FGR_MAX_TUPLES):
+        raise ValueError(f"fgr_batched: max_tuples={max_tuples} (1..{FGR_MAX_TUPLES})")
+    sd = np.arange(B, dtype=np.uint64) if seeds is None else np.array([int(s) & _MASK64 for s in seeds], dtype=np.uint64).reshape(-1)
+    if sd.shape[0] != B:
+        raise ValueError(f"fgr_batched: {B} pairs but {sd.shape[0]} seeds")
+    mt = int(max_tuples)
+    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
+    info = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+    rows = torch.empty((B, 3 * mt, 2), dtype=torch.int32, device=dev) if return_rows else None
+    weights = torch.empty((B, 3 * mt), dtype=torch.float64, device=dev) if return_rows else None
+    nbytes = max(L.buf_fgr_ws_bytes(int(corr.shape[0]), max(B, 1), mt), 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_fgr_batched(_ptr(src), _hptr(sl), _ptr(tgt), _hptr(tl), _ptr(corr), _hptr(cl), B, _hptr(sd), float(tuple_scale), mt,
+                            int(trial_factor), float(mu_start), float(delta), int(bool(delta_absolute)), float(division_factor),
+                            int(decrease_every), int(iterations), _ptr(T), _ptr(info), _ptr(rows), _ptr(weights), _ptr(ws), nbytes,
+                            _stream()), "buf_fgr_batched")
+    return T, info, rows, weights
+
+
 def pair_stats(points, lengths, pair_src, pair_tgt, T, radius, correspondences=False, cells_per_elem=0):
     """buf_pair_stats: statistics of P pairs over the C clouds stacked in points f32[sum lengths,3] under given transforms, one cell
     grid per call, nothing read back.  pair_src / pair_tgt host int[P] (cloud indices), T f64[P,4,4] (device) mapping the source

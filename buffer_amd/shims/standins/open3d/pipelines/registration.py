@@ -173,6 +173,54 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
                               corr[inl])
 
 
+class FastGlobalRegistrationOption:
+    """open3d's option holder, with its names and defaults (buffer_amd/fgr.py FgrOptions carries them to the kernel)"""
+
+    def __init__(self, division_factor=1.4, use_absolute_scale=False, decrease_mu=True, maximum_correspondence_distance=0.025,
+                 iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000):
+        self.division_factor, self.use_absolute_scale, self.decrease_mu = float(division_factor), bool(use_absolute_scale), bool(decrease_mu)
+        self.maximum_correspondence_distance, self.iteration_number = float(maximum_correspondence_distance), int(iteration_number)
+        self.tuple_scale, self.maximum_tuple_count = float(tuple_scale), int(maximum_tuple_count)
+
+    def __repr__(self):
+        return ("FastGlobalRegistrationOption class with " + ", ".join(f"{k}={v}" for k, v in vars(self).items()))
+
+
+def registration_fast_based_on_feature_matching(source, target, source_feature, target_feature, option=None, seed=0):
+    """open3d registration_fast_based_on_feature_matching: the MUTUAL 1-NN matches of the two feature sets (buffer_amd/fpfh.py match;
+    open3d's own matching adds a cross-check fall-back this one has not), then Fast Global Registration on them (buffer_amd/fgr.py,
+    csrc/fgr.hip; restated from the published algorithm, unpinned: include/buffer_hip.h N7 lists the deviations).
+    option.maximum_correspondence_distance is read in normalised units, as open3d reads it, both for the annealing floor and for the
+    result's inliers: the residual of a match is divided by the pair's scale D before it is compared.  use_absolute_scale=True is
+    refused.  `seed` seeds the tuple draw (open3d draws from its global generator)."""
+    import torch
+    from buffer_amd import fgr, fpfh
+    opt = option or FastGlobalRegistrationOption()
+    if opt.use_absolute_scale:
+        raise NotImplementedError("open3d stand-in: FastGlobalRegistrationOption.use_absolute_scale=True is not provided")
+    if source_feature.num() != len(source.points) or target_feature.num() != len(target.points):
+        raise ValueError("open3d stand-in: a feature set does not have one column per point of its cloud")
+    dev = _device()
+    sp, tp = np.asarray(source.points, np.float32).reshape(-1, 3), np.asarray(target.points, np.float32).reshape(-1, 3)
+    src, tgt = torch.from_numpy(sp).to(dev), torch.from_numpy(tp).to(dev)
+    fa = torch.from_numpy(np.ascontiguousarray(source_feature.data.T)).to(dev)
+    fb = torch.from_numpy(np.ascontiguousarray(target_feature.data.T)).to(dev)
+    corr_dev = fpfh.match(fa, fb, True)
+    corr = corr_dev.cpu().numpy()
+    res = fgr.fast_global_registration(src, [len(sp)], tgt, [len(tp)], corr_dev, [len(corr)], seeds=[seed], options=fgr.FgrOptions(
+        **{k: getattr(opt, k) for k in ('division_factor', 'use_absolute_scale', 'decrease_mu', 'maximum_correspondence_distance',
+                                        'iteration_number', 'tuple_scale', 'maximum_tuple_count')}))
+    T = res['poses'][0].cpu().numpy()
+    if len(corr) == 0:
+        return RegistrationResult(T)
+    fin = [c[np.isfinite(c).all(1)].astype(np.float64) for c in (sp, tp)]
+    D = max(float(np.linalg.norm(c - c.mean(0), axis=1).max()) if len(c) else 0.0 for c in fin)
+    p = sp[corr[:, 0]].astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+    d = np.linalg.norm(p - tp[corr[:, 1]], axis=1)
+    inl = d / D < opt.maximum_correspondence_distance if D > 0 else np.zeros(len(d), bool)
+    return RegistrationResult(T, inl.mean(), float(np.sqrt((d[inl] ** 2).mean())) if inl.any() else 0.0, corr[inl])
+
+
 def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
     """KITTI/dataset.py:104-107: ICP on the device (buffer_amd/icp.py, csrc/icp.hip).  TransformationEstimationPointToPlane uses
     the target's normals; a target without normals raises RuntimeError (open3d would hand back the initial transform unrefined:

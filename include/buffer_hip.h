@@ -529,6 +529,58 @@ int     buf_fpfh(const float* pts, const float* normals, int n, const int* nbr, 
                  double* fpfh_out /* f64[n,33] */, double* spfh_out /* f64[n,33], nullable = use ws */,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* N7  Fast Global Registration (Zhou, Park, Koltun, ECCV 2016; open3d registration_fast_based_on_feature_matching restated from
+ * its published form, parity unpinned: this text is the specification).  B pairs per call, two launches, nothing read back.
+ * Pair b owns src_lengths_host[b] / tgt_lengths_host[b] consecutive rows of src / tgt (f32[.,3], device) and corr_lengths_host[b]
+ * consecutive rows of corr (int32[.,2], device: (src row, tgt row) inside the pair's own clouds), and draws with seeds_host[b].
+ * All arithmetic is fp64 on the fp32 inputs promoted, without FMA; dot products are (x + y) + z.
+ * Tuple test (AdvancedMatching, step 3), on the coordinates as given, n = the pair's correspondences, ntrial = trial_factor * n:
+ *   trial t draws r_k = splitmix64(seed + 3 t + k) % n, k = 0, 1, 2 (the mixer of buf_ransac_kabsch: splitmix64(0) =
+ *   0xE220A8397B1DCDAF; with replacement, as open3d draws).  a_e / b_e = the squared lengths of the edges e = (0,1), (1,2), (2,0)
+ *   between the three target / source points, d = u - v, (dx*dx + dy*dy) + dz*dz.  With s2 = tuple_scale * tuple_scale (formed once,
+ *   on the host) the trial is accepted iff s2 * a_e < b_e and s2 * b_e < a_e for all three edges: strict, so a repeated index or a
+ *   coincident point rejects it.  (open3d compares scale * l < l' and l' < l / scale on the lengths, after normalisation: the same
+ *   decision up to rounding, without a square root.)  A trial with an index outside its cloud or a non-finite coordinate is rejected.
+ *   The accepted trials are kept in ascending trial order, the first max_tuples of them, each adding its three correspondences in the
+ *   order k = 0, 1, 2 (duplicates stay).  trials examined = 1 + the trial that filled the list, ntrial when it never filled.
+ *   rows_out[b] (nullable) int32[3 max_tuples, 2] = the kept (src row, tgt row), the tail -1.
+ * Normalisation (NormalizePointCloud, one scale): c_src, c_tgt = the means of the pair's whole clouds, D = the largest |p - c| over
+ *   both; a row with a non-finite coordinate is left out of mean, count and maximum.  The means are fixed-shape sums: lane k of 256
+ *   adds the rows k, k + 256, ... in ascending order, then a tree over the lanes.  The points used below are (p - c) / D.  An empty
+ *   cloud (no finite row) or D == 0 gives status NOTHING.
+ * Optimisation (OptimizePairwiseRegistration).  Fewer than 10 kept rows: status NOTHING.  Else T = I, mu = mu_start, floor = delta
+ *   (delta_absolute == 0: open3d's own comparison, in normalised units) or (delta / D)^2 (delta_absolute != 0: the paper's).  For
+ *   it = 0 .. iterations - 1, over the kept rows (s, p): q = R s + t per row of T as ((R0*sx + R1*sy) + R2*sz) + t; r = p - q;
+ *   w = (mu / (r.r + mu))^2, w = 0 where r.r is not finite (open3d transforms a copy of the cloud step by step instead of
+ *   accumulating T: rounding only).  Jacobian rows [0, -qz, qy, -1, 0, 0], [qz, 0, -qx, 0, -1, 0], [-qy, qx, 0, 0, 0, -1];
+ *   H += w J J^T, g += w J r, summed in the shape of the means; H x = -g by the LDL^T of buf_icp_batched; T <- dT(x) T with
+ *   dT = [Rz(x2) Ry(x1) Rx(x0) | x3..5]; then, if it % decrease_every == 0 and mu > floor, mu /= division_factor.  A system that is
+ *   not positive definite or a non-finite solution stops the pair with status FAILED and the T of the last good iterate.
+ * Outputs (device).  T_out f64[B,4,4] src -> tgt = [R | D t + c_tgt - R c_src]; a pair without an applied update (NOTHING, FAILED
+ *   in the first step, iterations == 0) returns the identity exactly (open3d would return the translation c_tgt - c_src there).
+ *   info_out int32[B,4] = status (BUF_FGR_*), tuples kept, trials examined, updates applied.  weights_out[b] (nullable)
+ *   f64[3 max_tuples] = w of the last linearisation per kept row (the failed one included), NaN in the tail and everywhere when
+ *   nothing was linearised.  No float atomics, every sum has a fixed order: a pair's outputs are the same bits alone, in any batch,
+ *   in any batch order and on reruns.
+ * BUF_EINVAL before any device work for npairs < 0, negative lengths, a null required argument with npairs > 0 (src / tgt / corr only
+ * where their rows are not zero), tuple_scale outside (0, 1], max_tuples outside 1..4096, trial_factor < 1 or trial_factor * n beyond
+ * int, mu_start / delta / division_factor not finite and > 0, division_factor <= 1, decrease_every < 1, iterations < 0, and a
+ * workspace that is null or smaller than buf_fgr_ws_bytes.  npairs == 0 succeeds and touches nothing; a pair with n == 0 returns the
+ * identity, NOTHING and zeros. */
+#define BUF_FGR_NOTHING 0
+#define BUF_FGR_OK      1
+#define BUF_FGR_FAILED  2
+size_t  buf_fgr_ws_bytes(int n_corr_total, int npairs, int max_tuples);
+int     buf_fgr_batched(const float* src, const int* src_lengths_host, const float* tgt, const int* tgt_lengths_host,
+                        const int* corr /* int32[sum corr_lengths,2]: (src row, tgt row), local to the pair's clouds */,
+                        const int* corr_lengths_host, int npairs, const unsigned long long* seeds_host,
+                        double tuple_scale, int max_tuples, int trial_factor,          /* 0.95, 1000, 100 */
+                        double mu_start, double delta, int delta_absolute,             /* 1.0, 0.025, 0 */
+                        double division_factor, int decrease_every, int iterations,    /* 1.4, 4, 64 */
+                        double* T_out /* f64[B,4,4] src -> tgt */, int* info_out /* int32[B,4] */,
+                        int* rows_out /* nullable int32[B,3*max_tuples,2] */, double* weights_out /* nullable f64[B,3*max_tuples] */,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* N4  Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
  * information matrix of a pair are made of; the evaluation half of an ICP round without the loop).
  * pts f32[sum lengths_host,3] stacks the C clouds; pair k = (pair_src_host[k], pair_tgt_host[k], T_f64[k]) with T_f64 f64[P,4,4]
