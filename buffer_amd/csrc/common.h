@@ -91,6 +91,28 @@ __device__ __forceinline__ int xcd_contiguous_block(int bid, int nb)
 }
 
 // ---- A2 cell-grid lookups (the grid of radius.hip; every kernel that reads it finds a query's cells with these two) ----
+// Cell edge and table dims of one element: ext[] = extent of its box (finite, >= 0), cells = slots of its dense table (>= 1).  The
+// edge starts strictly larger than the radius (so that |dx| < r never spans two cells + 1) and is coarsened by 1.25 UNTIL the table
+// fits: the loop ends by construction, since an edge above the largest extent gives floor(ext / edge) = 0 on every axis, a table of
+// one cell (an edge that overflows to +inf included: ext / inf = 0).  dim[] is therefore always taken from a fitting table, every
+// dim lies in [1, cells] and the int conversion is exact.  (The loop used to give up after 200 steps -- an extent above
+// ~2.4e19 * cells^(1/3) radii, e.g. a 1e30 sentinel point in a cloud searched at 0.07 -- and dim[] then came from a table that did
+// not fit, past the int range.)  Host and device run the same fp64 operations in the same order: same edge and dims, bit for bit.
+__host__ __device__ inline void grid_cell_dims(const double ext[3], double radius, long long cells, double& edge, int dim[3])
+{
+    const double fit = cells > 1 ? (double)cells : 1.0;
+    double cell = radius > 0 ? radius * 1.00001 : 1.0;
+    double d[3];
+    for (;;) {
+        double tot = 1.0;
+        for (int c = 0; c < 3; c++) { d[c] = floor(ext[c] / cell) + 1.0; tot *= d[c]; }
+        if (tot <= fit) break;
+        cell *= 1.25;
+    }
+    for (int c = 0; c < 3; c++) dim[c] = (int)d[c];
+    edge = cell;
+}
+
 // Cell coordinate of a query coordinate v along one axis of an element's grid.  fp64: a query must land in exactly the cell its
 // coordinate rounds to (the cell edge exceeds the radius by 1e-5 only).  Clamped to [-2, dim + 1] before the int conversion:
 // far-away queries simply find no cell.  (The build side clamps to [0, dim - 1] instead: cell_coord in radius.hip.)

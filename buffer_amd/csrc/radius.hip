@@ -64,15 +64,8 @@ __global__ void __launch_bounds__(BBOX_THREADS) k_grid_bbox(const float* __restr
             g.mn[c] = a;
             ext[c] = (double)z - (double)a;
         }
-        // cell edge strictly larger than the radius so that |dx| < r never spans two cells + 1
-        double cell = radius > 0 ? radius * 1.00001 : 1.0;
-        for (int it = 0; it < 200; it++) {
-            double tot = 1.0;
-            for (int c = 0; c < 3; c++) tot *= floor(ext[c] / cell) + 1.0;
-            if (tot <= (double)cells_per_elem) break;
-            cell *= 1.25;
-        }
-        for (int c = 0; c < 3; c++) g.dim[c] = (int)(floor(ext[c] / cell) + 1.0);
+        double cell;
+        grid_cell_dims(ext, radius, cells_per_elem, cell, g.dim);    // edge > radius, coarsened until the table fits (common.h)
         g.inv_cell = 1.0 / cell;
         g.table_off = (int)((long long)b * cells_per_elem);
         g.s_off = lo;
@@ -644,6 +637,18 @@ extern "C" int64_t buf_grid_default_cells(int ns, int nb)
     // keep the concatenated table addressable with int32
     int64_t cap = nb > 0 ? (int64_t)0x7fff0000 / nb : 0x7fff0000;
     return c < cap ? c : cap;
+}
+
+// The cell rule of k_grid_bbox on the host (pure arithmetic, no device): what the build derives from an element's box.
+extern "C" int buf_grid_cell_dims(const double* ext, float radius, int64_t cells_per_elem, double* edge_out, int* dim_out)
+{
+    BUF_REQUIRE(ext && edge_out && dim_out, BUF_EINVAL, "buf_grid_cell_dims: null argument");
+    BUF_REQUIRE(radius == radius, BUF_EINVAL, "buf_grid_cell_dims: radius is NaN");
+    BUF_REQUIRE(cells_per_elem >= 1, BUF_EINVAL, "buf_grid_cell_dims: cells_per_elem=%lld", (long long)cells_per_elem);
+    for (int c = 0; c < 3; c++)
+        BUF_REQUIRE(ext[c] >= 0 && __builtin_isfinite(ext[c]), BUF_EINVAL, "buf_grid_cell_dims: ext[%d]=%g (a box extent is finite and >= 0)", c, ext[c]);
+    grid_cell_dims(ext, (double)radius, (long long)cells_per_elem, *edge_out, dim_out);
+    return BUF_OK;
 }
 
 static void carve_grid(buf_grid_t* g, WsCarver& w, int ns, int nb, int64_t cells)

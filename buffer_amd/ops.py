@@ -102,6 +102,14 @@ def radius_neighbors(queries, supports, q_lengths, s_lengths, radius, k=None):
     return grid.query(queries, q_lengths, k)
 
 
+def grid_cell_dims(ext, radius, cells_per_elem):
+    """The cell rule of buf_grid_build for a box of extent ext[3] -> (edge float, dims (int, int, int)).  Host arithmetic: no device."""
+    e = (C.c_double * 3)(*[float(v) for v in ext])
+    edge, dim = C.c_double(), (C.c_int * 3)()
+    check(_lib.lib().buf_grid_cell_dims(e, float(radius), int(cells_per_elem), C.byref(edge), dim), "buf_grid_cell_dims")
+    return edge.value, tuple(dim)
+
+
 HOST_WAIT_S = [0.0]        # diagnostics: seconds callers spent blocked in calls that end with a host round trip (subsample row counts)
 
 

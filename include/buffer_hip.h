@@ -96,6 +96,11 @@ typedef struct buf_grid {
 
 int64_t buf_grid_default_cells(int ns, int nb);
 size_t  buf_grid_ws_bytes(int ns, int nb, int64_t cells_per_elem);
+/* The cell rule of the build, on the host (pure arithmetic, no device): ext f64[3] = extent of an element's box over its finite
+ * coordinates (finite, >= 0), cells_per_elem >= 1.  edge = radius * 1.00001 (1.0 for radius <= 0), multiplied by 1.25 until
+ * prod(floor(ext / edge) + 1) <= cells_per_elem -- however many steps that takes: it ends at a one-cell table at the latest.
+ * -> *edge_out, dim_out int[3] (every dim >= 1, their product <= cells_per_elem): the values buf_grid_build derives, bit for bit. */
+int     buf_grid_cell_dims(const double* ext, float radius, int64_t cells_per_elem, double* edge_out, int* dim_out);
 int     buf_grid_build(buf_grid_t* g, const float* supports, int ns, const int* s_batches_host, int nb,
                        float radius, int64_t cells_per_elem, void* ws, size_t ws_bytes, void* stream);
 /* queries f32[nq,3]; q_order (nullable) int32[nq]: processing order, any permutation of 0..nq-1 (slot t handles query
