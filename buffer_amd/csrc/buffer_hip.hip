@@ -25,6 +25,7 @@
 #include "convnet_wg.hip"
 #include "convnet_w24.hip"
 #include "convnet_w24k.hip"
+#include "convnet_w24p.hip"
 #include "costnet.hip"
 #include "split_safe.hip"
 #include "fpfh.hip"

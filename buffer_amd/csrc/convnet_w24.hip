@@ -485,9 +485,12 @@ extern "C" int buf_cylindrical_net_wg_flags(const int* cin_host, const int* cout
 }
 
 // The F(2x4) launch behind wg_launch: P as wg_launch filled it (widths checked, relu[] still with the flag bits).  Stacks that carry
-// bit 2 (BUF_CYL_F24K: the K-split F(2x4) form of 64-output layers) go on to k_cyl_net_w24k (csrc/convnet_w24k.hip).
+// bit 2 (BUF_CYL_F24K: the F(2x4) form of 64-output layers) go on to k_cyl_net_w24k (csrc/convnet_w24k.hip: K split) or
+// k_cyl_net_w24p (csrc/convnet_w24p.hip: pass split) as `form` says.
+#define BUF_CYL_FORM_LIBRARY BUF_CYL_FORM_PASS_SPLIT      // what BUF_CYL_FORM_DEFAULT means (profiles/f24p_ab.md)
 static int w24k_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
-static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream)
+static int w24p_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
+static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream, int form)
 {
     if (int rc = w24_check_flags(P.cin, P.cout, P.relu)) return rc;
     bool ksplit = false;
@@ -496,7 +499,8 @@ static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void*
         ksplit |= (P.relu[l] & BUF_CYL_F24K) != 0;
         P.relu[l] &= ~WG_F24_FLAG;
     }
-    if (ksplit) return w24k_launch(x, npatch, P, y, stream);
+    if (form == BUF_CYL_FORM_DEFAULT) form = BUF_CYL_FORM_LIBRARY;
+    if (ksplit) return form == BUF_CYL_FORM_PASS_SPLIT ? w24p_launch(x, npatch, P, y, stream) : w24k_launch(x, npatch, P, y, stream);
     size_t lds = sizeof(float) * WG_BUF;
     static LdsGrant grant, grant_rerun;
     if (int rc = P.only_if ? grant_dynamic_lds((const void*)k_cyl_net_w24_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_w24, lds, grant)) return rc;

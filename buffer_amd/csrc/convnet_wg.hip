@@ -803,17 +803,19 @@ extern "C" int buf_cylindrical_net_wg_supports(const int* cin_host, const int* c
 
 // relu_host[l] bit 1 (WG_F24_FLAG): the layer's filter buffer holds the F(2x4) set behind the F(2x2) set and the stack runs in
 // k_cyl_net_w24 (csrc/convnet_w24.hip), which launches it: w24_launch.  Bit 2 (BUF_CYL_F24K) likewise for the K-split F(2x4) form of
-// 64-output layers (csrc/convnet_w24k.hip).  Every word above 1 goes to w24_launch, which checks the flag rules; callers that pass
+// 64-output layers (csrc/convnet_w24k.hip; `form` picks the pass-split form of csrc/convnet_w24p.hip instead).  Every word above 1 goes to w24_launch, which checks the flag rules; callers that pass
 // 0 / 1 never reach it.
 #define WG_F24_FLAG BUF_CYL_F24
 static inline bool wg_f24_flagged(int relu) { return relu >= 2; }
-static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
+static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream, int form);
 
 // x f32[np,48,140] -> y f32[np,32,140]; weights in the Winograd-domain tiling (see CylWgParams).
 static int wg_launch(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
-                     const int* cout_host, const int* relu_host, float* y, const int* only_if, void* stream)
+                     const int* cout_host, const int* relu_host, float* y, const int* only_if, void* stream, int form)
 {
     BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "buf_cylindrical_net_wg: npatch=%d", npatch);
+    BUF_REQUIRE(form >= BUF_CYL_FORM_DEFAULT && form <= BUF_CYL_FORM_PASS_SPLIT, BUF_EINVAL,
+                "buf_cylindrical_net_wg: form=%d (-1: the library's default, 0: K split, 1: pass split)", form);
     if (npatch == 0) return BUF_OK;
     BUF_REQUIRE(x && y && wt_host && bias_host && cin_host && cout_host && relu_host, BUF_EINVAL, "buf_cylindrical_net_wg: null argument");
     CylWgParams P;
@@ -825,7 +827,7 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
     if (int rc = wg_check_widths(P.cin, P.cout)) return rc;
     P.only_if = only_if;
     for (int l = 0; l < WG_LAYERS; l++)
-        if (wg_f24_flagged(relu_host[l])) return w24_launch(x, npatch, P, y, stream);
+        if (wg_f24_flagged(relu_host[l])) return w24_launch(x, npatch, P, y, stream, form);
     size_t lds = sizeof(float) * WG_BUF;
     static LdsGrant grant, grant_rerun;
     if (int rc = only_if ? grant_dynamic_lds((const void*)k_cyl_net_wg_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_wg, lds, grant)) return rc;
@@ -873,5 +875,12 @@ static int wg_launch(const float* x, int npatch, const float* const* wt_host, co
 extern "C" int buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                       const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream)
 {
-    return wg_launch(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, y, nullptr, stream);
+    return wg_launch(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, y, nullptr, stream, BUF_CYL_FORM_DEFAULT);
+}
+
+// The same with the form of the layers that carry bit 2 stated by the caller (BUF_CYL_FORM_*; stacks without bit 2 run as they do above)
+extern "C" int buf_cylindrical_net_wg_form(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
+                                           const int* cin_host, const int* cout_host, const int* relu_host, int form, float* y, void* stream)
+{
+    return wg_launch(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, y, nullptr, stream, form);
 }

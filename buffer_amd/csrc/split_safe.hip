@@ -16,16 +16,19 @@
 // desc f32[np,32] and y_or_equi = equi f32[np,32,140].  wt_split_host / wt_wg_host: the filters in the two kernels' tilings
 // (buf_split_tile_filters / buf_winograd_tile_weights; relu_host may carry the fp32 kernel's F(2x4) flag), bias_host shared.  flags_ws: DEVICE int32[np] (scratch; after the call
 // flags_ws[p] != 0 marks the patches that took the fp32 kernel).
-extern "C" int buf_cylindrical_net_split_safe(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
-                                              const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
-                                              const float* head_params, float* y_or_equi, float* desc, int* status_dev, int* flags_ws,
-                                              void* stream)
+// form: BUF_CYL_FORM_* of the fp32 re-run, as for buf_cylindrical_net_wg_form.
+extern "C" int buf_cylindrical_net_split_safe_form(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                                   const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                                   int form, const float* head_params, float* y_or_equi, float* desc, int* status_dev,
+                                                   int* flags_ws, void* stream)
 {
     BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "buf_cylindrical_net_split_safe: npatch=%d", npatch);
     if (npatch == 0) return BUF_OK;
     BUF_REQUIRE(x && y_or_equi && flags_ws && wt_split_host && wt_wg_host && bias_host && cin_host && cout_host && relu_host, BUF_EINVAL,
                 "buf_cylindrical_net_split_safe: null argument");
     BUF_REQUIRE(!head_params || desc, BUF_EINVAL, "buf_cylindrical_net_split_safe: head without desc");
+    BUF_REQUIRE(form >= BUF_CYL_FORM_DEFAULT && form <= BUF_CYL_FORM_PASS_SPLIT, BUF_EINVAL,
+                "buf_cylindrical_net_split_safe: form=%d (-1: the library's default, 0: K split, 1: pass split)", form);
     if (int rc = buf_cylindrical_net_wg_flags(cin_host, cout_host, relu_host)) return rc;       // the re-run must exist for these widths and take these relu words: before any device call
     hipStream_t s = (hipStream_t)stream;
     BUF_CHECK_HIP(hipMemsetAsync(flags_ws, 0, sizeof(int) * (size_t)npatch, s));
@@ -34,13 +37,22 @@ extern "C" int buf_cylindrical_net_split_safe(const float* x, int npatch, const 
     int rc = h3_launch(x, npatch, wt_split_host, bias_host, cin_host, cout_host, relu_split, head_params ? nullptr : y_or_equi, head_params,
                        desc, head_params ? y_or_equi : nullptr, status_dev, stream, flags_ws);
     if (rc) return rc;
-    rc = wg_launch(x, npatch, wt_wg_host, bias_host, cin_host, cout_host, relu_host, y_or_equi, flags_ws, stream);
+    rc = wg_launch(x, npatch, wt_wg_host, bias_host, cin_host, cout_host, relu_host, y_or_equi, flags_ws, stream, form);
     if (rc) return rc;
     if (head_params) {
         k_desc_head_masked<<<npatch, DH_THREADS, 0, s>>>(y_or_equi, head_params, desc, y_or_equi, flags_ws);
         BUF_LAUNCH_CHECK();
     }
     return BUF_OK;
+}
+
+extern "C" int buf_cylindrical_net_split_safe(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                              const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                              const float* head_params, float* y_or_equi, float* desc, int* status_dev, int* flags_ws,
+                                              void* stream)
+{
+    return buf_cylindrical_net_split_safe_form(x, npatch, wt_split_host, wt_wg_host, bias_host, cin_host, cout_host, relu_host, BUF_CYL_FORM_DEFAULT,
+                                               head_params, y_or_equi, desc, status_dev, flags_ws, stream);
 }
 
 // The cost net likewise: dense inputs (s_rows == null: s_eq, t_eq f32[m,32,5,20]) or the gathered form (s_eq = t_eq = equi

@@ -819,13 +819,14 @@ def winograd_f24_filters(w):
 
 
 F24_FLAG = 2          # relu_host[l] bit 1 of buf_cylindrical_net_wg: the layer's buffer holds the F(2x4) set behind the F(2x2) set
-F24K_FLAG = 4         # bit 2: the same for a layer with 64 output channels and Cin % 64 == 0 (the K-split form, k_cyl_net_w24k)
+F24K_FLAG = 4         # bit 2: the same for a layer with 64 output channels and Cin % 64 == 0 (k_cyl_net_w24k / k_cyl_net_w24p)
+F24P_DEFAULT = True   # the form of the bit-2 layers: pass split (k_cyl_net_w24p) | K split (k_cyl_net_w24k); profiles/f24p_ab.md
 
 
 def cyl_layer_filters(w, f24k=True):
     """The fp32 kernel's filter buffer of one layer and its F(2x4) flag: layers with 128 output channels run in the F(2x4) form
-    (flag 2) and, with f24k, so do the layers with 64 output channels whose Cin is a multiple of 64 (flag 4: the K-split form of
-    k_cyl_net_w24k); both carry that set behind the F(2x2) one."""
+    (flag 2) and, with f24k, so do the layers with 64 output channels whose Cin is a multiple of 64 (flag 4: k_cyl_net_w24k or
+    k_cyl_net_w24p, as the call's form says); both carry that set behind the F(2x2) one."""
     wt = winograd_tile_weights(w)
     cout, cin = w.shape[0], w.shape[1]
     if cout == 128:
@@ -838,15 +839,16 @@ def cyl_layer_filters(w, f24k=True):
 
 
 class CylindricalNet:
-    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip / csrc/convnet_w24k.hip: per layer U = G g G^T in
-    the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu word), biases."""
+    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip / csrc/convnet_w24k.hip / csrc/convnet_w24p.hip:
+    per layer U = G g G^T in the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu word), biases."""
 
-    def __init__(self, layers, device, f24=True, f24k=True):
+    def __init__(self, layers, device, f24=True, f24k=True, f24p=F24P_DEFAULT):
         """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  f24 = False: the F(2x2) form in every
         layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B); f24k = False: F(2x4) in the 128-output layers
-        only (k_cyl_net_w24)."""
+        only (k_cyl_net_w24); f24p: the flagged 64-output layers in the pass-split form (k_cyl_net_w24p), else K split (k_cyl_net_w24k)."""
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_wg"
+        self.form = 1 if f24p else 0
         flags = []
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
@@ -868,7 +870,7 @@ class CylindricalNet:
         x = x.contiguous()
         P = x.shape[0]
         y = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
-        check(L.buf_cylindrical_net_wg(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, _ptr(y), _stream()), self.entry)
+        check(L.buf_cylindrical_net_wg_form(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self.form, _ptr(y), _stream()), self.entry)
         return y
 
 
@@ -893,9 +895,10 @@ class CylindricalNetSplit:
     kernel.  For widths the fp32 kernel is not built for (the released network's are) the old contract stays: `check_range()` raises if
     the status word was set."""
 
-    def __init__(self, layers, device, f24k=True):
+    def __init__(self, layers, device, f24k=True, f24p=F24P_DEFAULT):
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_split"
+        self.form = 1 if f24p else 0                     # of the fp32 re-run, as in CylindricalNet
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
             self.wt.append(torch.from_numpy(split_tile_filters(w).view(np.int16)).to(device))
@@ -924,9 +927,9 @@ class CylindricalNetSplit:
         out = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
         desc = torch.empty((P, 32), dtype=torch.float32, device=x.device) if head is not None else None
         self.last_flags = torch.empty((max(P, 1),), dtype=torch.int32, device=x.device)
-        check(L.buf_cylindrical_net_split_safe(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe,
-                                               _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
-                                               _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe")
+        check(L.buf_cylindrical_net_split_safe_form(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self.form,
+                                                    _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
+                                                    _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe_form")
         return (desc, out) if head is not None else out
 
     def __call__(self, x):

@@ -316,6 +316,17 @@ int     buf_cylindrical_net_wg_flags(const int* cin_host, const int* cout_host, 
 int     buf_winograd_f24_tile_weights(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 24*Cout*Cin floats; Cout a multiple of 32 */
 int     buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream);
+/* The layers that carry bit 2 have two forms of the same arithmetic up to the order of summation: the K split above (k_cyl_net_w24k) and
+ * the pass split (csrc/convnet_w24p.hip, kernel k_cyl_net_w24p: each wavefront owns one row component of the F(2,3) row transform for all
+ * four N-tiles over the whole K, folds once and hands three N-tiles' partial outputs over through LDS).  Same buffers, same flags;
+ * `form` picks one per call (no process-wide state), BUF_CYL_FORM_DEFAULT what buf_cylindrical_net_wg runs: the pass split
+ * (profiles/f24p_ab.md).  A form outside -1..1 is
+ * BUF_EINVAL; a stack without bit 2 runs as it does through buf_cylindrical_net_wg. */
+#define BUF_CYL_FORM_DEFAULT (-1)
+#define BUF_CYL_FORM_K_SPLIT 0
+#define BUF_CYL_FORM_PASS_SPLIT 1
+int     buf_cylindrical_net_wg_form(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
+                                    const int* cin_host, const int* cout_host, const int* relu_host, int form, float* y, void* stream);
 int     buf_cylindrical_net_wg_supports(const int* cin_host, const int* cout_host);   /* host only: 0 if the kernel is built for these 8 widths */
 
 /* A11 (dense), split-f16 form -- the same stack with fp32-EQUIVALENT arithmetic on the f16 matrix pipe (csrc/convnet_h3.hip; opt-in,
@@ -353,6 +364,12 @@ int     buf_cylindrical_net_split_head(const float* x, int npatch, const void* c
 int     buf_cylindrical_net_split_safe(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                        const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                        const float* head_params, float* y_or_equi, float* desc, int* status_dev, int* flags_ws, void* stream);
+
+/* The same with the form of the fp32 re-run stated (BUF_CYL_FORM_*, as for buf_cylindrical_net_wg_form) */
+int     buf_cylindrical_net_split_safe_form(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                            const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                            int form, const float* head_params, float* y_or_equi, float* desc, int* status_dev, int* flags_ws,
+                                            void* stream);
 
 /* A11 (head)  attention pooling + normalisation (models/patch_embedder.py:66-72,81-84): pool_layer
  * (Conv2d 1x1 32->16 + BN + ReLU, Conv2d 1x1 16->1 + BN + ReLU), desc = normalize(mean(y * w)),
