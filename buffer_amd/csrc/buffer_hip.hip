@@ -26,6 +26,7 @@
 #include "convnet_w24.hip"
 #include "convnet_w24k.hip"
 #include "convnet_w24p.hip"
+#include "convnet_w24a.hip"
 #include "costnet.hip"
 #include "split_safe.hip"
 #include "fpfh.hip"

@@ -47,18 +47,8 @@
 // them).
 #define W24P_MFMA(PRE, ACC, A, B) asm volatile(PRE "v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(ACC) : "v"(A), "v"(B));
 
-// Row component `I = w` over `niter` x 4 k-steps for all four N-tiles: acc[n][j] += V_Ij(tile, c) * U_Ij(c, n).  w24_pass's steps and
-// fences with four N-tiles behind one transform and the LDS reads ONE step ahead (step s reads the words of step s + 1, runs its
-// 24 MFMAs, then forms the operands of step s + 1); P0 / P1: the two window rows (da, db), sgn: the sign of db.
-// On entry W holds the first two k-steps of the blocks at wp0 (N-tiles 0, 1) and wp1 (N-tiles 2, 3); the last iteration fetches the
-// k-steps 0, 1 at wp_next into every ring slot instead (unused by the pass-split layer, in bounds).
-__device__ __forceinline__ void w24p_pass(unsigned P0, unsigned P1, float sgn, __amdgpu_buffer_rsrc_t rs, unsigned wp0, unsigned wp1, unsigned wp_next,
-                                          unsigned lofs4, unsigned lofs2, int niter, wgf4 (&W4)[4][2], wgf2 (&W2)[4][2], wgf4 (&acc)[4][6])
-{
-    wgf2 D[6];                                       // one k-step of window words in flight: a k-step is 24 matrix instructions long
-    float V[2][6];
-    W24_LOAD(D, P0, P1, 0)
-    // row component da + sgn db of the six words, then B4^T as in w24_pass
+// Row component da + sgn db of the six window words in D (one v_fma per word), then B4^T as in w24_pass, into V[BUF]; uses the caller's
+// D, V and sgn.  Shared with w24a_pass (csrc/convnet_w24a.hip).
 #define W24P_XFORM(BUF)                                                                                   \
     {                                                                                                     \
         float r_[6];                                                                                      \
@@ -71,6 +61,18 @@ __device__ __forceinline__ void w24p_pass(unsigned P0, unsigned P1, float sgn, _
         V[BUF][3] = __builtin_fmaf(2.f, e_, c_); V[BUF][4] = __builtin_fmaf(-2.f, e_, c_);                \
         V[BUF][5] = __builtin_fmaf(-4.f, e_, wg_sub(r_[5], r_[3]));                                       \
     }
+
+// Row component `I = w` over `niter` x 4 k-steps for all four N-tiles: acc[n][j] += V_Ij(tile, c) * U_Ij(c, n).  w24_pass's steps and
+// fences with four N-tiles behind one transform and the LDS reads ONE step ahead (step s reads the words of step s + 1, runs its
+// 24 MFMAs, then forms the operands of step s + 1); P0 / P1: the two window rows (da, db), sgn: the sign of db.
+// On entry W holds the first two k-steps of the blocks at wp0 (N-tiles 0, 1) and wp1 (N-tiles 2, 3); the last iteration fetches the
+// k-steps 0, 1 at wp_next into every ring slot instead (unused by the pass-split layer, in bounds).
+__device__ __forceinline__ void w24p_pass(unsigned P0, unsigned P1, float sgn, __amdgpu_buffer_rsrc_t rs, unsigned wp0, unsigned wp1, unsigned wp_next,
+                                          unsigned lofs4, unsigned lofs2, int niter, wgf4 (&W4)[4][2], wgf2 (&W2)[4][2], wgf4 (&acc)[4][6])
+{
+    wgf2 D[6];                                       // one k-step of window words in flight: a k-step is 24 matrix instructions long
+    float V[2][6];
+    W24_LOAD(D, P0, P1, 0)
     W24P_XFORM(0)
     int it = 0;
 #pragma unroll 1
@@ -108,7 +110,6 @@ __device__ __forceinline__ void w24p_pass(unsigned P0, unsigned P1, float sgn, _
             __builtin_amdgcn_sched_barrier(0);
         }
     } while (++it < niter);
-#undef W24P_XFORM
     // The last matrix instructions' results (8 passes each) before anything reads them: the operands make every read wait for this
     // statement.  (In the loop the transform and the reloads of a step stand behind its matrix instructions as well.)
     asm volatile("s_nop 15"
@@ -118,7 +119,9 @@ __device__ __forceinline__ void w24p_pass(unsigned P0, unsigned P1, float sgn, _
 // Output row 6, columns 0..15 of ONE N-tile in the direct form: w24_round_direct's steps, pipeline and summation order (one
 // accumulator per azimuth tap, the filter rows a = 0, 1 add up in it, K ascending; y = 4 acc_0 - 3 acc_1 + acc_2, the bias starts in
 // acc_2).  The six MFMAs of a k-step go round the three accumulators twice, so none waits for its predecessor.
-// wp: block 0 of the N-tile's pair plus 256 n2; W0: its first two k-steps.
+// wp: block 0 of the N-tile's pair plus 256 n2; W0: its first two k-steps.  NOBIAS: bias_lane may be null (the upper K half of
+// w24a_layer_psplit32, csrc/convnet_w24a.hip, carries no bias).
+template <bool NOBIAS = false>
 __device__ __forceinline__ void w24p_round_direct(unsigned row5, __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned lofs, int niter, unsigned pstride,
                                                   const float* __restrict__ bias_lane, const wgf4 (&W0)[2], wgf4& Y)
 {
@@ -139,7 +142,8 @@ __device__ __forceinline__ void w24p_round_direct(unsigned row5, __amdgpu_buffer
     asm volatile("" : "+v"(zero));
     acc[0] = (wgf4){ zero, zero, zero, zero };
     acc[1] = (wgf4){ zero, zero, zero, zero };
-    acc[2] = *reinterpret_cast<const wgf4*>(bias_lane);
+    if constexpr (NOBIAS) acc[2] = bias_lane ? *reinterpret_cast<const wgf4*>(bias_lane) : (wgf4){ zero, zero, zero, zero };
+    else acc[2] = *reinterpret_cast<const wgf4*>(bias_lane);
     float G[6];
 #define W24P_TAPS(SLOT)                                                                                   \
     {                                                                                                     \

@@ -774,7 +774,8 @@ extern "C" int buf_winograd_tile_weights(const float* w_host, int cout, int cin,
 extern "C" int buf_winograd_group(int cin, int cout) { return wg_group(cin, cout); }
 
 // The widths k_cyl_net_wg is built for, stated once: what buf_cylindrical_net_wg accepts and buf_cylindrical_net_wg_supports reports.
-static int wg_check_widths(const int* cin, const int* cout)
+// follow: the rule that only 32-output layers follow a 32-output layer (buf_cylindrical_net_wg_all states it per layer form instead).
+static int wg_check_widths(const int* cin, const int* cout, bool follow = true)
 {
     for (int l = 0; l < WG_LAYERS; l++) {
         const int ci = cin[l], co = cout[l];
@@ -787,7 +788,7 @@ static int wg_check_widths(const int* cin, const int* cout)
         BUF_REQUIRE(l == 0 || ci == cout[l - 1], BUF_EINVAL, "buf_cylindrical_net_wg: layer %d width mismatch", l);
         // The 32-output layers hand their K-split partial sums over through the rows of the channels 64..95, zero words included
         // (wg_layer_mksplit); those words are written once at kernel start, so no wider layer may follow.
-        BUF_REQUIRE(l == 0 || cout[l - 1] != 32 || co == 32, BUF_EINVAL,
+        BUF_REQUIRE(!follow || l == 0 || cout[l - 1] != 32 || co == 32, BUF_EINVAL,
                     "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (only 32-output layers may follow a 32-output layer)", l, ci, co);
     }
     BUF_REQUIRE(cout[WG_LAYERS - 1] == 32, BUF_EINVAL, "buf_cylindrical_net_wg: the last layer must have 32 channels");

@@ -821,6 +821,11 @@ def winograd_f24_filters(w):
 F24_FLAG = 2          # relu_host[l] bit 1 of buf_cylindrical_net_wg: the layer's buffer holds the F(2x4) set behind the F(2x2) set
 F24K_FLAG = 4         # bit 2: the same for a layer with 64 output channels and Cin % 64 == 0 (k_cyl_net_w24k / k_cyl_net_w24p)
 F24P_DEFAULT = True   # the form of the bit-2 layers: pass split (k_cyl_net_w24p) | K split (k_cyl_net_w24k); profiles/f24p_ab.md
+# What a net built without a form argument runs (k_cyl_net_w24a, csrc/convnet_w24a.hip; profiles/f24a_ab.md): F(2x4) tiles in 'all'
+# layers; 'out64': only in the 64-output layers k_cyl_net_w24p leaves in the F(2x2) form (the released stack: layer 0); 'out32': only in the
+# 32-output layers; 'off' or None: k_cyl_net_w24p as it is.  The argument f24a= of the two classes picks one per net.
+F24A_DEFAULT = 'all'
+F24A_PARTS = {'all': (64, 32), 'out64': (64,), 'out32': (32,), 'off': (), None: ()}
 
 
 def cyl_layer_filters(w, f24k=True):
@@ -838,14 +843,45 @@ def cyl_layer_filters(w, f24k=True):
     return np.concatenate([wt, winograd_f24_tile_weights(w)]), flag
 
 
-class CylindricalNet:
-    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip / csrc/convnet_w24k.hip / csrc/convnet_w24p.hip:
-    per layer U = G g G^T in the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu word), biases."""
+def cyl_f24a_parts(f24, f24k, f24p, f24a):
+    """The output widths whose unflagged layers get an F(2x4) set of their own (k_cyl_net_w24a), and the three older arguments with
+    their defaults filled in.  An explicit f24 / f24k / f24p asks for one of the older kernels: no such layers then."""
+    explicit = not (f24 is None and f24k is None and f24p is None)
+    f24, f24k, f24p = (True if f24 is None else f24), (True if f24k is None else f24k), (F24P_DEFAULT if f24p is None else f24p)
+    if f24a is None:
+        f24a = None if explicit else F24A_DEFAULT
+    if f24a is True:
+        f24a = 'all'
+    if f24a is False:
+        f24a = 'off'
+    if f24a not in F24A_PARTS:
+        raise ValueError(f"f24a = {f24a!r}: one of 'all', 'out64', 'out32', 'off'")
+    if F24A_PARTS[f24a] and not (f24 and f24k and f24p):
+        raise ValueError("f24a goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
+    return f24, f24k, f24p, F24A_PARTS[f24a]
 
-    def __init__(self, layers, device, f24=True, f24k=True, f24p=F24P_DEFAULT):
-        """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  f24 = False: the F(2x2) form in every
+
+def cyl_f24a_filters(layers, flags, parts, device):
+    """Per layer the F(2x4) set in a buffer of its own (a tensor on `device`) where the layer carries no F(2x4) flag and has one of the
+    output widths `parts`, else None; and the pointer array buf_cylindrical_net_wg_all takes."""
+    sets = [torch.from_numpy(winograd_f24_tile_weights(w)).to(device)
+            if (flag == 0 and w.shape[0] in parts and w.shape[0] in (32, 64) and w.shape[1] % 16 == 0) else None
+            for (w, _, _), flag in zip(layers, flags)]
+    return sets, (C.c_void_p * len(sets))(*[None if t is None else t.data_ptr() for t in sets])
+
+
+class CylindricalNet:
+    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip / csrc/convnet_w24k.hip / csrc/convnet_w24p.hip /
+    csrc/convnet_w24a.hip: per layer U = G g G^T in the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu
+    word; for k_cyl_net_w24a the remaining layers' F(2x4) sets in buffers of their own, `wt24`), biases."""
+
+    def __init__(self, layers, device, f24=None, f24k=None, f24p=None, f24a=None):
+        """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  No form argument: k_cyl_net_w24a with F(2x4)
+        tiles in every layer (F24A_DEFAULT; f24a = 'all' | 'out64' | 'out32' | 'off' picks the parts).  An explicit f24, f24k or f24p gives
+        one of the older kernels with the defaults f24 = f24k = True, f24p = F24P_DEFAULT: f24 = False: the F(2x2) form in every
         layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B); f24k = False: F(2x4) in the 128-output layers
         only (k_cyl_net_w24); f24p: the flagged 64-output layers in the pass-split form (k_cyl_net_w24p), else K split (k_cyl_net_w24k)."""
+        f24, f24k, f24p, parts = cyl_f24a_parts(f24, f24k, f24p, f24a)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_wg"
         self.form = 1 if f24p else 0
@@ -863,6 +899,10 @@ class CylindricalNet:
         self._ci = (C.c_int * n)(*self.cin)
         self._co = (C.c_int * n)(*self.cout)
         self._re = (C.c_int * n)(*[r | f for r, f in zip(self.relu, flags)])
+        # the layers k_cyl_net_w24a runs on an F(2x4) set of their own; f24_all: every layer of the stack runs on F(2x4) tiles
+        self.wt24, self._w24p = cyl_f24a_filters(layers, flags, parts, device)
+        self.f24_layers = [l for l, t in enumerate(self.wt24) if t is not None]
+        self.f24_all = bool(self.f24_layers) and all(f or t is not None for f, t in zip(flags, self.wt24))
 
     def __call__(self, x):
         """x f32[P,16,420] (or [P,48,140]) -> f32[P,32,7,20]"""
@@ -870,6 +910,10 @@ class CylindricalNet:
         x = x.contiguous()
         P = x.shape[0]
         y = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
+        if self.f24_layers:
+            check(L.buf_cylindrical_net_wg_all(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self._w24p, _ptr(y), _stream()),
+                  "buf_cylindrical_net_wg_all")
+            return y
         check(L.buf_cylindrical_net_wg_form(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self.form, _ptr(y), _stream()), self.entry)
         return y
 
@@ -895,9 +939,12 @@ class CylindricalNetSplit:
     kernel.  For widths the fp32 kernel is not built for (the released network's are) the old contract stays: `check_range()` raises if
     the status word was set."""
 
-    def __init__(self, layers, device, f24k=True, f24p=F24P_DEFAULT):
+    def __init__(self, layers, device, f24k=None, f24p=None, f24a=None):
+        """f24k, f24p, f24a: the fp32 re-run's kernel, as in CylindricalNet (no form argument: k_cyl_net_w24a_rerun)"""
+        _, f24k, f24p, parts = cyl_f24a_parts(None, f24k, f24p, f24a)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_split"
+        self.f24_layers, self.f24_all = [], False
         self.form = 1 if f24p else 0                     # of the fp32 re-run, as in CylindricalNet
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
@@ -919,6 +966,9 @@ class CylindricalNetSplit:
             self.wt_wg = [torch.from_numpy(wt).to(device) for wt, _ in tiled]
             self._wwp = (C.c_void_p * n)(*[t.data_ptr() for t in self.wt_wg])
             self._re_safe = (C.c_int * n)(*[r | f for r, (_, f) in zip(self.relu, tiled)])     # (the split kernel itself takes 0 / 1)
+            self.wt24, self._w24p = cyl_f24a_filters(layers, [f for _, f in tiled], parts, device)
+            self.f24_layers = [l for l, t in enumerate(self.wt24) if t is not None]
+            self.f24_all = bool(self.f24_layers) and all(f or t is not None for (_, f), t in zip(tiled, self.wt24))
 
     def _safe_call(self, x, head):
         L = _lib.lib()
@@ -927,6 +977,11 @@ class CylindricalNetSplit:
         out = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
         desc = torch.empty((P, 32), dtype=torch.float32, device=x.device) if head is not None else None
         self.last_flags = torch.empty((max(P, 1),), dtype=torch.int32, device=x.device)
+        if self.f24_layers:
+            check(L.buf_cylindrical_net_split_safe_all(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self._w24p,
+                                                       _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
+                                                       _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe_all")
+            return (desc, out) if head is not None else out
         check(L.buf_cylindrical_net_split_safe_form(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self.form,
                                                     _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
                                                     _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe_form")

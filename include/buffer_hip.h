@@ -328,6 +328,21 @@ int     buf_cylindrical_net_wg(const float* x, int npatch, const float* const* w
 int     buf_cylindrical_net_wg_form(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                     const int* cin_host, const int* cout_host, const int* relu_host, int form, float* y, void* stream);
 int     buf_cylindrical_net_wg_supports(const int* cin_host, const int* cout_host);   /* host only: 0 if the kernel is built for these 8 widths */
+/* F(2x4) tiles in EVERY layer (csrc/convnet_w24a.hip, kernel k_cyl_net_w24a): buf_cylindrical_net_wg with one more array.  wt_host,
+ * bias_host and relu_host are exactly what buf_cylindrical_net_wg takes (same buffers, same words, same rules and messages for the words).
+ * wt24_host[8]: per layer null, or the 24*Cout*Cin floats of buf_winograd_f24_tile_weights ([pair][i][k-step][768]) in a buffer of their
+ * own -- allowed on a layer that carries neither BUF_CYL_F24 nor BUF_CYL_F24K and has 64 or 32 output channels, else BUF_EINVAL.  A
+ * 64-output layer with a set runs the pass-split form of k_cyl_net_w24p (any Cin that is a multiple of 16: layer 0's 48), a 32-output
+ * layer with a set the pass split over its one N-tile pair; a layer without a set runs as it does in k_cyl_net_w24p.  The widths rules
+ * are those of buf_cylindrical_net_wg_supports with one change: the rule "only 32-output layers follow a 32-output layer" binds from the
+ * first 32-output layer WITHOUT a set on, to the end of the stack (its form leaves partial sums in zero words that later, wider layers
+ * would read as padding); behind 32-output layers that all have their sets any supported layer may follow.  All checks happen before
+ * the first device call; buf_cylindrical_net_wg_all_flags reports on the host what a call would accept (of wt24_host it looks only at
+ * which entries are null).  Timed under BUF_TIMED_CYL_NET with the dense flop figure. */
+int     buf_cylindrical_net_wg_all_flags(const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host);
+int     buf_cylindrical_net_wg_all(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
+                                   const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
+                                   float* y, void* stream);
 
 /* A11 (dense), split-f16 form -- the same stack with fp32-EQUIVALENT arithmetic on the f16 matrix pipe (csrc/convnet_h3.hip; opt-in,
  * the all-fp32 kernel above stays the default): every fp32 operand is split once into hi = f16(x) and lo' = f16((x - hi) 2^11)
@@ -370,6 +385,12 @@ int     buf_cylindrical_net_split_safe_form(const float* x, int npatch, const vo
                                             const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                             int form, const float* head_params, float* y_or_equi, float* desc, int* status_dev, int* flags_ws,
                                             void* stream);
+/* The same with the fp32 re-run through k_cyl_net_w24a_rerun: wt24_host as for buf_cylindrical_net_wg_all (a flagged patch is bit-identical
+ * to that entry point's result) */
+int     buf_cylindrical_net_split_safe_all(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                           const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                           const float* const* wt24_host, const float* head_params, float* y_or_equi, float* desc,
+                                           int* status_dev, int* flags_ws, void* stream);
 
 /* A11 (head)  attention pooling + normalisation (models/patch_embedder.py:66-72,81-84): pool_layer
  * (Conv2d 1x1 32->16 + BN + ReLU, Conv2d 1x1 16->1 + BN + ReLU), desc = normalize(mean(y * w)),
