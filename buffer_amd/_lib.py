@@ -121,6 +121,9 @@ _SIGNATURES = {
     "buf_fgr_ws_bytes": (_sz, [_i, _i, _i]),
     "buf_fgr_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.c_double, _i, _i, C.c_double, C.c_double, _i, C.c_double, _i, _i,
                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "buf_sc2_ws_bytes": (_sz, [_vp, _i, _i]),
+    "buf_sc2_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i,
+                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "buf_match_metrics": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "buf_row_linear": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "buf_segment_instance_norm_ws_bytes": (_sz, [_i, _i]),

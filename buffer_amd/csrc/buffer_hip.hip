@@ -31,3 +31,4 @@
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "fgr.hip"
+#include "sc2.hip"

@@ -168,9 +168,10 @@ def add_descriptor_args(ap):
                     help='buffer: the learned path (default).  fpfh: the classical baseline on the same pairs, thresholds and logs -- FPFH on '
                          'the second-level clouds, mutual matches, RANSAC (buffer_amd/fpfh.py); no calibration, no --stage-metrics; the '
                          'summary carries "descriptor"')
-    ap.add_argument('--estimator', default='ransac', choices=('ransac', 'fgr'),
+    ap.add_argument('--estimator', default='ransac', choices=('ransac', 'fgr', 'sc2'),
                     help='the pose estimator of --descriptor fpfh.  ransac: seeded 3-point hypotheses (default).  fgr: Fast Global Registration '
-                         'on the same matches, one batched call per chunk (buffer_amd/fgr.py); the summary carries "estimator"')
+                         'on the same matches, one batched call per chunk (buffer_amd/fgr.py).  sc2: SC2-PCR, the deterministic second-order '
+                         'spatial-compatibility consensus, one batched call per chunk (buffer_amd/sc2.py); the summary carries "estimator"')
 
 
 def parse_with_preset(ap, argv, driver_name):
@@ -201,7 +202,7 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     summarize(poses) -> the driver's own figures, the common ones, --by-overlap under the driver's (rte, rre) thresholds and
     --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
     --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor" and
-    "estimator", --estimator choosing its RANSAC or its Fast Global Registration).
+    "estimator", --estimator choosing its RANSAC, its Fast Global Registration or its SC2-PCR).
     --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
     unrefined poses.
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""

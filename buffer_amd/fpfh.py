@@ -5,8 +5,9 @@ from its published form (include/buffer_hip.h, N6; parity unpinned).
 
     compute_fpfh        descriptors of one or several stacked clouds: one cell grid, one radius query, one launch pair
     match               (mutual) 1-NN matches of two descriptor sets through ops.knn (d = 33: the exact fp32 scan)
-    FpfhRegistration    estimator='ransac' (default) or 'fgr' (buffer_amd/fgr.py: one batched Fast Global Registration call per
-                        batch on the concatenated match lists); register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
+    FpfhRegistration    estimator='ransac' (default), 'fgr' (buffer_amd/fgr.py: one batched Fast Global Registration call per
+                        batch on the concatenated match lists) or 'sc2' (buffer_amd/sc2.py: one batched SC2-PCR call per batch on the
+                        same lists); register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
                         clouds and normals of driver.upload's dicts
 """
 import numpy as np
@@ -15,6 +16,7 @@ import torch
 from . import ops
 
 ESTIMATORS = ('ransac', 'fgr')
+ALL_ESTIMATORS = ESTIMATORS + ('sc2',)
 
 
 def compute_fpfh(points, normals, radius, max_nn=100, lengths=None):
@@ -64,14 +66,17 @@ class FpfhRegistration:
     """FPFH + mutual matching + RANSAC (+ ICP) with BufferPipeline's calling convention.  radius = radius_factor * cfg.voxel_size_0
     (the usual 5 voxels), RANSAC inlier distance = dist_factor * cfg.voxel_size_0, cfg.ransac_hypotheses hypotheses.
     estimator='fgr': Fast Global Registration instead of the RANSAC, on the same matches and seeds, with the paper's delta = the same
-    dist_factor * cfg.voxel_size_0 in the clouds' units and open3d's defaults otherwise."""
+    dist_factor * cfg.voxel_size_0 in the clouds' units and open3d's defaults otherwise.
+    estimator='sc2': SC2-PCR on the same matches (no seeds: it is deterministic), with d_thr = inlier_thr = the same
+    dist_factor * cfg.voxel_size_0, no non-maximum suppression and Sc2Options' defaults otherwise; a pair with more than
+    ops.SC2_MAX_ROWS (16 384) matches is an error, not a truncation."""
 
     def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac'):
         self.cfg, self.device = cfg, torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('FpfhRegistration runs on a HIP device only (no CPU path)')
-        if estimator not in ESTIMATORS:
-            raise ValueError(f'FpfhRegistration: unknown estimator {estimator!r} (one of {ESTIMATORS})')
+        if estimator not in ALL_ESTIMATORS:
+            raise ValueError(f'FpfhRegistration: unknown estimator {estimator!r} (one of {ALL_ESTIMATORS})')
         self.estimator = estimator
         self.radius = float(radius_factor) * cfg.voxel_size_0
         self.max_nn, self.max_dist, self.edge_similarity = int(max_nn), float(dist_factor) * cfg.voxel_size_0, float(edge_similarity)
@@ -101,6 +106,8 @@ class FpfhRegistration:
         off = np.concatenate([[0], np.cumsum(lens)])
         if self.estimator == 'fgr':
             return self._fgr_batch(pts, lens, off, F, seeds)
+        if self.estimator == 'sc2':
+            return self._sc2_batch(pts, lens, off, F)
         out = []
         for b in range(B):
             s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
@@ -109,17 +116,31 @@ class FpfhRegistration:
                                          self.edge_similarity))
         return out
 
-    def _fgr_batch(self, pts, lens, off, F, seeds):
-        """the matches of every pair (pair by pair, as the RANSAC path matches), then ONE fgr_batched call for the batch"""
-        from . import fgr
+    @staticmethod
+    def _batch_matches(pts, lens, off, F):
+        """the matches of every pair (pair by pair, as the RANSAC path matches) and the two sides stacked apart (the pairs' clouds
+        alternate in pts: src, tgt, src, ...) -> (src, tgt, list of corr)"""
         B = len(lens) // 2
         corrs = []
         for b in range(B):
             s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
             corrs.append(match(F[s0:t0], F[t0:t1], True))
-        # the pairs' clouds alternate in pts (src, tgt, src, ...): the kernel takes the two sides stacked apart
         src = torch.cat([pts[int(off[2 * b]):int(off[2 * b + 1])] for b in range(B)])
         tgt = torch.cat([pts[int(off[2 * b + 1]):int(off[2 * b + 2])] for b in range(B)])
+        return src, tgt, corrs
+
+    def _sc2_batch(self, pts, lens, off, F):
+        """the matches of every pair, then ONE sc2_batched call for the batch"""
+        from . import sc2
+        src, tgt, corrs = self._batch_matches(pts, lens, off, F)
+        res = sc2.sc2_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
+                                   d_thr=self.max_dist, inlier_thr=self.max_dist, nms_radius=0.0)
+        return list(res['poses'].float().unbind(0))
+
+    def _fgr_batch(self, pts, lens, off, F, seeds):
+        """the matches of every pair (pair by pair, as the RANSAC path matches), then ONE fgr_batched call for the batch"""
+        from . import fgr
+        src, tgt, corrs = self._batch_matches(pts, lens, off, F)
         res = fgr.fast_global_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
                                            seeds=[int(s) & ops._MASK64 for s in seeds], maximum_correspondence_distance=self.max_dist,
                                            delta_absolute=True)

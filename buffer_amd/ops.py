@@ -637,6 +637,53 @@ def fgr_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, seeds=No
     return T, info, rows, weights
 
 
+SC2_STATUS = ('NOTHING', 'OK')                                                                  # BUF_SC2_* of buffer_hip.h
+SC2_MAX_ROWS, SC2_MAX_SEEDS, SC2_MAX_K1 = 16384, 1024, 128
+
+
+def sc2_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, d_thr, inlier_thr, seed_ratio=0.2, max_seeds=512, k1=30,
+                nms_radius=0.0, power_iterations=10, refine_iterations=20, return_detail=False):
+    """buf_sc2_batched: SC2-PCR (second order spatial compatibility, single stage) of the pairs stacked in src f32[sum src_lengths,3] /
+    tgt f32[sum tgt_lengths,3] on the correspondences corr int32[sum corr_lengths,2] ((src row, tgt row) inside the pair's own
+    clouds); deterministic, no seeds -> (T f64[B,4,4] src -> tgt, info int32[B,6] = (index into SC2_STATUS, live rows, seeds, the
+    winner's row, its inlier count before refinement, the final count), detail), all on the device, nothing read back.  detail is None
+    or, with return_detail=True, dict(confidence f64[sum n] (NaN on dead rows), seeds int32[B,max_seeds] and hyp_counts
+    int32[B,max_seeds] (by rank, tail -1), counts int32[max_seeds * sum n] (pair b's block at max_seeds * its first row, rank r at
+    + r n_b), inlier_mask uint8[sum n])."""
+    L = _lib.lib()
+    src, tgt = _dev(src, torch.float32, "sc2_batched.src"), _dev(tgt, torch.float32, "sc2_batched.tgt")
+    corr = _dev(corr, torch.int32, "sc2_batched.corr")
+    sl, tl, cl = _host_i32(src_lengths), _host_i32(tgt_lengths), _host_i32(corr_lengths)
+    B, dev = int(sl.shape[0]), src.device
+    if tl.shape[0] != B or cl.shape[0] != B:
+        raise ValueError(f"sc2_batched: {B} source lengths but {tl.shape[0]} target and {cl.shape[0]} correspondence lengths")
+    for name, t, ln, w in (("src", src, sl, 3), ("tgt", tgt, tl, 3), ("corr", corr, cl, 2)):
+        if t.dim() != 2 or t.shape[1] != w:
+            raise ValueError(f"sc2_batched: {name} {tuple(t.shape)} is not [N,{w}]")
+        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
+            raise ValueError(f"sc2_batched: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    if B and int(cl.max()) > SC2_MAX_ROWS:
+        raise ValueError(f"sc2_batched: {int(cl.max())} correspondences in one pair (at most {SC2_MAX_ROWS})")
+    if not (1 <= int(max_seeds) <= SC2_MAX_SEEDS) or not (3 <= int(k1) <= SC2_MAX_K1):
+        raise ValueError(f"sc2_batched: max_seeds={max_seeds} (1..{SC2_MAX_SEEDS}), k1={k1} (3..{SC2_MAX_K1})")
+    ms, n = int(max_seeds), int(corr.shape[0])
+    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
+    info = torch.zeros((B, 6), dtype=torch.int32, device=dev)
+    detail = None
+    if return_detail:
+        detail = dict(confidence=torch.empty(n, dtype=torch.float64, device=dev), seeds=torch.empty((B, ms), dtype=torch.int32, device=dev),
+                      hyp_counts=torch.empty((B, ms), dtype=torch.int32, device=dev),
+                      counts=torch.empty(ms * n, dtype=torch.int32, device=dev), inlier_mask=torch.empty(n, dtype=torch.uint8, device=dev))
+    d = detail or {}
+    nbytes = max(L.buf_sc2_ws_bytes(_hptr(cl), B, ms), 1) if B else 1
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_sc2_batched(_ptr(src), _hptr(sl), _ptr(tgt), _hptr(tl), _ptr(corr), _hptr(cl), B, float(d_thr), float(inlier_thr),
+                            float(seed_ratio), ms, int(k1), float(nms_radius), int(power_iterations), int(refine_iterations), _ptr(T),
+                            _ptr(info), _ptr(d.get('confidence')), _ptr(d.get('seeds')), _ptr(d.get('hyp_counts')), _ptr(d.get('counts')),
+                            _ptr(d.get('inlier_mask')), _ptr(ws), nbytes, _stream()), "buf_sc2_batched")
+    return T, info, detail
+
+
 def pair_stats(points, lengths, pair_src, pair_tgt, T, radius, correspondences=False, cells_per_elem=0):
     """buf_pair_stats: statistics of P pairs over the C clouds stacked in points f32[sum lengths,3] under given transforms, one cell
     grid per call, nothing read back.  pair_src / pair_tgt host int[P] (cloud indices), T f64[P,4,4] (device) mapping the source

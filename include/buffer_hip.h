@@ -62,7 +62,12 @@ int         buf_device_count(void);
 #define BUF_TIMED_COST_NET_SPLIT 11  /* A13, split-f16 form */
 #define BUF_TIMED_SPFH           12  /* N6 k_spfh: work = n * (24 + 4*k_nbr + 24*K + 264) bytes, K = min(max_nn, k_nbr) (an upper bound: rows are shorter) */
 #define BUF_TIMED_FPFH           13  /* N6 k_fpfh: work = n * K * 264 bytes, the SPFH gather at full rows (an upper bound as well) */
-#define BUF_TIMED_NKERNELS       14
+#define BUF_TIMED_SC2_COMPAT     14  /* N8 k_sc2_gather + k_sc2_compat: work = sum n^2 pairs of rows */
+#define BUF_TIMED_SC2_CONF       15  /* N8 the power iteration, k_sc2_conf and k_sc2_seeds: work = power_iterations * sum n^2 */
+#define BUF_TIMED_SC2_COUNTS     16  /* N8 k_sc2_counts: work = 8 * sum (seed groups * n * words) bytes of bit rows streamed */
+#define BUF_TIMED_SC2_HYP        17  /* N8 k_sc2_hyp: work = seed ranks launched */
+#define BUF_TIMED_SC2_REFINE     18  /* N8 k_sc2_refine: work = pairs */
+#define BUF_TIMED_NKERNELS       19
 void        buf_timing_enable(int on);
 long long   buf_timing_collect(double* total_ms, double* total_bytes);
 long long   buf_timing_collect_kernel(int kernel_id, double* total_ms, double* total_work);
@@ -622,6 +627,63 @@ int     buf_fgr_batched(const float* src, const int* src_lengths_host, const flo
                         double division_factor, int decrease_every, int iterations,    /* 1.4, 4, 64 */
                         double* T_out /* f64[B,4,4] src -> tgt */, int* info_out /* int32[B,4] */,
                         int* rows_out /* nullable int32[B,3*max_tuples,2] */, double* weights_out /* nullable f64[B,3*max_tuples] */,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/* N8  SC2-PCR (Chen, Sun, Yang, Tao, "SC^2-PCR: A Second Order Spatial Compatibility for Efficient and Robust Point Cloud
+ * Registration", CVPR 2022), the single-stage form: a deterministic consensus estimator on given correspondences, the third pose
+ * estimator of the classical row.  No SC2-PCR source was at hand: the algorithm is restated from its published form, parity with any
+ * other implementation is unpinned and this text is the specification.  The paper's second sampling stage (k2) and its learned
+ * variants are not provided.  B pairs per call, 8 + power_iterations launches on the caller's stream, nothing read back.
+ * Pair b owns src_lengths_host[b] / tgt_lengths_host[b] consecutive rows of src / tgt (f32[.,3], device) and n = corr_lengths_host[b]
+ * consecutive rows of corr (int32[.,2], device: (src row, tgt row) inside the pair's own clouds); row i is (p_i, q_i), promoted to
+ * fp64.  A row is DEAD if an index is outside its cloud or a coordinate is not finite: its row and column of both compatibility
+ * matrices are zero, the diagonal included, and it is never a seed, a set member or an inlier.  All arithmetic is IEEE fp64, every
+ * product, sum, division and square root rounded once in the written order, without FMA.
+ *   d(a, b) = sqrt(((ax-bx)^2 + (ay-by)^2) + (az-bz)^2);  e_ij = |d(p_i, p_j) - d(q_i, q_j)|.
+ *   Hard compatibility C_ij = (e_ij <= d_thr), kept as a BIT MATRIX of n x ceil(n / 64) 64-bit words per pair (bit j % 64 of word
+ *   j / 64 of row i; C is symmetric, so row j serves as column j).  Soft compatibility s_ij = max(0, 1 - (e_ij e_ij) / (d_thr d_thr))
+ *   (d_thr d_thr formed once on the host); it is recomputed from the points wherever it is used and is exactly 0 where C_ij = 0.
+ *   Confidence: v = 1 on the live rows, then power_iterations times v <- S v and v <- v / max v.  v_i is summed in a fixed shape: the
+ *   columns in tiles of 128, tile t into partial sum t % 4 in ascending order, v_i = (s0 + s1) + (s2 + s3).
+ *   Non-maximum suppression (nms_radius > 0): c_i = v_i unless a live j with d(p_i, p_j) <= nms_radius has v_j > v_i, then c_i = -1;
+ *   nms_radius == 0: c = v.
+ *   Seeds: S = min(max_seeds, max(1, ceil(seed_ratio n))) (n = all rows of the pair); the seeds are the S rows of largest c, ties to
+ *   the lowest row, only those with c > 0; a seed's rank is its place in that order.
+ *   Second-order counts of seed s: K[s, j] = C[s, j] * sum_k C[s, k] C[k, j] = the population count of (row s AND row j), masked by
+ *   bit j of row s.  Its consensus set: the k1 columns of largest K, ties to the lowest column, only K > 0, in that order; fewer than
+ *   3 members: no hypothesis, count -1.
+ *   Hypothesis: weights w = 1 on the set, power_iterations times w <- S_set w (ascending set order), w <- w / max w; with
+ *   u = w / sum w: cp = sum u p, cq = sum u q, H = sum u ((p - cp)(q - cq)^T), R = V diag(1, 1, det(V U^T)) U^T of H = U S V^T
+ *   (one-sided Jacobi; the identity for H = 0 or a non-finite H), t = cq - R cp.  The sums over the set run over lanes and a tree.
+ *   Score = the live rows with |R p + t - q| < inlier_thr, R p per row as ((R0 px + R1 py) + R2 pz) + t.  The winner has the largest
+ *   score, ties to the lowest rank.
+ *   Refinement, up to refine_iterations passes: the inliers of the current pose; stop if this is not the first pass and their number
+ *   did not grow, or if it is below 3; else the unweighted Kabsch pose over them (means, then H, in the fixed shape of 256 lanes and
+ *   a tree) is the next pose.  The final count and inliers_out are those of the pose returned.
+ * Outputs (device).  T_out f64[B,4,4] src -> tgt.  info_out int32[B,6] = status (BUF_SC2_*), live rows, seeds, the winner's row (-1
+ *   without a hypothesis), the winner's score before refinement, the final count.  NOTHING = fewer than 3 live rows, no hypothesis or
+ *   a winner with fewer than 3 inliers: the identity exactly, final count 0, no inliers.  Nullable: conf_out f64[sum n] (v after the
+ *   last normalisation, NaN on dead rows), seeds_out / hyp_counts_out int32[B,max_seeds] (rows and scores by rank, tail -1),
+ *   counts_out int32[max_seeds * sum n] (pair b's block starts at max_seeds * (its first correspondence row), rank r at + r n_b;
+ *   ranks without a seed -1), inliers_out uint8[sum n].  No atomics, every sum has a fixed order: a pair's outputs are the same bits
+ *   alone, in any batch, in any batch order and on reruns.
+ * BUF_EINVAL before any device work for npairs outside 0..65535, negative lengths, more than BUF_SC2_MAX_ROWS correspondences in a pair,
+ * a null required argument with npairs > 0 (src / tgt / corr only where their rows are not zero), d_thr / inlier_thr not finite and
+ * > 0, seed_ratio outside (0, 1], max_seeds outside 1..1024, k1 outside 3..128, nms_radius negative or not finite, power_iterations
+ * outside 0..1000, refine_iterations < 0, and a workspace that is null or smaller than buf_sc2_ws_bytes (sized from the actual
+ * lengths: 76 bytes per row, the bit matrices, 4 min(max_seeds, max(1, n)) n bytes of counts and 104 max_seeds + 48 bytes per pair,
+ * each array rounded up to 256 bytes; 0 for arguments out of range).  npairs == 0 succeeds and touches nothing. */
+#define BUF_SC2_NOTHING 0
+#define BUF_SC2_OK      1
+#define BUF_SC2_MAX_ROWS 16384
+size_t  buf_sc2_ws_bytes(const int* corr_lengths_host, int npairs, int max_seeds);
+int     buf_sc2_batched(const float* src, const int* src_lengths_host, const float* tgt, const int* tgt_lengths_host,
+                        const int* corr /* int32[sum corr_lengths,2]: (src row, tgt row), local to the pair's clouds */,
+                        const int* corr_lengths_host, int npairs,
+                        double d_thr, double inlier_thr, double seed_ratio, int max_seeds,     /* -, -, 0.2, 512 */
+                        int k1, double nms_radius, int power_iterations, int refine_iterations, /* 30, 0, 10, 20 */
+                        double* T_out /* f64[B,4,4] src -> tgt */, int* info_out /* int32[B,6] */,
+                        double* conf_out, int* seeds_out, int* hyp_counts_out, int* counts_out, unsigned char* inliers_out /* nullable */,
                         void* ws, size_t ws_bytes, void* stream);
 
 /* N4  Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
