@@ -29,6 +29,16 @@ class buf_grid_t(C.Structure):
     ]
 
 
+class buf_voxel_map_t(C.Structure):
+    _fields_ = [
+        ("buf", C.c_void_p), ("buf_bytes", C.c_size_t),
+        ("nclouds", C.c_int), ("nrows", C.c_int), ("n", C.c_int),
+        ("max_cells", C.c_int64),
+        ("voxel", C.c_double), ("epsilon", C.c_double),
+        ("clouds", C.c_void_p), ("table", C.c_void_p), ("rows", C.c_void_p), ("keys", C.c_void_p), ("row_off", C.c_void_p),
+    ]
+
+
 _lib = None
 
 _vp, _i, _f, _i64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
@@ -124,7 +134,14 @@ _SIGNATURES = {
     "buf_sc2_ws_bytes": (_sz, [_vp, _i, _i]),
     "buf_sc2_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "buf_match_metrics": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
+    "buf_voxel_map_bytes": (_sz, [_i, _i, _i64]),
+    "buf_voxel_map_ws_bytes": (_sz, [_i, _i, _i64]),
+    "buf_voxel_map_build": (_i, [C.POINTER(buf_voxel_map_t), _vp, _vp, _vp, _i, C.c_double, C.c_double, _i64, _vp, _sz, _vp, _sz, _vp]),
+    "buf_voxel_map_export": (_i, [C.POINTER(buf_voxel_map_t), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "buf_vgicp_ws_bytes": (_sz, [_i, _i]),
+    "buf_vgicp_batched": (_i, [C.POINTER(buf_voxel_map_t), _vp, _vp, _vp, _vp, _i, _i, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _sz, _vp]),
+    "buf_match_metrics":(_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "buf_row_linear": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "buf_segment_instance_norm_ws_bytes": (_sz, [_i, _i]),
     "buf_segment_instance_norm": (_i, [_vp, _i, _i, _vp, _i, _f, _vp, _vp, _sz, _vp]),

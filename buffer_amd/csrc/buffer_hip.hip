@@ -32,3 +32,4 @@
 #include "fpfh.hip"
 #include "fgr.hip"
 #include "sc2.hip"
+#include "vgicp.hip"

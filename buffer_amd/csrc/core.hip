@@ -13,7 +13,7 @@ void buf_set_error(const char* fmt, ...)
 }
 
 extern "C" const char* buf_last_error(void) { return g_err; }
-extern "C" int buf_version(void) { return 660; }   // 660: buf_sc2_batched (csrc/sc2.hip: SC2-PCR, eight kernels; no other kernel changed); 650: k_cyl_net_w24a (csrc/convnet_w24a.hip: F(2x4) tiles in layer 0 and the 32-output layers as well) carries the descriptor CNN; 640: k_cyl_net_w24p (csrc/convnet_w24p.hip: the flagged 64-output layers split by row component) carries the descriptor CNN; 630: buf_fgr_batched (csrc/fgr.hip: k_fgr_tuples, k_fgr_optimize; no other kernel changed); 620: buf_fpfh (csrc/fpfh.hip: k_spfh, k_fpfh; no other kernel changed); 610: k_cyl_net_w24k (F(2x4) tiles in the 64-output layers, K split) carries the descriptor CNN; 600: round 6 (split-f16 kernels safe by construction, cell records of the A2 self query, A1 with 13 launches); 500: round 5 (no packed-fp32 instructions, per-element scaled 1-NN planes); 200: round 2 (batched entry points, Winograd descriptor CNN); 300: round 3 (filter tilings: N-tile
+extern "C" int buf_version(void) { return 670; }   // 670: buf_voxel_map_build / buf_vgicp_batched (csrc/vgicp.hip: voxelized Generalized ICP on a reusable voxel map; no other kernel changed); 660: buf_sc2_batched (csrc/sc2.hip: SC2-PCR, eight kernels; no other kernel changed); 650: k_cyl_net_w24a (csrc/convnet_w24a.hip: F(2x4) tiles in layer 0 and the 32-output layers as well) carries the descriptor CNN; 640: k_cyl_net_w24p (csrc/convnet_w24p.hip: the flagged 64-output layers split by row component) carries the descriptor CNN; 630: buf_fgr_batched (csrc/fgr.hip: k_fgr_tuples, k_fgr_optimize; no other kernel changed); 620: buf_fpfh (csrc/fpfh.hip: k_spfh, k_fpfh; no other kernel changed); 610: k_cyl_net_w24k (F(2x4) tiles in the 64-output layers, K split) carries the descriptor CNN; 600: round 6 (split-f16 kernels safe by construction, cell records of the A2 self query, A1 with 13 launches); 500: round 5 (no packed-fp32 instructions, per-element scaled 1-NN planes); 200: round 2 (batched entry points, Winograd descriptor CNN); 300: round 3 (filter tilings: N-tile
                                                    // groups for 32 / 64 channels, Winograd layers 1-5 of the cost net, compact voxel lookup table)
 
 // ------------------------------------------------------------------------------------------

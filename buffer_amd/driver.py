@@ -154,12 +154,17 @@ def add_common_args(ap, driver_name, batch_default, log_root_default, preset_not
 def add_refine_args(ap):
     """--refine and its two settings: the dense refinement stage, the same on every driver (parse_with_preset adds them)"""
     from .ops import ICP_METHODS
-    ap.add_argument('--refine', default=None, choices=sorted(ICP_METHODS),
+    ap.add_argument('--refine', default=None, choices=sorted(ICP_METHODS) + ['voxelized'],
                     help='also refine every returned pose by dense ICP on the first-level clouds (BufferPipeline.refine_batch): summary '
                          'key "refined" = the figures of the refined poses + mean fitness / inlier_rmse / iterations; every other key '
-                         'stays that of the unrefined poses')
+                         'stays that of the unrefined poses.  voxelized: voxelized Generalized ICP on one voxel map of the targets '
+                         '(the learned path only; "refined" also carries voxel and neighbors, its inlier_rmse is the distance to voxel means)')
     ap.add_argument('--refine-dist', type=float, default=None, help='correspondence distance of --refine (default: the preset\'s dist_th)')
     ap.add_argument('--refine-iters', type=int, default=30, help='most ICP iterations of --refine')
+    ap.add_argument('--refine-voxel', type=float, default=None,
+                    help='--refine voxelized: the voxel edge (default: twice the correspondence distance)')
+    ap.add_argument('--refine-neighbors', type=int, default=7, choices=(1, 7, 27),
+                    help='--refine voxelized: voxels met by a source point (the voxel it falls into, + its 6 face neighbours, or all 27)')
 
 
 def add_descriptor_args(ap):
@@ -184,6 +189,10 @@ def parse_with_preset(ap, argv, driver_name):
         ap.error('--stage-metrics measures the stages of the learned path: not available with --descriptor fpfh')
     if a.estimator != 'ransac' and a.descriptor != 'fpfh':
         ap.error(f'--estimator {a.estimator} chooses the estimator of the classical baseline: it needs --descriptor fpfh')
+    if a.refine == 'voxelized' and a.descriptor == 'fpfh':
+        ap.error('--refine voxelized refines the learned path: not available with --descriptor fpfh')
+    if a.refine_voxel is not None and not (0.0 < a.refine_voxel < float('inf')):
+        ap.error(f'--refine-voxel {a.refine_voxel}: must be finite and > 0')
     try:
         return a, preset(a.preset, driver_name)
     except ValueError as e:
@@ -230,6 +239,9 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     refine = None
     if getattr(a, 'refine', None):
         refine = dict(method=a.refine, max_dist=cfg.dist_th if a.refine_dist is None else a.refine_dist, max_iteration=a.refine_iters)
+        if a.refine == 'voxelized':
+            rv = getattr(a, 'refine_voxel', None)
+            refine.update(voxel=2.0 * refine['max_dist'] if rv is None else rv, neighbors=getattr(a, 'refine_neighbors', 7))
     res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics, refine=refine)
     refined = None
     if refine is not None:
@@ -250,6 +262,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
                            max_iteration=a.refine_iters, fitness=float(stats[:, 0].mean()) if len(stats) else 0.0,
                            inlier_rmse=float(stats[:, 1].mean()) if len(stats) else 0.0,
                            iterations=float(stats[:, 2].mean()) if len(stats) else 0.0)
+            if a.refine == 'voxelized':
+                ref_out.update(voxel=refine['voxel'], neighbors=refine['neighbors'])
         out = summarize(poses)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
         if fpfh:

@@ -575,6 +575,92 @@ def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='po
     return T, fit, rmse, iters, (nn[:int(src.shape[0])] if nn is not None else None)
 
 
+VGICP_NEIGHBORS = (1, 7, 27)
+VOXEL_MAP_CELLS = (1 << 22, 1 << 25, 1 << 28)     # table sizes voxel_map_build tries in turn when max_cells is not given
+
+
+class VoxelMap:
+    """A built voxel map (include/buffer_hip.h, N9): the device buffer `buf` that holds it, the host handle `m` into it, nclouds, voxel,
+    epsilon, nrows (rows of all clouds).  It serves any number of vgicp_batched calls."""
+
+    def __init__(self, m, buf):
+        self.m, self.buf = m, buf
+        self.nclouds, self.nrows, self.voxel, self.epsilon = int(m.nclouds), int(m.nrows), float(m.voxel), float(m.epsilon)
+
+    def rows(self):
+        """buf_voxel_map_export -> dict of device tensors: keys int64[R], counts int32[R], means f64[R,3], covs f64[R,6] (00 01 02 11 12
+        22), row_off int32[nclouds + 1]; rows of a cloud in ascending key order, clouds one after the other."""
+        dev, R = self.buf.device, self.nrows
+        out = dict(keys=torch.empty((R,), dtype=torch.int64, device=dev), counts=torch.empty((R,), dtype=torch.int32, device=dev),
+                   means=torch.empty((R, 3), dtype=torch.float64, device=dev), covs=torch.empty((R, 6), dtype=torch.float64, device=dev),
+                   row_off=torch.empty((self.nclouds + 1,), dtype=torch.int32, device=dev))
+        check(_lib.lib().buf_voxel_map_export(C.byref(self.m), R, _ptr(out['keys']), _ptr(out['counts']), _ptr(out['means']),
+                                              _ptr(out['covs']), _ptr(out['row_off']), _stream()), "buf_voxel_map_export")
+        return out
+
+
+def voxel_map_build(points, lengths, voxel, normals=None, epsilon=1e-3, max_cells=0):
+    """buf_voxel_map_build: the voxel map of the clouds stacked in points f32[sum lengths,3] (normals f32 like points, or None: C = I)
+    -> VoxelMap.  max_cells bounds the dense lookup table over the clouds' voxel boxes (BufferHipError, BUF_ECAPACITY, when they need
+    more); 0: VOXEL_MAP_CELLS are tried in turn.  One small readback per attempt."""
+    L = _lib.lib()
+    points = _dev(points, torch.float32, "voxel_map_build.points").reshape(-1, 3)
+    lengths = _host_i32(lengths)
+    n, nb = int(points.shape[0]), int(lengths.shape[0])
+    if normals is not None:
+        normals = _dev(normals, torch.float32, "voxel_map_build.normals").reshape(-1, 3)
+        if tuple(normals.shape) != tuple(points.shape):
+            raise ValueError("voxel_map_build: normals must be shaped like points")
+    sizes = (int(max_cells),) if max_cells > 0 else VOXEL_MAP_CELLS
+    for k, cells in enumerate(sizes):
+        nbytes, wbytes = max(L.buf_voxel_map_bytes(n, nb, cells), 1), max(L.buf_voxel_map_ws_bytes(n, nb, cells), 1)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+        ws = torch.empty(wbytes, dtype=torch.uint8, device=points.device)
+        m = _lib.buf_voxel_map_t()
+        rc = L.buf_voxel_map_build(C.byref(m), _ptr(points), _ptr(normals), _hptr(lengths), nb, float(voxel), float(epsilon), cells,
+                                   _ptr(buf), nbytes, _ptr(ws), wbytes, _stream())
+        if rc == -4 and k + 1 < len(sizes):                 # BUF_ECAPACITY: the next table size
+            continue
+        check(rc, "buf_voxel_map_build")
+        return VoxelMap(m, buf)
+
+
+def vgicp_batched(src, src_lengths, vmap, T_init, neighbors=7, src_normals=None, pair_cloud=None, max_iteration=30, rel_fitness=1e-6,
+                  rel_rmse=1e-6, rows=False):
+    """buf_vgicp_batched: voxelized Generalized ICP of the sources stacked in src f32[sum src_lengths,3] against the clouds of vmap (a
+    VoxelMap; pair b uses cloud pair_cloud[b], or cloud b without pair_cloud), T_init f64[B,4,4] -> (T f64[B,4,4], fitness f64[B],
+    rmse f64[B], iterations int32[B], row int32[sum src_lengths] or None: the cloud-local map row of the voxel each source point fell
+    into in the last pass, -1 = none)."""
+    L = _lib.lib()
+    if neighbors not in VGICP_NEIGHBORS:
+        raise ValueError(f"vgicp_batched: neighbors={neighbors} (one of {VGICP_NEIGHBORS})")
+    src = _dev(src, torch.float32, "vgicp_batched.src").reshape(-1, 3)
+    sl = _host_i32(src_lengths)
+    B, dev, ns = int(sl.shape[0]), src.device, int(src.shape[0])
+    snrm = None
+    if src_normals is not None:
+        snrm = _dev(src_normals, torch.float32, "vgicp_batched.src_normals").reshape(-1, 3)
+        if tuple(snrm.shape) != tuple(src.shape):
+            raise ValueError("vgicp_batched: src_normals must be shaped like src")
+    pc = None
+    if pair_cloud is not None:
+        pc = _host_i32(pair_cloud)
+        if pc.shape[0] != B:
+            raise ValueError(f"vgicp_batched: {B} pairs but {pc.shape[0]} pair_cloud entries")
+    T_init = _dev(T_init, torch.float64, "vgicp_batched.T_init").reshape(B, 4, 4)
+    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
+    fit = torch.empty((B,), dtype=torch.float64, device=dev)
+    rmse = torch.empty((B,), dtype=torch.float64, device=dev)
+    iters = torch.empty((B,), dtype=torch.int32, device=dev)
+    row = torch.empty((max(ns, 1),), dtype=torch.int32, device=dev) if rows else None
+    nbytes = max(L.buf_vgicp_ws_bytes(ns, max(B, 1)), 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_vgicp_batched(C.byref(vmap.m), _ptr(src), _ptr(snrm), _hptr(sl), _hptr(pc) if pc is not None else C.c_void_p(0), B,
+                              int(neighbors), _ptr(T_init), int(max_iteration), float(rel_fitness), float(rel_rmse), _ptr(T), _ptr(fit),
+                              _ptr(rmse), _ptr(iters), _ptr(row), _ptr(ws), nbytes, _stream()), "buf_vgicp_batched")
+    return T, fit, rmse, iters, (row[:ns] if row is not None else None)
+
+
 def fpfh(points, normals, nbr, max_nn=100, return_spfh=False):
     """buf_fpfh: FPFH descriptors of the points f32[n,3] with normals f32[n,3] from their sorted radius rows nbr int32[n,k]
     (CellGrid.query: padded with values >= n; column 0 is the point itself) -> f64[n,33] (, the SPFH table f64[n,33]).  The rows may

@@ -90,7 +90,7 @@ class BufferPipeline:
         return res
 
     @torch.no_grad()
-    def refine_batch(self, inps, poses, method='generalized', max_dist=None, max_iteration=30, epsilon=1e-3):
+    def refine_batch(self, inps, poses, method='generalized', max_dist=None, max_iteration=30, epsilon=1e-3, voxel=None, neighbors=7):
         """Dense refinement of a batch's poses: ONE batched ICP call (icp.py / csrc/icp.hip, all pairs in one set of launches) on the
         dense first-level clouds of inps (src_raw / tgt_raw), started from `poses` (B src -> tgt 4x4: what register_batch returned, a
         list or a [B,4,4] tensor), which are converted to f64 on the device -- no pose passes through the host.
@@ -98,11 +98,17 @@ class BufferPipeline:
         max_dist: the correspondence distance, cfg.dist_th unless given.  Normals come from ONE stacked
         preprocess.estimate_normals(knn=30, orient=False, lengths=) call: of all 2B clouds (sources, then targets) for 'generalized', of
         the B targets for 'point_to_plane', none for 'point_to_point'.
+        method 'voxelized' (icp.vgicp_batched, csrc/vgicp.hip): the normals of 'generalized', ONE voxel map of the B targets (voxel:
+        its edge, twice the correspondence distance unless given; epsilon) and one batched call on it with `neighbors` (1, 7 or 27)
+        voxels per source point; no nearest-neighbour search.  Its inlier_rmse is the distance to voxel means: of the order of the
+        voxel size, not comparable with the other methods'.
         -> dict of device tensors: poses f32[B,4,4], fitness f64[B], inlier_rmse f64[B], iterations int32[B].
-        Host waits: the normal estimation's own round trips and ICP's one int per 8 rounds."""
+        Host waits: the normal estimation's own round trips and ICP's one int per 8 rounds ('voxelized': and the map's one record)."""
         from . import preprocess
-        if method not in ops.ICP_METHODS:
-            raise ValueError(f'refine_batch: unknown method {method!r} (one of {sorted(ops.ICP_METHODS)})')
+        if method != 'voxelized' and method not in ops.ICP_METHODS:
+            raise ValueError(f"refine_batch: unknown method {method!r} (one of {sorted(list(ops.ICP_METHODS) + ['voxelized'])})")
+        if method == 'voxelized' and neighbors not in ops.VGICP_NEIGHBORS:
+            raise ValueError(f'refine_batch: neighbors={neighbors} (one of {ops.VGICP_NEIGHBORS})')
         dev, B = self.device, len(inps)
         if isinstance(poses, (list, tuple)):
             poses = torch.stack(list(poses)) if B else torch.zeros((0, 4, 4), device=dev)
@@ -114,11 +120,16 @@ class BufferPipeline:
         sl, tl = np.array([s.shape[0] for s in srcs], np.int32), np.array([t.shape[0] for t in tgts], np.int32)
         src, tgt = torch.cat(srcs).float().contiguous(), torch.cat(tgts).float().contiguous()
         snrm = tnrm = None
-        if method == 'generalized':
+        if method in ('generalized', 'voxelized'):
             nrm = preprocess.estimate_normals(torch.cat([src, tgt]), knn=30, orient=False, lengths=np.concatenate([sl, tl]))
             snrm, tnrm = nrm[:src.shape[0]].contiguous(), nrm[src.shape[0]:].contiguous()
         elif method == 'point_to_plane':
             tnrm = preprocess.estimate_normals(tgt, knn=30, orient=False, lengths=tl)
+        if method == 'voxelized':
+            edge = float(voxel) if voxel is not None else 2.0 * float(self.cfg.dist_th if max_dist is None else max_dist)
+            vmap = ops.voxel_map_build(tgt, tl, edge, tnrm, epsilon)
+            T, fit, rmse, iters, _ = ops.vgicp_batched(src, sl, vmap, T0, int(neighbors), snrm, None, int(max_iteration))
+            return dict(poses=T.float(), fitness=fit, inlier_rmse=rmse, iterations=iters)
         T, fit, rmse, iters, _ = ops.icp_batched(src, sl, tgt, tl, float(self.cfg.dist_th if max_dist is None else max_dist), T0, method,
                                                  tnrm, int(max_iteration), src_normals=snrm, epsilon=epsilon)
         return dict(poses=T.float(), fitness=fit, inlier_rmse=rmse, iterations=iters)

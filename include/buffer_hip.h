@@ -686,6 +686,84 @@ int     buf_sc2_batched(const float* src, const int* src_lengths_host, const flo
                         double* conf_out, int* seeds_out, int* hyp_counts_out, int* counts_out, unsigned char* inliers_out /* nullable */,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* N9  Voxelized Generalized ICP (Koide, Yokozuka, Oishi, Banno, "Voxelized GICP for fast and accurate 3D point cloud
+ * registration", ICRA 2021) against a reusable map of target voxels.  No VGICP source was at hand: the method is restated from the
+ * paper, parity with any other implementation is unpinned and this text is the specification.  Unless stated otherwise all
+ * arithmetic is IEEE fp64, every operation rounded once in the written order, without FMA, and every sum runs in a fixed order: a
+ * pair's outputs are the same bits alone, in any batch, in reversed order and on reruns.  No float atomics.
+ *
+ * THE MAP covers nclouds target clouds stacked in pts (f32[sum lengths_host,3], device); normals f32[.,3] is nullable.
+ *   Voxel of a point: k_c = floor((double)p_c / voxel) per axis (a division; the origin is absolute, no bounding box enters it).  A
+ *   point with a non-finite coordinate or any |k_c| >= 2^20 is left out of the map.
+ *   key = ((kz + 2^20) << 42) | ((ky + 2^20) << 21) | (kx + 2^20).
+ *   Every occupied voxel of a cloud gives one row: count N; mean = (sum of its points, in input order, each promoted to fp64) / N;
+ *   cov = (sum over its points, in input order, of C(n_i)) / N, stored as six values 00 01 02 11 12 22.
+ *   C(n)_rc = delta_rc - ((1 - epsilon) n_r) n_c, with (1 - epsilon) formed once; n is the point's normal row promoted to fp64
+ *   under N2's rule: it counts if | ((nx nx + ny ny) + nz nz) - 1 | < 1e-3 (which a non-finite component fails), any other row and
+ *   every row of a null array is taken as zero, C = I.
+ *   Rows of a cloud are in ascending key order, clouds follow one another; row_off int32[nclouds + 1] (device) is each cloud's row
+ *   range.  The map remembers voxel and epsilon.
+ *   Lookup: a dense table of row indices over each cloud's box of occupied voxel coordinates, the clouds' tables one after the
+ *   other, at most max_cells slots in all (BUF_ECAPACITY if the boxes need more: a far outlier inflates its cloud's box).  The same
+ *   table is the counting sort's, so where a row lands and what a lookup returns never depend on the run.
+ *   The map lives in ONE caller-allocated device buffer of buf_voxel_map_bytes(sum lengths, nclouds, max_cells) bytes (88 bytes per
+ *   point and 4 per slot, rounded up); the build also takes a workspace of buf_voxel_map_ws_bytes (12 bytes per point and 4 per
+ *   slot) that is free again when it returns.  buf_voxel_map_t is a host handle into that buffer: it stays valid as long as the
+ *   buffer does and may serve any number of buf_vgicp_batched calls.  Building synchronises once, to read back one record of two ints
+ *   (capacity status, rows).  buf_voxel_map_export writes keys int64[n], counts int32[n], means f64[n,3], covs f64[n,6] (the first
+ *   map->nrows rows of each; n = their capacity) and row_off int32[nclouds + 1], all device arrays.
+ *   BUF_EINVAL before any device work for voxel <= 0 or not finite, epsilon outside (0, 1] or not finite, nclouds outside 1..65535,
+ *   negative lengths, max_cells outside 1..2^31-2; in export for n < map->nrows.  The two size functions answer 0 out of range.
+ *
+ * REGISTRATION: B pairs per call.  Sources are stacked as in N2 (src f32[sum src_lengths_host,3]); src_normals f32[.,3] is nullable
+ *   (C = I).  pair_cloud_host int[B] (nullable: pair b uses cloud b) names the map cloud of each pair; several pairs may name one.
+ *   neighbors is 1 (the voxel a point falls into), 7 (that voxel, then +x, -x, +y, -y, +z, -z) or 27 (all offsets, dz outermost and
+ *   dx innermost, each running -1, 0, +1).
+ *   Per round and source point: p = T s with N2's expression ((T0 x + T1 y) + T2 z) + T3 per row; k = floor(p / voxel); a
+ *   non-finite p or a |k_c| >= 2^20 gives no term.  Every OCCUPIED voxel v among the offsets, in offset order, gives one term (there
+ *   is no distance test): d = p - mean_v; S_rc = (cov_v,rc + (R R^T)_rc) - ((1 - epsilon) m_r) m_c with R the rotation block of T,
+ *   (R R^T)_rc = (R_r0 R_c0 + R_r1 R_c1) + R_r2 R_c2 and m = R n_s (rows as (R_r0 n0 + R_r1 n1) + R_r2 n2), i.e. cov_v + R C(n_s) R^T;
+ *   M = S^-1 by cofactors as in N2; J = [-[p]x | I]; H += N_v J^T M J, g += N_v J^T M d (each entry formed as in N2, times N_v, and
+ *   added to the point's running sum; the points of a tile of 256 are summed by an xor butterfly inside each wavefront, the four
+ *   wavefronts in ascending order, the tiles of a pair by lane and butterfly).
+ *   Per pair and round: fitness = source points with at least one term / source points; inlier_rmse = sqrt(sum over all terms of
+ *   ((dx dx + dy dy) + dz dz) / terms), 0 without terms: the Euclidean distance to VOXEL MEANS, of the order of the voxel size, not a
+ *   surface residual, and comparable only at equal voxel and neighbors.
+ *   Update: H x = -g by N2's Cholesky (LDL^T) solve, N2's dT, T <- dT T.  Stopping is N2's with terms in the place of matches:
+ *   before an update with fewer than 6 terms or a system that is not positive definite (T unchanged); after an update when
+ *   |d fitness| < rel_fitness and |d rmse| < rel_rmse; after max_iteration updates.
+ *   Outputs as in buf_gicp_batched (T_out f64[B,4,4], fitness_out / rmse_out f64[B], iters_out int32[B], of the last pass); row_out
+ *   (nullable) int32[sum src_lengths]: the cloud-local map row of the voxel the point fell into in the pair's last pass, or -1.  A
+ *   pair with an empty source or an empty map cloud returns T_init, fitness 0 and 0 iterations.
+ *   Synchronises as N2: one int read back after every 8th round.
+ *   BUF_EINVAL before any device work for a null or unbuilt map, neighbors outside {1, 7, 27}, a pair_cloud entry outside the map
+ *   (or, with a null pair_cloud, more pairs than map clouds), npairs outside 0..65535, negative lengths, max_iteration < 0, a null
+ *   required argument; BUF_EWORKSPACE for a workspace below buf_vgicp_ws_bytes(sum src_lengths, B). */
+typedef struct buf_voxel_map {
+    void*   buf;                 /* the caller's device buffer */
+    size_t  buf_bytes;
+    int     nclouds, nrows, n;   /* clouds, rows of all clouds, points given */
+    int64_t max_cells;
+    double  voxel, epsilon;
+    void*   clouds;              /* views into buf: per-cloud box and table offset */
+    int*    table;               /* [max_cells + 1] slot -> row of all clouds, -1 = empty voxel */
+    double* rows;                /* [nrows,10] mean (3), cov (6), count */
+    long long* keys;             /* [nrows] */
+    int*    row_off;             /* [nclouds + 1] */
+} buf_voxel_map_t;
+size_t  buf_voxel_map_bytes(int n_total, int nclouds, int64_t max_cells);
+size_t  buf_voxel_map_ws_bytes(int n_total, int nclouds, int64_t max_cells);
+int     buf_voxel_map_build(buf_voxel_map_t* map, const float* pts, const float* normals, const int* lengths_host, int nclouds,
+                            double voxel, double epsilon, int64_t max_cells, void* buf, size_t buf_bytes, void* ws, size_t ws_bytes,
+                            void* stream);
+int     buf_voxel_map_export(const buf_voxel_map_t* map, int n, long long* keys, int* counts, double* means, double* covs,
+                             int* row_off, void* stream);
+size_t  buf_vgicp_ws_bytes(int n_src_total, int npairs);
+int     buf_vgicp_batched(const buf_voxel_map_t* map, const float* src, const float* src_normals, const int* src_lengths_host,
+                          const int* pair_cloud_host, int npairs, int neighbors, const double* T_init_f64, int max_iteration,
+                          double rel_fitness, double rel_rmse, double* T_out_f64, double* fitness_out, double* rmse_out,
+                          int* iters_out, int* row_out, void* ws, size_t ws_bytes, void* stream);
+
 /* N4  Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
  * information matrix of a pair are made of; the evaluation half of an ICP round without the loop).
  * pts f32[sum lengths_host,3] stacks the C clouds; pair k = (pair_src_host[k], pair_tgt_host[k], T_f64[k]) with T_f64 f64[P,4,4]

@@ -4,6 +4,8 @@ kitti.KittiTestSet refines its ground truth (0.20 m, <= 200 iterations, relative
 perturbed by a small error (odometry is close, not exact).  Times are HIP-event spans after a warm-up of every path.
 --method point_to_plane / generalized: the same runs with that step; the 30-NN normals they need (targets / all scans, ONE stacked
 preprocess.estimate_normals call) are timed as a span of their own, normals_ms, outside the ICP spans.
+--method voxelized [--voxel V] [--neighbors K]: voxelized Generalized ICP (icp.vgicp_batched); the map build and the loop on a
+prebuilt map are spans of their own.  --repeats R: every span (the normals excepted) is the median of R runs.
 Prints one JSON line:  python tools/icp_time.py [--pairs 16] [--method point_to_point]"""
 import argparse
 import json
@@ -17,14 +19,21 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from buffer_amd import icp, ops, preprocess, synth  # noqa: E402
 
 
+REPEATS = [1]
+
+
 def _span(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return out, a.elapsed_time(b)
+    """-> (fn's result, the median HIP-event span in ms of --repeats runs)"""
+    ms = []
+    for _ in range(REPEATS[0]):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return out, float(np.median(ms))
 
 
 def main():
@@ -32,8 +41,11 @@ def main():
     ap.add_argument('--pairs', type=int, default=16)
     ap.add_argument('--max-iteration', type=int, default=200)
     ap.add_argument('--dist', type=float, default=0.20)
-    ap.add_argument('--method', default='point_to_point', choices=sorted(ops.ICP_METHODS))
-    ap.add_argument('--epsilon', type=float, default=1e-3, help='generalized: the covariance along a normal')
+    ap.add_argument('--method', default='point_to_point', choices=sorted(ops.ICP_METHODS) + ['voxelized'])
+    ap.add_argument('--epsilon', type=float, default=1e-3, help='generalized / voxelized: the covariance along a normal')
+    ap.add_argument('--voxel', type=float, default=None, help='voxelized: the voxel edge (default: twice --dist)')
+    ap.add_argument('--neighbors', type=int, default=7, choices=ops.VGICP_NEIGHBORS, help='voxelized: voxels met by a source point')
+    ap.add_argument('--repeats', type=int, default=1, help='timed runs per span after the warm-up; the median is reported')
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     rng = np.random.default_rng(0)
@@ -54,11 +66,14 @@ def main():
         n = [c.shape[0] for c in clouds]
         return list(torch.split(preprocess.estimate_normals(torch.cat(clouds), knn=30, orient=False, lengths=n), n))
 
-    need = dict(point_to_point=[], point_to_plane=tgts, generalized=srcs + tgts)[a.method]
+    need = dict(point_to_point=[], point_to_plane=tgts, generalized=srcs + tgts, voxelized=srcs + tgts)[a.method]
     nrm, t_normals = [], 0.0
     if need:
         normals(need)                                                        # warm-up
         nrm, t_normals = _span(lambda: normals(need))
+    REPEATS[0] = max(a.repeats, 1)
+    if a.method == 'voxelized':
+        return voxelized(a, srcs, tgts, nrm, t_normals)
 
     def extra(lo, hi):
         """the method's arguments for pairs lo..hi-1"""
@@ -86,6 +101,36 @@ def main():
         batched_ms_per_pair=t_batch / B, batched_ms_per_pair_iteration=t_batch / max(sum(itb), 1),
         batched_rounds=max(itb) + 1, iterations_batched=itb,
         iterations_batch1_equal_batched=it1 == itb,
+        max_abs_T_diff_batch1_vs_batched=float(max(np.abs(x['T'] - y['T']).max() for x, y in zip(one, batch))))))
+
+
+def voxelized(a, srcs, tgts, nrm, t_normals):
+    """--method voxelized: the map build (one map of all targets; one map per target for the batch-1 runs) and the loop on a PREBUILT
+    map are spans of their own: the loop span is what a second call on the same targets costs, the map span what reuse saves."""
+    B = len(srcs)
+    voxel = 2.0 * a.dist if a.voxel is None else a.voxel
+    sn, tn = nrm[:B], nrm[B:]
+    kw = dict(neighbors=a.neighbors, max_iteration=a.max_iteration)
+    icp.vgicp_batched(srcs[:1], icp.voxel_map(tgts[:1], voxel, tn[:1], a.epsilon), src_normals=sn[:1], **dict(kw, max_iteration=3))   # warm-up
+    icp.vgicp_batched(srcs, icp.voxel_map(tgts, voxel, tn, a.epsilon), src_normals=sn, **dict(kw, max_iteration=3))
+    maps, t_map1 = [], 0.0
+    for b in range(B):
+        m, ms = _span(lambda: icp.voxel_map(tgts[b:b + 1], voxel, tn[b:b + 1], a.epsilon))
+        maps.append(m); t_map1 += ms
+    vmap, t_map = _span(lambda: icp.voxel_map(tgts, voxel, tn, a.epsilon))
+    one, t_one = [], 0.0
+    for b in range(B):
+        r, ms = _span(lambda: icp.vgicp_batched(srcs[b:b + 1], maps[b], src_normals=sn[b:b + 1], **kw)[0])
+        one.append(r); t_one += ms
+    batch, t_batch = _span(lambda: icp.vgicp_batched(srcs, vmap, src_normals=sn, **kw))
+    it1, itb = [r['iterations'] for r in one], [r['iterations'] for r in batch]
+    print(json.dumps(dict(
+        method=a.method, voxel=voxel, neighbors=a.neighbors, normals_ms=t_normals, pairs=B, points_per_scan=int(np.mean([s.shape[0] for s in srcs])),
+        max_iteration=a.max_iteration, map_rows=vmap.nrows, batch1_map_ms_per_pair=t_map1 / B, batched_map_ms_per_pair=t_map / B,
+        batch1_ms_per_pair=t_one / B, batch1_ms_per_iteration=t_one / max(sum(it1), 1),
+        batched_ms_per_pair=t_batch / B, batched_ms_per_pair_iteration=t_batch / max(sum(itb), 1),
+        batched_rounds=max(itb) + 1, iterations_batched=itb, iterations_batch1_equal_batched=it1 == itb,
+        mean_fitness=float(np.mean([r['fitness'] for r in batch])),
         max_abs_T_diff_batch1_vs_batched=float(max(np.abs(x['T'] - y['T']).max() for x, y in zip(one, batch))))))
 
 
