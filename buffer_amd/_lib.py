@@ -134,6 +134,9 @@ _SIGNATURES = {
     "buf_sc2_ws_bytes": (_sz, [_vp, _i, _i]),
     "buf_sc2_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "buf_clique_ws_bytes": (_sz, [_vp, _i, _i, _i]),
+    "buf_clique_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double, _i,
+                                _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "buf_voxel_map_bytes": (_sz, [_i, _i, _i64]),
     "buf_voxel_map_ws_bytes": (_sz, [_i, _i, _i64]),
     "buf_voxel_map_build": (_i, [C.POINTER(buf_voxel_map_t), _vp, _vp, _vp, _i, C.c_double, C.c_double, _i64, _vp, _sz, _vp, _sz, _vp]),

@@ -32,4 +32,5 @@
 #include "fpfh.hip"
 #include "fgr.hip"
 #include "sc2.hip"
+#include "clique.hip"
 #include "vgicp.hip"

@@ -173,10 +173,12 @@ def add_descriptor_args(ap):
                     help='buffer: the learned path (default).  fpfh: the classical baseline on the same pairs, thresholds and logs -- FPFH on '
                          'the second-level clouds, mutual matches, RANSAC (buffer_amd/fpfh.py); no calibration, no --stage-metrics; the '
                          'summary carries "descriptor"')
-    ap.add_argument('--estimator', default='ransac', choices=('ransac', 'fgr', 'sc2'),
+    ap.add_argument('--estimator', default='ransac', choices=('ransac', 'fgr', 'sc2', 'clique'),
                     help='the pose estimator of --descriptor fpfh.  ransac: seeded 3-point hypotheses (default).  fgr: Fast Global Registration '
                          'on the same matches, one batched call per chunk (buffer_amd/fgr.py).  sc2: SC2-PCR, the deterministic second-order '
-                         'spatial-compatibility consensus, one batched call per chunk (buffer_amd/sc2.py); the summary carries "estimator"')
+                         'spatial-compatibility consensus, one batched call per chunk (buffer_amd/sc2.py).  clique: greedy maximum clique of the '
+                         'compatibility graph + truncated least squares, one batched call per chunk (buffer_amd/clique.py), also reporting '
+                         '"certified_pairs" = the pairs whose clique reaches the k-core bound; the summary carries "estimator"')
 
 
 def parse_with_preset(ap, argv, driver_name):
@@ -211,7 +213,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     summarize(poses) -> the driver's own figures, the common ones, --by-overlap under the driver's (rte, rre) thresholds and
     --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
     --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor" and
-    "estimator", --estimator choosing its RANSAC, its Fast Global Registration or its SC2-PCR).
+    "estimator", --estimator choosing its RANSAC, its Fast Global Registration, its SC2-PCR or its max-clique + TLS estimator, which adds
+    "certified_pairs").
     --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
     unrefined poses.
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
@@ -251,6 +254,10 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
         refined = bdist.gather_poses(ids, refined['poses'], len(ds), device=cdev, extra=torch.stack(
             [refined['fitness'].float(), refined['inlier_rmse'].float(), refined['iterations'].float()], 1))
     counts = bdist.gather_counts(ids, res[1].to(cdev), len(ds), device=cdev).cpu().numpy() if a.stage_metrics else None
+    certified = None
+    if fpfh and pipe.estimator == 'clique':                  # one flag per pair, in the order of ids (the chunks' order)
+        flags = torch.cat(pipe.certified_log or [torch.zeros(0, dtype=torch.bool, device=dev)]).to(torch.int32).reshape(-1, 1)
+        certified = bdist.gather_counts(ids, flags.to(cdev), len(ds), device=cdev)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     poses = poses.cpu().numpy()
@@ -269,6 +276,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
         if fpfh:
             out['descriptor'] = 'fpfh'
             out['estimator'] = getattr(a, 'estimator', 'ransac')
+            if certified is not None:
+                out['certified_pairs'] = int((certified == 1).sum())
         if ref_out is not None:
             out['refined'] = ref_out
         overlaps = None

@@ -6,8 +6,9 @@ from its published form (include/buffer_hip.h, N6; parity unpinned).
     compute_fpfh        descriptors of one or several stacked clouds: one cell grid, one radius query, one launch pair
     match               (mutual) 1-NN matches of two descriptor sets through ops.knn (d = 33: the exact fp32 scan)
     FpfhRegistration    estimator='ransac' (default), 'fgr' (buffer_amd/fgr.py: one batched Fast Global Registration call per
-                        batch on the concatenated match lists) or 'sc2' (buffer_amd/sc2.py: one batched SC2-PCR call per batch on the
-                        same lists); register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
+                        batch on the concatenated match lists), 'sc2' (buffer_amd/sc2.py: one batched SC2-PCR call per batch on the
+                        same lists) or 'clique' (buffer_amd/clique.py: one batched max-clique + TLS call per batch on the same
+                        lists); register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
                         clouds and normals of driver.upload's dicts
 """
 import numpy as np
@@ -17,6 +18,7 @@ from . import ops
 
 ESTIMATORS = ('ransac', 'fgr')
 ALL_ESTIMATORS = ESTIMATORS + ('sc2',)
+KNOWN_ESTIMATORS = ALL_ESTIMATORS + ('clique',)
 
 
 def compute_fpfh(points, normals, radius, max_nn=100, lengths=None):
@@ -69,15 +71,20 @@ class FpfhRegistration:
     dist_factor * cfg.voxel_size_0 in the clouds' units and open3d's defaults otherwise.
     estimator='sc2': SC2-PCR on the same matches (no seeds: it is deterministic), with d_thr = inlier_thr = the same
     dist_factor * cfg.voxel_size_0, no non-maximum suppression and Sc2Options' defaults otherwise; a pair with more than
-    ops.SC2_MAX_ROWS (16 384) matches is an error, not a truncation."""
+    ops.SC2_MAX_ROWS (16 384) matches is an error, not a truncation.
+    estimator='clique': the max-clique + TLS estimator on the same matches (deterministic as well), with d_thr = tim_thr = inlier_thr =
+    the same dist_factor * cfg.voxel_size_0, t_thr = half of it and CliqueOptions' defaults otherwise, under the same row limit; the
+    last call's `certified` (bool[B]: the clique reaches the k-core bound) and `bound` (int32[B]) stay on the object, on the device."""
 
     def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac'):
         self.cfg, self.device = cfg, torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('FpfhRegistration runs on a HIP device only (no CPU path)')
-        if estimator not in ALL_ESTIMATORS:
-            raise ValueError(f'FpfhRegistration: unknown estimator {estimator!r} (one of {ALL_ESTIMATORS})')
+        if estimator not in KNOWN_ESTIMATORS:
+            raise ValueError(f'FpfhRegistration: unknown estimator {estimator!r} (one of {KNOWN_ESTIMATORS})')
         self.estimator = estimator
+        self.certified = self.bound = None   # estimator='clique': of the last register_batch call
+        self.certified_log = []              # and `certified` of every call so far, in call order (the drivers count it)
         self.radius = float(radius_factor) * cfg.voxel_size_0
         self.max_nn, self.max_dist, self.edge_similarity = int(max_nn), float(dist_factor) * cfg.voxel_size_0, float(edge_similarity)
         self.limits = None                   # the neighbourhood limits of the learned path: nothing to calibrate here
@@ -108,6 +115,8 @@ class FpfhRegistration:
             return self._fgr_batch(pts, lens, off, F, seeds)
         if self.estimator == 'sc2':
             return self._sc2_batch(pts, lens, off, F)
+        if self.estimator == 'clique':
+            return self._clique_batch(pts, lens, off, F)
         out = []
         for b in range(B):
             s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
@@ -135,6 +144,16 @@ class FpfhRegistration:
         src, tgt, corrs = self._batch_matches(pts, lens, off, F)
         res = sc2.sc2_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
                                    d_thr=self.max_dist, inlier_thr=self.max_dist, nms_radius=0.0)
+        return list(res['poses'].float().unbind(0))
+
+    def _clique_batch(self, pts, lens, off, F):
+        """the matches of every pair, then ONE clique_batched call for the batch; keeps its `certified` and `bound`"""
+        from . import clique
+        src, tgt, corrs = self._batch_matches(pts, lens, off, F)
+        res = clique.clique_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
+                                         d_thr=self.max_dist, tim_thr=self.max_dist, t_thr=self.max_dist / 2, inlier_thr=self.max_dist)
+        self.certified, self.bound = res['certified'], res['bound']
+        self.certified_log.append(self.certified)
         return list(res['poses'].float().unbind(0))
 
     def _fgr_batch(self, pts, lens, off, F, seeds):

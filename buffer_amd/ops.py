@@ -770,6 +770,61 @@ def sc2_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, d_thr, i
     return T, info, detail
 
 
+CLIQUE_STATUS = ('NOTHING', 'OK')                                                               # BUF_CLIQUE_* of buffer_hip.h
+CLIQUE_MAX_SEEDS, CLIQUE_MAX_MEMBERS = 1024, 512
+
+
+def clique_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, d_thr, tim_thr=None, t_thr=None, inlier_thr=None,
+                   max_seeds=64, max_members=256, gnc_factor=1.4, gnc_iterations=100, refine_iterations=20, return_detail=False):
+    """buf_clique_batched: greedy maximum clique of the compatibility graph with its k-core bound, GNC-TLS rotation, voted translation
+    and SC2's refit (the TEASER-style estimator, N10 of buffer_hip.h) of the pairs stacked in src f32[sum src_lengths,3] / tgt
+    f32[sum tgt_lengths,3] on the correspondences corr int32[sum corr_lengths,2] ((src row, tgt row) inside the pair's own clouds);
+    deterministic, no seeds; tim_thr and inlier_thr default to d_thr, t_thr to d_thr / 2 -> (T f64[B,4,4] src -> tgt, info int32[B,8] =
+    (index into CLIQUE_STATUS, live rows, bound, the winner's size, its rank, members used, GNC steps, the final inlier count),
+    detail), all on the device, nothing read back.  detail is None or, with return_detail=True, dict(deg / core / rank int32[sum n]
+    (-1 on dead rows), sizes int32[B,max_seeds] (by rank, tail -1), members int32[B,max_members] (rows, tail -1), weights
+    f64[B, max_members (max_members - 1) / 2] (NaN tail), pose0 f64[B,12] (R and t before the refit), inlier_mask uint8[sum n])."""
+    L = _lib.lib()
+    src, tgt = _dev(src, torch.float32, "clique_batched.src"), _dev(tgt, torch.float32, "clique_batched.tgt")
+    corr = _dev(corr, torch.int32, "clique_batched.corr")
+    sl, tl, cl = _host_i32(src_lengths), _host_i32(tgt_lengths), _host_i32(corr_lengths)
+    B, dev = int(sl.shape[0]), src.device
+    if tl.shape[0] != B or cl.shape[0] != B:
+        raise ValueError(f"clique_batched: {B} source lengths but {tl.shape[0]} target and {cl.shape[0]} correspondence lengths")
+    for name, t, ln, w in (("src", src, sl, 3), ("tgt", tgt, tl, 3), ("corr", corr, cl, 2)):
+        if t.dim() != 2 or t.shape[1] != w:
+            raise ValueError(f"clique_batched: {name} {tuple(t.shape)} is not [N,{w}]")
+        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
+            raise ValueError(f"clique_batched: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    if B and int(cl.max()) > SC2_MAX_ROWS:
+        raise ValueError(f"clique_batched: {int(cl.max())} correspondences in one pair (at most {SC2_MAX_ROWS})")
+    if not (1 <= int(max_seeds) <= CLIQUE_MAX_SEEDS) or not (3 <= int(max_members) <= CLIQUE_MAX_MEMBERS):
+        raise ValueError(f"clique_batched: max_seeds={max_seeds} (1..{CLIQUE_MAX_SEEDS}), max_members={max_members} "
+                         f"(3..{CLIQUE_MAX_MEMBERS})")
+    d_thr = float(d_thr)
+    tim_thr = d_thr if tim_thr is None else float(tim_thr)
+    t_thr = d_thr / 2 if t_thr is None else float(t_thr)
+    inlier_thr = d_thr if inlier_thr is None else float(inlier_thr)
+    ms, mm, n = int(max_seeds), int(max_members), int(corr.shape[0])
+    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
+    info = torch.zeros((B, 8), dtype=torch.int32, device=dev)
+    detail = None
+    if return_detail:
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        detail = dict(deg=i32(n), core=i32(n), rank=i32(n), sizes=i32(B, ms), members=i32(B, mm),
+                      weights=torch.empty((B, mm * (mm - 1) // 2), dtype=torch.float64, device=dev),
+                      pose0=torch.empty((B, 12), dtype=torch.float64, device=dev), inlier_mask=torch.empty(n, dtype=torch.uint8, device=dev))
+    d = detail or {}
+    nbytes = max(L.buf_clique_ws_bytes(_hptr(cl), B, ms, mm), 1) if B else 1
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_clique_batched(_ptr(src), _hptr(sl), _ptr(tgt), _hptr(tl), _ptr(corr), _hptr(cl), B, d_thr, tim_thr, t_thr, inlier_thr, ms,
+                               mm, float(gnc_factor), int(gnc_iterations), int(refine_iterations), _ptr(T), _ptr(info), _ptr(d.get('deg')),
+                               _ptr(d.get('core')), _ptr(d.get('rank')), _ptr(d.get('sizes')), _ptr(d.get('members')),
+                               _ptr(d.get('weights')), _ptr(d.get('pose0')), _ptr(d.get('inlier_mask')), _ptr(ws), nbytes, _stream()),
+          "buf_clique_batched")
+    return T, info, detail
+
+
 def pair_stats(points, lengths, pair_src, pair_tgt, T, radius, correspondences=False, cells_per_elem=0):
     """buf_pair_stats: statistics of P pairs over the C clouds stacked in points f32[sum lengths,3] under given transforms, one cell
     grid per call, nothing read back.  pair_src / pair_tgt host int[P] (cloud indices), T f64[P,4,4] (device) mapping the source

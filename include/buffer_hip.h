@@ -67,7 +67,13 @@ int         buf_device_count(void);
 #define BUF_TIMED_SC2_COUNTS     16  /* N8 k_sc2_counts: work = 8 * sum (seed groups * n * words) bytes of bit rows streamed */
 #define BUF_TIMED_SC2_HYP        17  /* N8 k_sc2_hyp: work = seed ranks launched */
 #define BUF_TIMED_SC2_REFINE     18  /* N8 k_sc2_refine: work = pairs */
-#define BUF_TIMED_NKERNELS       19
+#define BUF_TIMED_CLIQUE_GRAPH   19  /* N10 k_sc2_gather + k_sc2_compat + k_clique_deg: work = sum n^2 pairs of rows */
+#define BUF_TIMED_CLIQUE_PEEL    20  /* N10 k_clique_peel: work = pairs */
+#define BUF_TIMED_CLIQUE_ORDER   21  /* N10 k_clique_order + the second k_sc2_compat: work = 2 sum n^2 */
+#define BUF_TIMED_CLIQUE_WALK    22  /* N10 k_clique_walk: work = seed ranks launched */
+#define BUF_TIMED_CLIQUE_POSE    23  /* N10 k_clique_pose (GNC-TLS + voting): work = pairs */
+#define BUF_TIMED_CLIQUE_POLISH  24  /* N10 k_clique_polish: work = pairs */
+#define BUF_TIMED_NKERNELS       25
 void        buf_timing_enable(int on);
 long long   buf_timing_collect(double* total_ms, double* total_bytes);
 long long   buf_timing_collect_kernel(int kernel_id, double* total_ms, double* total_work);
@@ -764,7 +770,66 @@ int     buf_vgicp_batched(const buf_voxel_map_t* map, const float* src, const fl
                           double rel_fitness, double rel_rmse, double* T_out_f64, double* fitness_out, double* rmse_out,
                           int* iters_out, int* row_out, void* ws, size_t ws_bytes, void* stream);
 
-/* N4  Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
+/* N10  Maximum-clique inlier selection + truncated-least-squares pose, the method made known by TEASER++ (Yang, Shi, Carlone, "TEASER:
+ * Fast and Certifiable Point Cloud Registration", T-RO 2021): the fourth pose estimator of the classical row, for inlier ratios of a few
+ * per cent, with a per-pair bound on the size of any consistent set.  No TEASER++ source or paper was at hand: this text is the
+ * specification and parity with the authors' code is unpinned.  Deviations: the scale is fixed to 1; the clique comes from a
+ * deterministic greedy heuristic with the k-core bound beside it, not from exact branch and bound; there is no certification stage; N8's
+ * inlier refit is appended.  B pairs per call, 9 kernels after the upload of the pair table on the caller's stream, nothing read back.  Pairs, rows (p_i, q_i), DEAD rows,
+ * d(a, b), e_ij and the arithmetic rules (IEEE fp64, every operation rounded once in the written order, no FMA) are N8's.
+ *   Graph: the vertices are the live rows; an edge ij (i != j) iff e_ij <= d_thr; a bit matrix with a ZERO diagonal.  deg_i = the
+ *   population count of row i.  Dead rows have deg = core = rank = -1.
+ *   Core numbers: core_i = the largest k such that i lies in a subgraph in which every vertex has degree >= k (unique, whatever the
+ *   peeling order).  bound = max core + 1 (0 without live rows): no clique of the graph has more vertices.
+ *   Order: the live rows sorted by (core descending, deg descending, row ascending); rank_i = the place of row i.
+ *   Greedy cliques: the seeds are the first S = min(max_seeds, live rows) rows of the order.  The walk of seed s: members = (s),
+ *   candidates = row s; while candidates are left, the candidate of lowest rank becomes the next member and the candidates are ANDed
+ *   with its row (rows ranked before s take part like any other).  size[r] = the walk length of the seed of rank r.  The winner has the
+ *   largest size, ties to the lowest rank.  K = min(size, max_members); the members m_0 .. m_{K-1} are the first K of the winner's walk
+ *   in walk order.  size < 3: NOTHING.
+ *   Rotation, GNC-TLS over the translation-invariant measurements: for a < b in lexicographic order alpha = p[m_b] - p[m_a], beta =
+ *   q[m_b] - q[m_a], M = K (K - 1) / 2 of them.  c2 = tim_thr tim_thr (formed once on the host).  w = 1; iteration it = 0, 1, ...:
+ *   H = sum w alpha beta^T; R from H as in N8 (V diag(1, 1, det(V U^T)) U^T, the identity for H = 0 or a non-finite H); r2 =
+ *   |beta - R alpha|^2 with R alpha as ((R0 ax + R1 ay) + R2 az); in iteration 0: g = 2 max(r2) / c2 - 1, g <= 0 stops with all weights
+ *   1 and gnc_steps = 1, else mu = 1 / g; hi = ((mu + 1) / mu) c2, lo = (mu / (mu + 1)) c2; the new weight is 0 if r2 >= hi, 1 if
+ *   r2 <= lo, else sqrt((c2 (mu (mu + 1))) / r2) - mu; the exact zeros and ones are counted; stop after this iteration if it >= 1 and
+ *   zeros + ones == M and (zeros, ones) equal the previous iteration's (before iteration 0: (0, M)), or if it + 1 == gnc_iterations;
+ *   mu <- mu gnc_factor.  The rotation is the R of the last iteration run, gnc_steps the number of iterations run.  H and the two
+ *   counts are summed over 256 lanes (lane l takes the measurements (a, a + 1 + l + 256 k) of every a, in ascending order) and a tree.
+ *   Translation, component-wise TLS voting: x_k = q[m_k] - (R p[m_k]).  Per axis with the values v_k and c = t_thr: the 2K endpoints
+ *   v_k - c, v_k + c sorted ascending into e_0 .. e_{2K-1}; candidates h_j = (e_j + e_{j+1}) 0.5; the consensus set I_j = {k : |v_k -
+ *   h_j| <= c} (an empty one is skipped); est_j = (sum over I_j of v_k) / |I_j| in member order; cost_j = sum over I_j of (v_k -
+ *   est_j)^2 + (K - |I_j|) (c c); the component is the est_j of least cost, ties to the lowest j.
+ *   Polish: N8's refinement unchanged, started from (R, t) with inlier_thr and refine_iterations.  Fewer than 3 final inliers: NOTHING.
+ * Outputs (device).  T_out f64[B,4,4] src -> tgt.  info_out int32[B,8] = status (BUF_CLIQUE_*), live rows, bound, the winner's size,
+ *   the winner's rank (-1 without one), K, gnc_steps, the final inlier count.  NOTHING: the identity exactly, final count 0, no inliers.
+ *   Nullable: deg_out / core_out / rank_out int32[sum n]; sizes_out int32[B,max_seeds] (tail -1); members_out int32[B,max_members]
+ *   (rows, tail -1); weights_out f64[B, max_members (max_members - 1) / 2] (the last weights computed, NaN tail; all NaN without a
+ *   rotation); pose0_out f64[B,12] (R row-major and t before the polish; the identity and 0 without one); inliers_out uint8[sum n].
+ *   Integer LDS atomics only, every float sum in a fixed order: a pair's outputs are the same bits alone, in any batch, in any batch
+ *   order and on reruns.
+ * BUF_EINVAL before any device work for npairs outside 0..65535, negative lengths, more than BUF_SC2_MAX_ROWS correspondences in a
+ * pair, a null required argument with npairs > 0 (src / tgt / corr only where their rows are not zero), d_thr / tim_thr / t_thr /
+ * inlier_thr not finite and > 0 (tim_thr and t_thr: and so their squares), max_seeds outside 1..1024, max_members outside 3..512,
+ * gnc_factor not finite and > 1, gnc_iterations outside 1..1000, refine_iterations < 0, and a workspace that is null or smaller than
+ * buf_clique_ws_bytes (sized from the actual lengths: 116 bytes per row, the two bit matrices, 4 max_seeds (max_members + 2) + 192
+ * bytes per pair, each array rounded up to 256 bytes; 0 for arguments out of range).  npairs == 0 succeeds and touches nothing; a pair
+ * with n == 0 returns the identity, NOTHING and zeros (winner's rank -1). */
+#define BUF_CLIQUE_NOTHING 0
+#define BUF_CLIQUE_OK      1
+size_t  buf_clique_ws_bytes(const int* corr_lengths_host, int npairs, int max_seeds, int max_members);
+int     buf_clique_batched(const float* src, const int* src_lengths_host, const float* tgt, const int* tgt_lengths_host,
+                           const int* corr /* int32[sum corr_lengths,2]: (src row, tgt row), local to the pair's clouds */,
+                           const int* corr_lengths_host, int npairs,
+                           double d_thr, double tim_thr, double t_thr, double inlier_thr,          /* -, d_thr, d_thr / 2, d_thr */
+                           int max_seeds, int max_members, double gnc_factor, int gnc_iterations,  /* 64, 256, 1.4, 100 */
+                           int refine_iterations,                                                   /* 20 */
+                           double* T_out /* f64[B,4,4] src -> tgt */, int* info_out /* int32[B,8] */,
+                           int* deg_out, int* core_out, int* rank_out, int* sizes_out, int* members_out, double* weights_out,
+                           double* pose0_out, unsigned char* inliers_out /* nullable */,
+                           void* ws, size_t ws_bytes, void* stream);
+
+/* N4 Pair statistics under a given transform: P pairs over C shared clouds per call (what overlap ratio, inlier RMSE and the 6x6
  * information matrix of a pair are made of; the evaluation half of an ICP round without the loop).
  * pts f32[sum lengths_host,3] stacks the C clouds; pair k = (pair_src_host[k], pair_tgt_host[k], T_f64[k]) with T_f64 f64[P,4,4]
  * (device) mapping the source cloud into the frame of the target cloud.  A cloud may appear in any number of pairs, on either side,
