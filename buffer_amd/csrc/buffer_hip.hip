@@ -28,6 +28,7 @@
 #include "convnet_w24p.hip"
 #include "convnet_w24a.hip"
 #include "costnet.hip"
+#include "costnet_w24.hip"
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "fgr.hip"

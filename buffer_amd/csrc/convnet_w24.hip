@@ -79,7 +79,7 @@ __device__ __forceinline__ wgf2 w24_ldw2(__amdgpu_buffer_rsrc_t rs, unsigned uni
 // One row component I over `niter` x 4 k-steps for the N-tile pair: acc[n][j] += V_Ij(tile, c) * U_Ij(c, n).  The structure is
 // wg_pass's with one M-tile: step s issues the LDS reads of step s + 2, runs the 12 MFMAs of step s, then forms the operands of
 // step s + 1; the weights (a ring of two k-steps) are reloaded with the k-step two further on as soon as their MFMAs are through.
-template <int I, bool PRIMED, int INEXT>
+template <int I, bool PRIMED, int INEXT, unsigned KSTEP = WG_KSTEP>
 __device__ __forceinline__ void w24_pass(unsigned (&RA)[4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_next, unsigned lofs4, unsigned lofs2,
                                          int niter, wgf4 (&W4)[2][2], wgf2 (&W2)[2][2], wgf4 (&acc)[2][6], wgf2 (&D)[2][6])
 {
@@ -89,7 +89,7 @@ __device__ __forceinline__ void w24_pass(unsigned (&RA)[4], __amdgpu_buffer_rsrc
     unsigned P0 = RA[A1], P1 = RA[A2];
     if constexpr (!PRIMED) {
         W24_LOAD(D[0], P0, P1, 0)
-        W24_LOAD(D[1], P0, P1, WG_KSTEP)
+        W24_LOAD(D[1], P0, P1, KSTEP)
     }
     // row component (d0 - d2 | d1 + d2 | d2 - d1 | d1 - d3) of the six words, then B4^T:
     //     t0 = 4 r0 - 5 r2 + r4,   t1,2 = (r4 - 4 r2) +- (r3 - 4 r1),   t3,4 = (r4 - r2) +- 2 (r3 - r1),   t5 = 4 r1 - 5 r3 + r5
@@ -114,18 +114,18 @@ __device__ __forceinline__ void w24_pass(unsigned (&RA)[4], __amdgpu_buffer_rsrc
         const bool more = it + 1 < niter;
         const unsigned wcur = wp + 4 * it * W24_WSTRIDE;          // this iteration's k-steps 2, 3 ...
         const unsigned wn = more ? wcur + 4 * W24_WSTRIDE : wp_next;   // ... and the k-steps 0, 1 of the next one (or of the next pass)
-        const unsigned adv = more ? 4u * WG_KSTEP : 0u;           // past the end: the iteration's own first steps again (unused)
+        const unsigned adv = more ? 4u * KSTEP : 0u;           // past the end: the iteration's own first steps again (unused)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            if (s < 2) W24_LOAD(D[s & 1], P0, P1, (s + 2) * WG_KSTEP)
+            if (s < 2) W24_LOAD(D[s & 1], P0, P1, (s + 2) * KSTEP)
             else {
                 if (s == 2) { P0 += adv; P1 += adv; }              // the next iteration's base from here on
                 if constexpr (INEXT >= 0) {                        // last iteration: the next pass's first steps instead
                     unsigned q0 = more ? P0 : RA[A1N], q1 = more ? P1 : RA[A2N];
-                    W24_LOAD(D[s & 1], q0, q1, (s - 2) * WG_KSTEP)
+                    W24_LOAD(D[s & 1], q0, q1, (s - 2) * KSTEP)
                 } else
-                    W24_LOAD(D[s & 1], P0, P1, (s - 2) * WG_KSTEP)
+                    W24_LOAD(D[s & 1], P0, P1, (s - 2) * KSTEP)
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -153,7 +153,8 @@ __device__ __forceinline__ void w24_pass(unsigned (&RA)[4], __amdgpu_buffer_rsrc
 // The bias enters column component 1 -- the one A4^T carries into all four columns with weight 1 -- before pass 1.
 // On entry W holds the first two k-steps at wp, on exit those at wp_after.
 // NOBIAS: bias_lane may be null, as in wg_round (the upper K half of w24k_layer_ksplit, csrc/convnet_w24k.hip, carries no bias).
-template <bool NOBIAS = false>
+// KSTEP: LDS bytes between k-steps, as in wg_round (k_cost_net_w24's maps, csrc/costnet_w24.hip).
+template <bool NOBIAS = false, unsigned KSTEP = WG_KSTEP>
 __device__ __forceinline__ void w24_round(unsigned (&RA)[4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_after, unsigned lofs4, unsigned lofs2,
                                           int niter, unsigned pstride, const float* __restrict__ bias_lane, wgf4 (&W4)[2][2], wgf2 (&W2)[2][2],
                                           wgf4 (&Y)[2][2][4])
@@ -181,7 +182,7 @@ __device__ __forceinline__ void w24_round(unsigned (&RA)[4], __amdgpu_buffer_rsr
             for (int n = 0; n < 2; n++) acc[n][1] += bv[n];
         }
         constexpr int ICHAIN = (INEXT != 0 && wg_chains(I)) ? INEXT : -1;
-        w24_pass<I, wg_chains(I - 1), ICHAIN>(RA, rs, wp + I * pstride, INEXT == 0 ? wp_after : wp + (I + 1) * pstride, lofs4, lofs2, niter, W4, W2, acc, D);
+        w24_pass<I, wg_chains(I - 1), ICHAIN, KSTEP>(RA, rs, wp + I * pstride, INEXT == 0 ? wp_after : wp + (I + 1) * pstride, lofs4, lofs2, niter, W4, W2, acc, D);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int n = 0; n < 2; n++) {

@@ -348,8 +348,19 @@ __device__ long long* cv_stamp_ptr;       // development build (-DCV_STAMP): s_m
 #define CV_STAMP_AT(SLOT)
 #endif
 
+// The forms of csrc/costnet_w24.hip (defined there): F(2x4) tiles in layers 2 and 4, the Winograd form in layer 6 behind a channel-major layer 5
+#define CW_CS5 72         // channel stride of layer 5's channel-major 8 x 8 map (= 8 mod 64: the three tile rows of layer 6's M-tile start on
+                          //   the banks 0, 16, 32 and take six each; the half-wave's second channel takes the six from 8, 24, 40 on)
+template <int C, int CS, int USED>
+__device__ __forceinline__ void cw24_zero_spare(float* __restrict__ map);
+template <int HIN, int RS, int CS, int NTX, int TYPM, int CIN, int RSO, int CSO>
+__device__ __forceinline__ void cw24_layer(float* __restrict__ map, const float* __restrict__ wt, const float* __restrict__ bias, int pair, int t);
+
+// W24 (k_cost_net_w24): f24[0], f24[1] nullable F(2x4) sets of layers 2 and 4, f24[2] nullable F(2x2) set (group 1) of layer 6; a layer
+// without a set, and every layer of the default W24 = false (k_cost_net), runs the forms below as they always were.
+template <bool W24 = false>
 __device__ __forceinline__ void cost_net_body(const float* __restrict__ s_eq, const float* __restrict__ t_eq, const CostNetParams& P,
-                                              float* __restrict__ ind_out, float* __restrict__ lds)
+                                              float* __restrict__ ind_out, float* __restrict__ lds, const float* const* f24 = nullptr)
 {
     // lds: ONE buffer of CV_BUF floats (75 KB): two workgroups per CU
     float* bufA = lds;                       // every map from layer 1 on (layers 2..6 rewrite it in place)
@@ -468,19 +479,44 @@ __device__ __forceinline__ void cost_net_body(const float* __restrict__ s_eq, co
     }
     // ---- phase B: layers 2..6 rewrite the buffer in place; the three tiny last layers hop through its free parts -----------
     //                                 in: size rows stride | tile rows per M-tile | Cin | N-tiles, M-tiles per wavefront | out
-    cw_layer<16, 16, CW_CS1, 2, 64, 2, 2, 0, 14, CW_CS2, false>(bufA, P.wt[2], P.bias[2], w & 1, 2 * (w >> 1));   // 16x16 -> 14x14, 64 ch
+    bool f24_2 = false, f24_4 = false, f24_6 = false;
+    if constexpr (W24) { f24_2 = f24[0] != nullptr; f24_4 = f24[1] != nullptr; f24_6 = f24[2] != nullptr; }
+    if (W24 && f24_2) {                      // wavefront (pair, M-tile): M-tile 0 holds the tile rows 0..3, M-tile 1 the rows 4..6
+        if constexpr (W24) {
+            cw24_zero_spare<64, CW_CS1, 256>(bufA);
+            __syncthreads();
+            cw24_layer<16, 16, CW_CS1, 4, 4, 64, 14, CW_CS2>(bufA, f24[0], P.bias[2], w & 1, w >> 1);
+        }
+    } else
+        cw_layer<16, 16, CW_CS1, 2, 64, 2, 2, 0, 14, CW_CS2, false>(bufA, P.wt[2], P.bias[2], w & 1, 2 * (w >> 1));   // 16x16 -> 14x14, 64 ch
     __syncthreads();
     CV_STAMP_AT(3)
     cw_layer<14, 14, CW_CS2, 2, 64, 2, 2, 1, 12, CW_CS3, false>(bufA, P.wt[3], P.bias[3], w, 0);                  // -> 12x12, 128 ch
     __syncthreads();
     CV_STAMP_AT(4)
-    cw_layer<12, 12, CW_CS3, 3, 128, 2, 2, 0, 12, CW_CS3, false>(bufA, P.wt[4], P.bias[4], w, 0);                 // -> 10x10 (rows of 12)
+    if (W24 && f24_4) {                      // wavefront w owns pair w over the one M-tile of 5 x 3 tiles
+        if constexpr (W24) {
+            cw24_zero_spare<128, CW_CS3, 144>(bufA);
+            __syncthreads();
+            cw24_layer<12, 12, CW_CS3, 3, 5, 128, 12, CW_CS3>(bufA, f24[1], P.bias[4], w, 0);
+        }
+    } else
+        cw_layer<12, 12, CW_CS3, 3, 128, 2, 2, 0, 12, CW_CS3, false>(bufA, P.wt[4], P.bias[4], w, 0);             // -> 10x10 (rows of 12)
     __syncthreads();
     CV_STAMP_AT(5)
-    cw_layer<10, 12, CW_CS3, 4, 128, 1, 1, 0, 0, CV_C64, true>(bufA, P.wt[5], P.bias[5], w, 0);                   // -> 8x8, position-major
-    __syncthreads();
-    CV_STAMP_AT(6)
-    cv_conv_layer<3, 1, 64, 64, 8, 3, true>(bufA, bufA, P.wt[6], P.bias[6], w, true);            // -> 6x6 (36 x 68 floats)
+    if (W24 && f24_6) {
+        if constexpr (W24) {
+            cw_layer<10, 12, CW_CS3, 4, 128, 1, 1, 0, 8, CW_CS5, false>(bufA, P.wt[5], P.bias[5], w, 0);          // -> 8x8, channel-major
+            __syncthreads();
+            CV_STAMP_AT(6)
+            cw_layer<8, 8, CW_CS5, 3, 64, 1, 1, 0, 0, CV_C64, true>(bufA, f24[2], P.bias[6], w, 0);               // -> 6x6, position-major
+        }
+    } else {
+        cw_layer<10, 12, CW_CS3, 4, 128, 1, 1, 0, 0, CV_C64, true>(bufA, P.wt[5], P.bias[5], w, 0);               // -> 8x8, position-major
+        __syncthreads();
+        CV_STAMP_AT(6)
+        cv_conv_layer<3, 1, 64, 64, 8, 3, true>(bufA, bufA, P.wt[6], P.bias[6], w, true);        // -> 6x6 (36 x 68 floats)
+    }
     __syncthreads();
     CV_STAMP_AT(7)
     float* hop1 = lds + 4096;
@@ -528,11 +564,10 @@ extern "C" int buf_cost_winograd_group(int layer)
     return layer >= 0 && layer <= 5 ? group[layer] : 0;
 }
 
-static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
-                           const long long* s_rows, const long long* t_rows, int ele_n, float* ind_out, void* stream, const char* who,
-                           const int* only_if = nullptr)
+// The kernel parameters of a launch (shared with csrc/costnet_w24.hip)
+static int cost_net_params(CostNetParams& P, const float* const* wt_host, const float* const* bias_host, const long long* s_rows,
+                           const long long* t_rows, int ele_n, const int* only_if, const char* who)
 {
-    CostNetParams P;
     for (int l = 0; l < CV_LAYERS; l++) {
         P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
         BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "%s: null weights for layer %d", who, l);
@@ -542,29 +577,27 @@ static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const fl
     P.row_floats = 32 * P.chan_floats;
     P.skip_floats = s_rows ? 20 : 0;                         // elevation row 0 of every channel is not part of the cost volume
     P.only_if = only_if;
-    size_t lds = sizeof(float) * CV_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = only_if ? grant_dynamic_lds((const void*)k_cost_net_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cost_net, lds, grant)) return rc;
-    // EXECUTED flops per match: layer 0 in its separated form (S-term 60 x 480 x 32, T-term 54 x 288 x 32 MAC instead of the
-    // dense 972 x 864 x 32), then the valid convolutions 18x3x18 -> 16x1x16 -> 14 -> 12 -> 10 -> 8 -> 6 -> 4 -> 2 -> 1:
-    // 2 * sum(out positions * K * Cout), layers 1..5 with 16 products per 2 x 2 output tile (Winograd) = 0.0519 GFLOP.  The dense algorithmic count of SURVEY 8d is 0.160 GFLOP/match
-    // (bench.py reports both; the roofline fraction is taken on the executed count).
-    static const double macs_per_match =
-        60.0 * 480 * 32 + 54.0 * 288 * 32 + 16.0 * 64 * 96 * 64 +
-        16.0 * (49.0 * 64 * 64 + 36.0 * 64 * 128 + 25.0 * 128 * 128 + 16.0 * 128 * 64) +        // layers 2..5: 16 components per 2 x 2 tile
-        36.0 * 576 * 64 + 16.0 * 576 * 32 + 4.0 * 288 * 32 + 1.0 * 128 * 20;
-    TimedSpan span;
-    bool timed = !only_if && timing_begin((hipStream_t)stream, &span, 2.0 * macs_per_match * m, BUF_TIMED_COST_NET);   // (a masked re-run is not a full launch)
+    return BUF_OK;
+}
+
+// EXECUTED flops per match: layer 0 in its separated form (S-term 60 x 480 x 32, T-term 54 x 288 x 32 MAC instead of the
+// dense 972 x 864 x 32), then the valid convolutions 18x3x18 -> 16x1x16 -> 14 -> 12 -> 10 -> 8 -> 6 -> 4 -> 2 -> 1:
+// 2 * sum(out positions * K * Cout), layers 1..5 with 16 products per 2 x 2 output tile (Winograd) = 0.0519 GFLOP.  The dense algorithmic count of SURVEY 8d is 0.160 GFLOP/match
+// (bench.py reports both; the roofline fraction is taken on the executed count).
+static const double cost_net_macs_per_match =
+    60.0 * 480 * 32 + 54.0 * 288 * 32 + 16.0 * 64 * 96 * 64 +
+    16.0 * (49.0 * 64 * 64 + 36.0 * 64 * 128 + 25.0 * 128 * 128 + 16.0 * 128 * 64) +        // layers 2..5: 16 components per 2 x 2 tile
+    36.0 * 576 * 64 + 16.0 * 576 * 32 + 4.0 * 288 * 32 + 1.0 * 128 * 20;
+
 #ifdef CV_STAMP
-    long long* stamps = nullptr;
-    BUF_CHECK_HIP(hipMalloc(&stamps, (size_t)m * 16 * sizeof(long long)));
-    BUF_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cv_stamp_ptr), &stamps, sizeof(stamps)));
-#endif
-    if (only_if) k_cost_net_rerun<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, P, ind_out);
-    else k_cost_net<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, P, ind_out);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-#ifdef CV_STAMP
+static int cv_stamp_begin(int m, long long** stamps)
+{
+    BUF_CHECK_HIP(hipMalloc(stamps, (size_t)m * 16 * sizeof(long long)));
+    BUF_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cv_stamp_ptr), stamps, sizeof(*stamps)));
+    return BUF_OK;
+}
+static int cv_stamp_end(int m, long long* stamps, void* stream, const char* kernel)
+{
     if (m >= 2048) {
         BUF_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
         long long* h = (long long*)malloc((size_t)m * 16 * sizeof(long long));
@@ -573,10 +606,35 @@ static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const fl
         double d[8] = {};
         for (int b = m / 2; b < m; b++)
             for (int i = 0; i < 8; i++) d[i] += (double)(h[(size_t)b * 16 + i + 1] - h[(size_t)b * 16 + i]);
-        for (int i = 0; i < 8; i++) fprintf(stderr, "  CV_STAMP %-20s %8.0f cycles per match\n", name[i], d[i] / (m - m / 2));
+        for (int i = 0; i < 8; i++) fprintf(stderr, "  CV_STAMP %s %-20s %8.0f cycles per match\n", kernel, name[i], d[i] / (m - m / 2));
         free(h);
     }
     (void)hipFree(stamps);
+    return BUF_OK;
+}
+#endif
+
+static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
+                           const long long* s_rows, const long long* t_rows, int ele_n, float* ind_out, void* stream, const char* who,
+                           const int* only_if = nullptr)
+{
+    CostNetParams P;
+    if (int rc = cost_net_params(P, wt_host, bias_host, s_rows, t_rows, ele_n, only_if, who)) return rc;
+    size_t lds = sizeof(float) * CV_BUF;
+    static LdsGrant grant, grant_rerun;
+    if (int rc = only_if ? grant_dynamic_lds((const void*)k_cost_net_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cost_net, lds, grant)) return rc;
+    TimedSpan span;
+    bool timed = !only_if && timing_begin((hipStream_t)stream, &span, 2.0 * cost_net_macs_per_match * m, BUF_TIMED_COST_NET);   // (a masked re-run is not a full launch)
+#ifdef CV_STAMP
+    long long* stamps = nullptr;
+    if (int rc = cv_stamp_begin(m, &stamps)) return rc;
+#endif
+    if (only_if) k_cost_net_rerun<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, P, ind_out);
+    else k_cost_net<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, P, ind_out);
+    if (timed) timing_end((hipStream_t)stream, &span);
+    BUF_LAUNCH_CHECK();
+#ifdef CV_STAMP
+    if (int rc = cv_stamp_end(m, stamps, stream, "k_cost_net")) return rc;
 #endif
     return BUF_OK;
 }

@@ -1261,14 +1261,52 @@ def separate_cost_layer0(w):
     return ws.reshape(-1, cout).astype(np.float32), wt.reshape(-1, cout).astype(np.float32)
 
 
+# What a cost net built without a form argument runs (k_cost_net_w24, csrc/costnet_w24.hip; profiles/cost_f24_ab.md): 'all': F(2x4) tiles in
+# layers 2 and 4 and the Winograd F(2x2) form in layer 6; 'l2', 'l4', 'l6': one of the three alone; 'off' or None: k_cost_net as it is, bit
+# for bit.  The argument f24= of CostVolumeNet, CostVolumeNetSplit and registration.CostVolume picks one per net.
+COST_F24_DEFAULT = 'all'
+COST_F24_PARTS = {'all': (2, 4, 6), 'l2': (2,), 'l4': (4,), 'l6': (6,), 'off': (), None: ()}
+
+
+def cost_f24_parts(f24):
+    if f24 is None:
+        f24 = COST_F24_DEFAULT
+    if f24 is True:
+        f24 = 'all'
+    if f24 is False:
+        f24 = 'off'
+    if f24 not in COST_F24_PARTS:
+        raise ValueError(f"f24 = {f24!r}: one of 'all', 'l2', 'l4', 'l6', 'off'")
+    return COST_F24_PARTS[f24]
+
+
+def cost_f24_filters(layers, parts):
+    """The three extra filter sets of k_cost_net_w24 (None where the layer keeps k_cost_net's form): layers 2 and 4 in the F(2x4) tiling
+    (winograd_f24_tile_weights of the (3,1,3) filters as [Cout][Cin][3][3]), layer 6 in the F(2x2) tiling with one N-tile per group."""
+    sets = []
+    for l in (2, 4, 6):
+        if l not in parts:
+            sets.append(None)
+            continue
+        w = layers[l][0]
+        assert tuple(w.shape[2:]) == (3, 1, 3), w.shape
+        w2d = np.ascontiguousarray(w[:, :, :, 0, :])
+        sets.append(winograd_tile_weights(w2d, ng=1) if l == 6 else winograd_f24_tile_weights(w2d))
+    return sets
+
+
 class CostVolumeNet:
     """Device weights of CostNet re-laid for csrc/costnet.hip: layer 0 in its separated form (separate_cost_layer0: Ws then
     Wt in one buffer), layers 6..9 as Wt[((dn*KH+dk)*KW+dl)*Cin + c][Cout], MFMA-tiled; layers 1..5 as U = G g G^T in the
-    Winograd tiling (winograd_tile_weights; groups per buf_cost_winograd_group; layer 1 with its three k planes as channels)."""
+    Winograd tiling (winograd_tile_weights; groups per buf_cost_winograd_group; layer 1 with its three k planes as channels).
+    f24: the parts that run in k_cost_net_w24's forms (COST_F24_DEFAULT); their sets live in buffers of their own (self.wt24)."""
 
-    def __init__(self, layers, device):
+    def __init__(self, layers, device, f24=None):
         """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout])"""
         assert len(layers) == 10
+        self.parts = cost_f24_parts(f24)
+        self.wt24 = [None if a is None else torch.from_numpy(a).to(device) for a in cost_f24_filters(layers, self.parts)]
+        self._fp = (C.c_void_p * 3)(*[None if t is None else t.data_ptr() for t in self.wt24])
         self.wt, self.bias = [], []
         for i, (w, b) in enumerate(layers):
             cout, cin = w.shape[0], w.shape[1]
@@ -1307,6 +1345,10 @@ class CostVolumeNet:
         s_eq, t_eq = s_eq.contiguous(), t_eq.contiguous()
         m = s_eq.shape[0]
         out = torch.empty((m,), dtype=torch.float32, device=s_eq.device)
+        if self.parts:
+            check(L.buf_cost_volume_net_w24(_ptr(s_eq), _ptr(t_eq), m, self._wp, self._bp, self._fp, _ptr(out), _stream()),
+                  "buf_cost_volume_net_w24")
+            return out
         check(L.buf_cost_volume_net(_ptr(s_eq), _ptr(t_eq), m, self._wp, self._bp, _ptr(out), _stream()),
               "buf_cost_volume_net")
         return out
@@ -1321,6 +1363,10 @@ class CostVolumeNet:
         s_rows, t_rows = _dev(s_rows, torch.int64, "s_rows"), _dev(t_rows, torch.int64, "t_rows")
         m = int(s_rows.shape[0])
         out = torch.empty((m,), dtype=torch.float32, device=equi.device)
+        if self.parts:
+            check(L.buf_cost_volume_net_w24_gather(_ptr(equi), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self._fp, _ptr(out),
+                                                   _stream()), "buf_cost_volume_net_w24_gather")
+            return out
         check(L.buf_cost_volume_net_gather(_ptr(equi), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, _ptr(out), _stream()),
               "buf_cost_volume_net_gather")
         return out
@@ -1330,9 +1376,10 @@ class CostVolumeNetSplit:
     """CostNet on the f16 matrix pipe with fp32-equivalent arithmetic (csrc/costnet_h3.hip): opt-in next to CostVolumeNet, same calls.
     Layer 0 in its separated form (separate_cost_layer0), layer 1 with its three k' planes as channels, every layer direct form."""
 
-    def __init__(self, layers, device):
-        """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout])"""
+    def __init__(self, layers, device, f24=None):
+        """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout]); f24: the fp32 re-run's kernel, as in CostVolumeNet"""
         assert len(layers) == 10
+        self.parts = cost_f24_parts(f24)
         mats = []
         w0 = layers[0][0]
         assert tuple(w0.shape) == (32, 32, 3, 3, 3), w0.shape
@@ -1361,13 +1408,18 @@ class CostVolumeNetSplit:
         self._bp = (C.c_void_p * 10)(*[t.data_ptr() for t in self.bias])
         # safe by construction (csrc/split_safe.hip): the fp32 kernel's weights ride along and re-run the matches the split kernel flags
         self.safe = not os.environ.get('BUF_SPLIT_UNSAFE')
-        self.f32 = CostVolumeNet(layers, device) if self.safe else None
+        self.f32 = CostVolumeNet(layers, device, f24=f24) if self.safe else None
         self.last_flags = None
 
     def _safe(self, s_eq, t_eq, s_rows, t_rows, m, dev):
         L = _lib.lib()
         out = torch.empty((m,), dtype=torch.float32, device=dev)
         self.last_flags = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
+        if self.parts:
+            check(L.buf_cost_volume_net_split_safe_w24(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp,
+                                                       self.f32._bp, self.f32._fp, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()),
+                  "buf_cost_volume_net_split_safe_w24")
+            return out
         check(L.buf_cost_volume_net_split_safe(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp,
                                                self.f32._bp, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()),
               "buf_cost_volume_net_split_safe")

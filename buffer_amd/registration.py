@@ -11,7 +11,7 @@ class CostVolume:
     (csrc/costnet.hip).  The kernel is written for the released geometry (32 channels, 5 elevation rows,
     azi_n = 20); anything else raises -- there is no library-convolution path in the product."""
 
-    def __init__(self, W, device, azi_n=20, arith='f32'):
+    def __init__(self, W, device, azi_n=20, arith='f32', f24=None):
         if arith not in ('f32', 'split'):
             raise ValueError(f"cnn_arith must be 'f32' or 'split', got {arith!r}")
         if azi_n != 20:
@@ -23,7 +23,9 @@ class CostVolume:
             layers.append(_fold_bn(W[f'{p}.{i}.weight'], W[f'{p}.{i}.bias'], W[f'{p}.{bn}.running_mean'], W[f'{p}.{bn}.running_var']))
         layers.append((np.asarray(W[f'{p}.27.weight'], np.float32), np.asarray(W[f'{p}.27.bias'], np.float32)))
         # 'split': csrc/costnet_h3.hip -- the same network on the f16 matrix pipe, operands split hi + 2^-11 lo' (fp32-equivalent)
-        self.fused = ops.CostVolumeNetSplit(layers, device) if arith == 'split' else ops.CostVolumeNet(layers, device)
+        # f24: the parts of the fp32 kernel (and of the split form's fp32 re-run) in k_cost_net_w24's forms: 'all' | 'l2' | 'l4' | 'l6' | 'off'
+        # (None: ops.COST_F24_DEFAULT)
+        self.fused = ops.CostVolumeNetSplit(layers, device, f24=f24) if arith == 'split' else ops.CostVolumeNet(layers, device, f24=f24)
 
     def __call__(self, d1, d2):
         """d1,d2 f32[M,32,5,20] -> expected azimuth shift f32[M]."""

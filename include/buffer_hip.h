@@ -431,6 +431,15 @@ int     buf_cost_volume_net(const float* s_eq, const float* t_eq, int m, const f
  * match i pairs row s_rows[i] with row t_rows[i] (DEVICE int64[m]); elevation rows 1..ele_n-2 are read inside the kernel. */
 int     buf_cost_volume_net_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
                                    const float* const* wt_host, const float* const* bias_host, float* ind_out, void* stream);
+/* The twins through k_cost_net_w24 (csrc/costnet_w24.hip): F(2x4, 3x3) tiles in layers 2 and 4, the Winograd F(2x2) form in layer 6.
+ * f24_host: HOST array of 3 DEVICE pointers, each nullable -- [0], [1]: buf_winograd_f24_tile_weights of the [Cout][Cin][3][3] filters
+ * of layers 2 and 4, [2]: buf_winograd_tile_filters(w2d, 64, 64, 1, 4, out) of layer 6.  A layer without a set runs as in
+ * buf_cost_volume_net from wt_host (all ten matrices are still required).  The timed span is BUF_TIMED_COST_NET with the same work figure. */
+int     buf_cost_volume_net_w24(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
+                                const float* const* f24_host, float* ind_out, void* stream);
+int     buf_cost_volume_net_w24_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
+                                       const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
+                                       float* ind_out, void* stream);
 
 /* A13, split-f16 form -- the same network with fp32-EQUIVALENT arithmetic on the f16 matrix pipe (csrc/costnet_h3.hip; opt-in, see
  * buf_cylindrical_net_split for the operand split): layer 0 separated as above, every layer a direct-form correlation.
@@ -455,6 +464,11 @@ int     buf_cost_volume_net_split_safe(const float* s_eq, const float* t_eq, int
                                        int m, const void* const* wt_split_host, const float* const* bias_split_host,
                                        const float* const* wt_f32_host, const float* const* bias_f32_host, float* ind_out,
                                        int* status_dev, int* flags_ws, void* stream);
+/* The same with the masked re-run through k_cost_net_w24_rerun: f24_host as for buf_cost_volume_net_w24, whose bits the flagged matches carry. */
+int     buf_cost_volume_net_split_safe_w24(const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows, const long long* t_rows,
+                                           int m, const void* const* wt_split_host, const float* const* bias_split_host,
+                                           const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,
+                                           float* ind_out, int* status_dev, int* flags_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A14  hypotheses + all-vs-all scoring (models/BUFFER.py:295-311): ind f32[m] -> R f32[m,3,3], t f32[m,3],

@@ -35,9 +35,23 @@ for k in ('k_patch_voxelize', 'k_cyl_net_wg', 'k_cyl_net_w24', 'k_cyl_net_w24k',
     for c, name in (('SQ_INSTS_VALU', 'valu_per_patch'), ('SQ_INSTS_MFMA', 'mfma_per_patch'), ('SQ_WAVES', 'waves_per_patch')):
         if all(c in x for x in d):
             kernels[k][name] = sum(x[c] for x in d) / len(d) / patches
+# the cost net, per match (one workgroup per match; matches per launch from the work figure of its timed span, as in make_traffic.py)
+cost = [o for o in bench.get('roofline_other', []) if o and o['kernel'].startswith('k_cost_net')]
+matches = cost[0]['avg_algorithmic_flops'] / 51905536.0 if cost else None
+for k in ('k_cost_net', 'k_cost_net_w24'):
+    d = list(rows.get(k, {}).values())
+    if not d or not matches:
+        continue
+    g = max(x['grid'] for x in d)
+    d = [x for x in d if x['grid'] == g]
+    kernels[k] = {'launches': len(d), 'matches_per_launch': matches}
+    for c, name in (('SQ_INSTS_VALU', 'valu_per_match'), ('SQ_INSTS_MFMA', 'mfma_per_match'), ('SQ_WAVES', 'waves_per_match')):
+        if all(c in x for x in d):
+            kernels[k][name] = sum(x[c] for x in d) / len(d) / matches
 lib = ctypes.CDLL(os.path.join(ROOT, 'buffer_amd', 'libbuffer_hip.so'))
 src = {f: hashlib.sha256(open(os.path.join(ROOT, 'buffer_amd', 'csrc', f), 'rb').read()).hexdigest()[:16]
-       for f in ('voxelize.hip', 'convnet_wg.hip', 'convnet_w24.hip', 'convnet_w24k.hip', 'convnet_w24p.hip', 'convnet_w24a.hip', 'convnet_h3.hip')}
+       for f in ('voxelize.hip', 'convnet_wg.hip', 'convnet_w24.hip', 'convnet_w24k.hip', 'convnet_w24p.hip', 'convnet_w24a.hip', 'convnet_h3.hip',
+                 'costnet.hip', 'costnet_w24.hip')}
 json.dump(dict(source='rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVES on the bench.py command of the line in `bench` '
                       '(wave-level instruction counts; SQ_INSTS_VALU includes the MFMAs)',
                lib_version=int(lib.buf_version()), csrc_sha256_16=src, bench=dict(value=bench['value'], config=cfg), kernels=kernels),
