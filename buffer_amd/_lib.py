@@ -154,6 +154,9 @@ _SIGNATURES = {
     "buf_cost_volume_net_w24": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "buf_cost_volume_net_w24_gather": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "buf_cost_volume_net_split_safe_w24": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "buf_cost_volume_net_w24b": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "buf_cost_volume_net_w24b_gather": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "buf_cost_volume_net_split_safe_w24b": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "buf_hypotheses_score": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "buf_ransac_ws_bytes": (_sz, [_i]),
     "buf_ransac_kabsch": (_i, [_vp, _vp, _vp, _i, _i, C.c_uint64, _f, _f, _vp, _vp, _vp, _sz, _vp]),

@@ -29,6 +29,7 @@
 #include "convnet_w24a.hip"
 #include "costnet.hip"
 #include "costnet_w24.hip"
+#include "costnet_w24b.hip"
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "fgr.hip"

@@ -356,9 +356,15 @@ __device__ __forceinline__ void cw24_zero_spare(float* __restrict__ map);
 template <int HIN, int RS, int CS, int NTX, int TYPM, int CIN, int RSO, int CSO>
 __device__ __forceinline__ void cw24_layer(float* __restrict__ map, const float* __restrict__ wt, const float* __restrict__ bias, int pair, int t);
 
+// The forms of csrc/costnet_w24b.hip (defined there): layer 1 on F(2x4) tiles, one k' plane at a time; layer 3 as F(2x4) rows + an F(2x2) tail
+__device__ __forceinline__ void cw24b_layer1(float* __restrict__ lds, const float* __restrict__ wt, const float* __restrict__ bias, int w);
+__device__ __forceinline__ void cw24b_layer3(float* __restrict__ map, const float* __restrict__ wt24, const float* __restrict__ wt22,
+                                             const float* __restrict__ bias, int w);
+
 // W24 (k_cost_net_w24): f24[0], f24[1] nullable F(2x4) sets of layers 2 and 4, f24[2] nullable F(2x2) set (group 1) of layer 6; a layer
 // without a set, and every layer of the default W24 = false (k_cost_net), runs the forms below as they always were.
-template <bool W24 = false>
+// W24B (k_cost_net_w24b, with W24): f24[3], f24[4] nullable F(2x4) sets of layers 1 and 3, switched in the same way.
+template <bool W24 = false, bool W24B = false>
 __device__ __forceinline__ void cost_net_body(const float* __restrict__ s_eq, const float* __restrict__ t_eq, const CostNetParams& P,
                                               float* __restrict__ ind_out, float* __restrict__ lds, const float* const* f24 = nullptr)
 {
@@ -427,7 +433,14 @@ __device__ __forceinline__ void cost_net_body(const float* __restrict__ s_eq, co
     // K halves of a pair share the stores (kh = 0: chunks 0, 1; kh = 1: chunks 2, 3): the partial sums of a chunk go from the half
     // that does not store it to the one that does, which holds its 2 x 32 output registers until the last chunk has been read.
     // 64 tile rows x 16 components x 96 channels = 0.44 of the direct form's matrix instructions (3 456 -> 1 536 per wavefront).
-    {
+    bool f24_1 = false, f24_3 = false;
+    if constexpr (W24B) { f24_1 = f24[3] != nullptr; f24_3 = f24[4] != nullptr; }
+    if (W24B && f24_1) {
+        if constexpr (W24B) {
+            cw24b_layer1(lds, f24[3], P.bias[1], w);
+            CV_STAMP_AT(2)
+        }
+    } else {
         int lane_ = threadIdx.x & (WAVE - 1);
         asm volatile("" : "+v"(lane_));
         const int li_ = lane_ & 15, lk_ = lane_ >> 4;
@@ -491,7 +504,10 @@ __device__ __forceinline__ void cost_net_body(const float* __restrict__ s_eq, co
         cw_layer<16, 16, CW_CS1, 2, 64, 2, 2, 0, 14, CW_CS2, false>(bufA, P.wt[2], P.bias[2], w & 1, 2 * (w >> 1));   // 16x16 -> 14x14, 64 ch
     __syncthreads();
     CV_STAMP_AT(3)
-    cw_layer<14, 14, CW_CS2, 2, 64, 2, 2, 1, 12, CW_CS3, false>(bufA, P.wt[3], P.bias[3], w, 0);                  // -> 12x12, 128 ch
+    if (W24B && f24_3) {                     // wavefront w owns pair w: 5 x 3 F(2x4) tiles (rows 0..9), then the F(2x2) tile row 5 (rows 10, 11)
+        if constexpr (W24B) cw24b_layer3(bufA, f24[4], P.wt[3], P.bias[3], w);
+    } else
+        cw_layer<14, 14, CW_CS2, 2, 64, 2, 2, 1, 12, CW_CS3, false>(bufA, P.wt[3], P.bias[3], w, 0);              // -> 12x12, 128 ch
     __syncthreads();
     CV_STAMP_AT(4)
     if (W24 && f24_4) {                      // wavefront w owns pair w over the one M-tile of 5 x 3 tiles

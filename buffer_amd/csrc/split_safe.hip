@@ -128,3 +128,24 @@ extern "C" int buf_cost_volume_net_split_safe_w24(const float* s_eq, const float
     return cost_net_w24_launch(s_eq, t_eq, m, wt_f32_host, bias_f32_host, f24_host, s_rows, t_rows, ele_n, ind_out, stream,
                                "buf_cost_volume_net_split_safe_w24", flags_ws);
 }
+
+// The same with the re-run through k_cost_net_w24b_rerun (csrc/costnet_w24b.hip): f24_host[5] as for buf_cost_volume_net_w24b.
+extern "C" int buf_cost_volume_net_split_safe_w24b(const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows, const long long* t_rows,
+                                                   int m, const void* const* wt_split_host, const float* const* bias_split_host,
+                                                   const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,
+                                                   float* ind_out, int* status_dev, int* flags_ws, void* stream)
+{
+    BUF_REQUIRE(m >= 0, BUF_EINVAL, "buf_cost_volume_net_split_safe_w24b: m=%d", m);
+    if (m == 0) return BUF_OK;
+    BUF_REQUIRE(s_eq && t_eq && wt_split_host && bias_split_host && wt_f32_host && bias_f32_host && f24_host && ind_out && flags_ws, BUF_EINVAL,
+                "buf_cost_volume_net_split_safe_w24b: null argument");
+    BUF_REQUIRE((s_rows == nullptr) == (t_rows == nullptr), BUF_EINVAL, "buf_cost_volume_net_split_safe_w24b: one row list without the other");
+    BUF_REQUIRE(!s_rows || ele_n == 7, BUF_EINVAL, "buf_cost_volume_net_split_safe_w24b: ele_n=%d (the kernels are built for ele_n = 7)", ele_n);
+    hipStream_t s = (hipStream_t)stream;
+    BUF_CHECK_HIP(hipMemsetAsync(flags_ws, 0, sizeof(int) * (size_t)m, s));
+    int rc = cost_net_h3_launch(s_eq, t_eq, m, wt_split_host, bias_split_host, s_rows, t_rows, ele_n, ind_out, status_dev, stream,
+                                "buf_cost_volume_net_split_safe_w24b", flags_ws);
+    if (rc) return rc;
+    return cost_net_w24b_launch(s_eq, t_eq, m, wt_f32_host, bias_f32_host, f24_host, s_rows, t_rows, ele_n, ind_out, stream,
+                                "buf_cost_volume_net_split_safe_w24b", flags_ws);
+}

@@ -1295,18 +1295,61 @@ def cost_f24_filters(layers, parts):
     return sets
 
 
+# The forms of k_cost_net_w24b (csrc/costnet_w24b.hip; profiles/cost_f24b_ab.md) beside those above: 'all': layer 1 on F(2x4) tiles and layer 3
+# as F(2x4) rows with an F(2x2) tail; 'l1', 'l3': one of the two alone; 'off': k_cost_net_w24 (or k_cost_net) as it is, bit for bit.  The
+# argument f24b= picks one per net.  Left alone it is COST_F24B_DEFAULT for a net built with no form argument at all, and 'off' beside an
+# explicit f24=, which asks for one of the older kernels.
+COST_F24B_DEFAULT = 'all'
+COST_F24B_PARTS = {'all': (1, 3), 'l1': (1,), 'l3': (3,), 'off': ()}
+
+
+def cost_f24b_parts(f24, f24b):
+    if f24b is None:
+        f24b = COST_F24B_DEFAULT if f24 is None else 'off'
+    if f24b is True:
+        f24b = 'all'
+    if f24b is False:
+        f24b = 'off'
+    if f24b not in COST_F24B_PARTS:
+        raise ValueError(f"f24b = {f24b!r}: one of 'all', 'l1', 'l3', 'off'")
+    return COST_F24B_PARTS[f24b]
+
+
+def cost_f24b_filters(layers, parts):
+    """The two extra filter sets of k_cost_net_w24b (None where the layer keeps its form): winograd_f24_tile_weights of layer 1's collapsed
+    filter [64][96 = (dk, c)][dn][dl] and of layer 3's (3,1,3) filter as [128][64][3][3]."""
+    sets = []
+    for l in (1, 3):
+        if l not in parts:
+            sets.append(None)
+            continue
+        w = layers[l][0]
+        if l == 1:
+            assert tuple(w.shape) == (64, 32, 3, 3, 3), w.shape
+            w2d = np.ascontiguousarray(np.transpose(w, (0, 3, 1, 2, 4)).reshape(64, 96, 3, 3))
+        else:
+            assert tuple(w.shape[2:]) == (3, 1, 3), w.shape
+            w2d = np.ascontiguousarray(w[:, :, :, 0, :])
+        sets.append(winograd_f24_tile_weights(w2d))
+    return sets
+
+
 class CostVolumeNet:
     """Device weights of CostNet re-laid for csrc/costnet.hip: layer 0 in its separated form (separate_cost_layer0: Ws then
     Wt in one buffer), layers 6..9 as Wt[((dn*KH+dk)*KW+dl)*Cin + c][Cout], MFMA-tiled; layers 1..5 as U = G g G^T in the
     Winograd tiling (winograd_tile_weights; groups per buf_cost_winograd_group; layer 1 with its three k planes as channels).
-    f24: the parts that run in k_cost_net_w24's forms (COST_F24_DEFAULT); their sets live in buffers of their own (self.wt24)."""
+    f24: the parts that run in k_cost_net_w24's forms (COST_F24_DEFAULT); their sets live in buffers of their own (self.wt24).
+    f24b: the parts that run in k_cost_net_w24b's forms (cost_f24b_parts); their sets: self.wt24b."""
 
-    def __init__(self, layers, device, f24=None):
+    def __init__(self, layers, device, f24=None, f24b=None):
         """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout])"""
         assert len(layers) == 10
         self.parts = cost_f24_parts(f24)
+        self.parts_b = cost_f24b_parts(f24, f24b)
         self.wt24 = [None if a is None else torch.from_numpy(a).to(device) for a in cost_f24_filters(layers, self.parts)]
         self._fp = (C.c_void_p * 3)(*[None if t is None else t.data_ptr() for t in self.wt24])
+        self.wt24b = [None if a is None else torch.from_numpy(a).to(device) for a in cost_f24b_filters(layers, self.parts_b)]
+        self._fpb = (C.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in self.wt24 + self.wt24b])      # k_cost_net_w24b's five
         self.wt, self.bias = [], []
         for i, (w, b) in enumerate(layers):
             cout, cin = w.shape[0], w.shape[1]
@@ -1345,6 +1388,10 @@ class CostVolumeNet:
         s_eq, t_eq = s_eq.contiguous(), t_eq.contiguous()
         m = s_eq.shape[0]
         out = torch.empty((m,), dtype=torch.float32, device=s_eq.device)
+        if self.parts_b:
+            check(L.buf_cost_volume_net_w24b(_ptr(s_eq), _ptr(t_eq), m, self._wp, self._bp, self._fpb, _ptr(out), _stream()),
+                  "buf_cost_volume_net_w24b")
+            return out
         if self.parts:
             check(L.buf_cost_volume_net_w24(_ptr(s_eq), _ptr(t_eq), m, self._wp, self._bp, self._fp, _ptr(out), _stream()),
                   "buf_cost_volume_net_w24")
@@ -1363,6 +1410,10 @@ class CostVolumeNet:
         s_rows, t_rows = _dev(s_rows, torch.int64, "s_rows"), _dev(t_rows, torch.int64, "t_rows")
         m = int(s_rows.shape[0])
         out = torch.empty((m,), dtype=torch.float32, device=equi.device)
+        if self.parts_b:
+            check(L.buf_cost_volume_net_w24b_gather(_ptr(equi), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self._fpb, _ptr(out),
+                                                    _stream()), "buf_cost_volume_net_w24b_gather")
+            return out
         if self.parts:
             check(L.buf_cost_volume_net_w24_gather(_ptr(equi), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self._fp, _ptr(out),
                                                    _stream()), "buf_cost_volume_net_w24_gather")
@@ -1376,10 +1427,11 @@ class CostVolumeNetSplit:
     """CostNet on the f16 matrix pipe with fp32-equivalent arithmetic (csrc/costnet_h3.hip): opt-in next to CostVolumeNet, same calls.
     Layer 0 in its separated form (separate_cost_layer0), layer 1 with its three k' planes as channels, every layer direct form."""
 
-    def __init__(self, layers, device, f24=None):
-        """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout]); f24: the fp32 re-run's kernel, as in CostVolumeNet"""
+    def __init__(self, layers, device, f24=None, f24b=None):
+        """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout]); f24, f24b: the fp32 re-run's kernel, as in CostVolumeNet"""
         assert len(layers) == 10
         self.parts = cost_f24_parts(f24)
+        self.parts_b = cost_f24b_parts(f24, f24b)
         mats = []
         w0 = layers[0][0]
         assert tuple(w0.shape) == (32, 32, 3, 3, 3), w0.shape
@@ -1408,13 +1460,18 @@ class CostVolumeNetSplit:
         self._bp = (C.c_void_p * 10)(*[t.data_ptr() for t in self.bias])
         # safe by construction (csrc/split_safe.hip): the fp32 kernel's weights ride along and re-run the matches the split kernel flags
         self.safe = not os.environ.get('BUF_SPLIT_UNSAFE')
-        self.f32 = CostVolumeNet(layers, device, f24=f24) if self.safe else None
+        self.f32 = CostVolumeNet(layers, device, f24=f24, f24b=f24b) if self.safe else None
         self.last_flags = None
 
     def _safe(self, s_eq, t_eq, s_rows, t_rows, m, dev):
         L = _lib.lib()
         out = torch.empty((m,), dtype=torch.float32, device=dev)
         self.last_flags = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
+        if self.parts_b:
+            check(L.buf_cost_volume_net_split_safe_w24b(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp,
+                                                        self.f32._bp, self.f32._fpb, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()),
+                  "buf_cost_volume_net_split_safe_w24b")
+            return out
         if self.parts:
             check(L.buf_cost_volume_net_split_safe_w24(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp,
                                                        self.f32._bp, self.f32._fp, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()),

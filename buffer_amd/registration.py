@@ -11,7 +11,7 @@ class CostVolume:
     (csrc/costnet.hip).  The kernel is written for the released geometry (32 channels, 5 elevation rows,
     azi_n = 20); anything else raises -- there is no library-convolution path in the product."""
 
-    def __init__(self, W, device, azi_n=20, arith='f32', f24=None):
+    def __init__(self, W, device, azi_n=20, arith='f32', f24=None, f24b=None):
         if arith not in ('f32', 'split'):
             raise ValueError(f"cnn_arith must be 'f32' or 'split', got {arith!r}")
         if azi_n != 20:
@@ -25,7 +25,10 @@ class CostVolume:
         # 'split': csrc/costnet_h3.hip -- the same network on the f16 matrix pipe, operands split hi + 2^-11 lo' (fp32-equivalent)
         # f24: the parts of the fp32 kernel (and of the split form's fp32 re-run) in k_cost_net_w24's forms: 'all' | 'l2' | 'l4' | 'l6' | 'off'
         # (None: ops.COST_F24_DEFAULT)
-        self.fused = ops.CostVolumeNetSplit(layers, device, f24=f24) if arith == 'split' else ops.CostVolumeNet(layers, device, f24=f24)
+        # f24b: the parts in k_cost_net_w24b's forms beside them: 'all' | 'l1' | 'l3' | 'off' (None: ops.COST_F24B_DEFAULT when f24 is left
+        # alone too, 'off' beside an explicit f24)
+        cls = ops.CostVolumeNetSplit if arith == 'split' else ops.CostVolumeNet
+        self.fused = cls(layers, device, f24=f24, f24b=f24b)
 
     def __call__(self, d1, d2):
         """d1,d2 f32[M,32,5,20] -> expected azimuth shift f32[M]."""

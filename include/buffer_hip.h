@@ -440,6 +440,15 @@ int     buf_cost_volume_net_w24(const float* s_eq, const float* t_eq, int m, con
 int     buf_cost_volume_net_w24_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
                                        const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
                                        float* ind_out, void* stream);
+/* The twins through k_cost_net_w24b (csrc/costnet_w24b.hip): beside the forms above, layer 1 on F(2x4) tiles (one k' plane resident at a
+ * time) and layer 3 as F(2x4) rows with an F(2x2) tail.  f24_host: HOST array of 5 DEVICE pointers, each nullable -- [0..2] as above,
+ * [3]: buf_winograd_f24_tile_weights of layer 1's collapsed filter [64][96 = (dk, c)][dn][dl], [4]: the same of layer 3's [128][64][3][3].
+ * A layer without a set runs as in buf_cost_volume_net_w24.  The timed span is BUF_TIMED_COST_NET with the same work figure. */
+int     buf_cost_volume_net_w24b(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
+                                 const float* const* f24_host, float* ind_out, void* stream);
+int     buf_cost_volume_net_w24b_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
+                                        const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
+                                        float* ind_out, void* stream);
 
 /* A13, split-f16 form -- the same network with fp32-EQUIVALENT arithmetic on the f16 matrix pipe (csrc/costnet_h3.hip; opt-in, see
  * buf_cylindrical_net_split for the operand split): layer 0 separated as above, every layer a direct-form correlation.
@@ -469,9 +478,14 @@ int     buf_cost_volume_net_split_safe_w24(const float* s_eq, const float* t_eq,
                                            int m, const void* const* wt_split_host, const float* const* bias_split_host,
                                            const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,
                                            float* ind_out, int* status_dev, int* flags_ws, void* stream);
+/* ... and through k_cost_net_w24b_rerun: f24_host[5] as for buf_cost_volume_net_w24b. */
+int     buf_cost_volume_net_split_safe_w24b(const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows, const long long* t_rows,
+                                            int m, const void* const* wt_split_host, const float* const* bias_split_host,
+                                            const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,
+                                            float* ind_out, int* status_dev, int* flags_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * A14  hypotheses + all-vs-all scoring (models/BUFFER.py:295-311): ind f32[m] -> R f32[m,3,3], t f32[m,3],
+ * A14 hypotheses + all-vs-all scoring (models/BUFFER.py:295-311): ind f32[m] -> R f32[m,3,3], t f32[m,3],
  * inlier_num int32[m], best_out int32[1] (first arg-max), best_mask uint8[m]. */
 int     buf_hypotheses_score(const float* ind, const float* ss_kpts, const float* tt_kpts, const float* ss_R,
                              const float* tt_R, int m, int azi_n, float inlier_th, float* R_out, float* t_out,

@@ -77,6 +77,7 @@ units = {
     'k_select_patches_grid': (patches, 'patch', 12 * 512 + 12),
     'k_cost_net': (matches, 'match', 2 * 3200 * 4 + 4),
     'k_cost_net_w24': (matches, 'match', 2 * 3200 * 4 + 4),
+    'k_cost_net_w24b': (matches, 'match', 2 * 3200 * 4 + 4),
     'k_cyl_net_h3': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
     'k_cost_net_h3': (matches, 'match', 2 * 3200 * 4 + 4),
     'k_grid_query': (pairs, 'pair (mean over the 7 query shapes: 3 cell-centric self queries, 4 query-centric)', None),
@@ -95,8 +96,9 @@ for k, (u, unit, alg) in units.items():
                       launches_profiled=n_f[k], launches_dropped=dropped.get(k, 0), units_per_launch=u, unit=unit, hbm_bytes_per_unit=hbm / u,
                       algorithmic_bytes_per_unit=alg)
 # bench.py looks the cost net up as k_cost_net: when the profiled run went through k_cost_net_w24, its bytes are recorded under both names
-if 'k_cost_net' not in kernels and 'k_cost_net_w24' in kernels:
-    kernels['k_cost_net'] = dict(kernels['k_cost_net_w24'], measured_on='k_cost_net_w24')
+for twin in ('k_cost_net_w24b', 'k_cost_net_w24'):
+    if 'k_cost_net' not in kernels and twin in kernels:
+        kernels['k_cost_net'] = dict(kernels[twin], measured_on=twin)
 json.dump(dict(source='rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on the bench.py command of '
                       'the line in `bench`; per-dispatch means over the full-step launches',
                correction='gfx950: FETCH_SIZE tallies 128-B requests at 64 B -> doubled (MI355X_MICROARCH.md, HBM); WRITE_SIZE as is; '
