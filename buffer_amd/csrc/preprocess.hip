@@ -414,6 +414,7 @@ extern "C" int buf_knn_normals(const float* pts, int ns, const int* qidx, int nq
     BUF_REQUIRE(ncand >= 1 && ncand <= NRM_MAXC && knn <= ncand, BUF_EINVAL, "buf_knn_normals: ncand=%d (1..%d, >= knn=%d)", ncand, NRM_MAXC, knn);
     if (nq == 0) return BUF_OK;
     BUF_REQUIRE(pts && cand && normals && deficient && (!orient || camera_host), BUF_EINVAL, "buf_knn_normals: null argument");
+    BUF_REQUIRE(qidx || nq <= ns, BUF_EINVAL, "buf_knn_normals: nq=%d > ns=%d without qidx (row = point)", nq, ns);
     double cx = orient ? camera_host[0] : 0.0, cy = orient ? camera_host[1] : 0.0, cz = orient ? camera_host[2] : 0.0;
     k_knn_normals<<<cdiv(nq, 64), 64, 0, (hipStream_t)stream>>>(pts, ns, qidx, nq, cand, ncand, knn, cx, cy, cz, orient, normals, deficient);
     BUF_LAUNCH_CHECK();

@@ -530,7 +530,7 @@ int     buf_recover_poses_batched(const float* ind, const float* ss_kpts, const 
  * buf_knn_normals = estimate_normals(KDTreeSearchParamKNN(knn)) + orient_normals_towards_camera_location on the
  * candidate lists of a radius search: cand int32[nq,ncand] = buf_grid_query output (sorted by distance, >= ns = empty),
  * knn <= ncand <= 48.  The knn nearest are re-ranked in fp64; covariance by cumulants, normal = eigenvector of the
- * smallest eigenvalue (open3d FastEigen3x3).  qidx (nullable) maps row -> point (for retries on a subset);
+ * smallest eigenvalue (open3d FastEigen3x3).  qidx (nullable) maps row -> point (for retries on a subset; null: row = point, nq <= ns);
  * deficient[row] = 1 when the row holds fewer than min(knn, ns) points (its search ball was too small: retry with a
  * larger radius), else the normal of point qidx[row] is written.  camera_host: HOST double[3]. */
 size_t  buf_voxel_downsample_ws_bytes(int n, int64_t max_cells);

@@ -4,6 +4,8 @@ UNPINNED (open3d 0.13.0 is a pip dependency absent from /root/reference and from
 import numpy as np
 import pytest
 
+from preprocess_ref import voxel_means as _np_voxel_down_sample
+
 
 def _cloud(seed, n, scale=1.0):
     rng = np.random.default_rng(seed)
@@ -13,22 +15,6 @@ def _cloud(seed, n, scale=1.0):
     p[np.arange(n), face] = 0.0
     p += rng.normal(0, 0.003, p.shape)
     return ((p + 0.5) * scale).astype(np.float32)
-
-
-def _np_voxel_down_sample(pts, voxel):
-    pts = np.asarray(pts, np.float64)
-    o = pts.min(0) - voxel * 0.5
-    idx = np.floor((pts - o) / voxel).astype(np.int64)
-    N = np.floor((pts.max(0) - o) / voxel).astype(np.int64) + 1
-    key = idx[:, 0] + N[0] * idx[:, 1] + N[0] * N[1] * idx[:, 2]
-    rows = []
-    for k in np.unique(key):
-        sel = np.nonzero(key == k)[0]
-        s = np.zeros(3)
-        for i in sel:                      # input order, sequential fp64 sum
-            s = s + pts[i]
-        rows.append(s / len(sel))
-    return np.array(rows)
 
 
 def test_oracle_voxel_down_sample_vs_numpy(oracle):
