@@ -92,6 +92,10 @@ _SIGNATURES = {
     "buf_cylindrical_net_wg_form": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "buf_cylindrical_net_wg_all": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "buf_cylindrical_net_wg_all_flags": (_i, [_vp, _vp, _vp, _vp]),
+    "buf_cylindrical_net_w25": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "buf_cylindrical_net_w25_flags": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "buf_cylindrical_net_split_safe_w25": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "buf_winograd_f25_tile_weights": (_i, [_vp, _i, _i, _vp]),
     "buf_cylindrical_net_wg_supports": (_i, [_vp, _vp]),
     "buf_cylindrical_net_wg_flags": (_i, [_vp, _vp, _vp]),
     "buf_cylindrical_net_split_safe": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

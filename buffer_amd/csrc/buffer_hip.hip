@@ -27,6 +27,7 @@
 #include "convnet_w24k.hip"
 #include "convnet_w24p.hip"
 #include "convnet_w24a.hip"
+#include "convnet_w25.hip"
 #include "costnet.hip"
 #include "costnet_w24.hip"
 #include "costnet_w24b.hip"

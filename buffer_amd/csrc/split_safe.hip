@@ -85,6 +85,36 @@ extern "C" int buf_cylindrical_net_split_safe_all(const float* x, int npatch, co
     return BUF_OK;
 }
 
+// The same through k_cyl_net_w25 (csrc/convnet_w25.hip): wt24_host and wt25_host as for buf_cylindrical_net_w25, the re-run is
+// k_cyl_net_w25_rerun.  Everything is checked before the first device call.
+extern "C" int buf_cylindrical_net_split_safe_w25(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                                  const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                                  const float* const* wt24_host, const float* const* wt25_host, const float* head_params,
+                                                  float* y_or_equi, float* desc, int* status_dev, int* flags_ws, void* stream)
+{
+    BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "buf_cylindrical_net_split_safe_w25: npatch=%d", npatch);
+    if (npatch == 0) return BUF_OK;
+    BUF_REQUIRE(x && y_or_equi && flags_ws && wt_split_host, BUF_EINVAL, "buf_cylindrical_net_split_safe_w25: null argument");
+    BUF_REQUIRE(!head_params || desc, BUF_EINVAL, "buf_cylindrical_net_split_safe_w25: head without desc");
+    CylWgParams P;
+    if (int rc = w25_prepare(wt_wg_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, P)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    BUF_CHECK_HIP(hipMemsetAsync(flags_ws, 0, sizeof(int) * (size_t)npatch, s));
+    int relu_split[WG_LAYERS];                        // the split kernel knows 0 / 1 only
+    for (int l = 0; l < WG_LAYERS; l++) relu_split[l] = relu_host[l] & 1;
+    int rc = h3_launch(x, npatch, wt_split_host, bias_host, cin_host, cout_host, relu_split, head_params ? nullptr : y_or_equi, head_params,
+                       desc, head_params ? y_or_equi : nullptr, status_dev, stream, flags_ws);
+    if (rc) return rc;
+    P.only_if = flags_ws;
+    rc = w25_launch(x, npatch, P, y_or_equi, stream);
+    if (rc) return rc;
+    if (head_params) {
+        k_desc_head_masked<<<npatch, DH_THREADS, 0, s>>>(y_or_equi, head_params, desc, y_or_equi, flags_ws);
+        BUF_LAUNCH_CHECK();
+    }
+    return BUF_OK;
+}
+
 // The cost net likewise: dense inputs (s_rows == null: s_eq, t_eq f32[m,32,5,20]) or the gathered form (s_eq = t_eq = equi
 // f32[rows,32,ele_n,20] with ele_n = 7 and int64 row ids).  wt_split_host: 11 planes (buf_split_tile_gemm), wt_f32_host: the 10 matrices of
 // buf_cost_volume_net; the two bias sets as for those entry points.  flags_ws: DEVICE int32[m].

@@ -1006,6 +1006,52 @@ def winograd_f24_filters(w):
     return U
 
 
+# F(2x5, 3x3): F(2,3) down the rows as above, F(5,3) along the azimuth on the seven points 0, +-1, +-2, +-1/2 (no point at infinity: the
+# product polynomial has degree 6).  Column component j belongs to point F25_POINTS[j]; B5^T row j holds the coefficients of
+# L_j(x) = prod_{k != j} (x - p_k), G5 row j the powers of p_j over L_j(p_j), A5^T row i the i-th powers of the points.
+F25_POINTS = (0.0, 1.0, -1.0, 2.0, -2.0, 0.5, -0.5)
+
+
+def _f25_matrices():
+    pts = np.array(F25_POINTS, np.float64)
+    bt = np.zeros((7, 7))
+    g = np.zeros((7, 3))
+    for j, p in enumerate(pts):
+        lj = np.poly(np.delete(pts, j))[::-1]                                        # ascending powers, monic
+        bt[j] = lj
+        nj = np.prod(p - np.delete(pts, j))                                          # L_j(p_j), exact in float64
+        g[j] = [1 / nj, p / nj, p * p / nj]
+    at = pts[None, :] ** np.arange(5)[:, None]
+    return np.round(bt * 16) / 16, g, at                                             # (the coefficients of L_j are multiples of 1/16)
+
+
+F25_B5T, F25_G5, F25_A5T = _f25_matrices()
+
+
+def winograd_f25_filters(w):
+    """[Cout, Cin, 3, 3] -> U = G2 g G5^T in float64, [4, 7, Cout, Cin]"""
+    w64 = np.asarray(w, np.float64)
+    U = np.zeros((4, 7) + w64.shape[:2], np.float64)
+    for a in range(3):
+        for b in range(3):
+            U += (F24_G2[:, a][:, None, None, None] * w64[None, None, :, :, a, b]) * F25_G5[:, b][None, :, None, None]
+    return U
+
+
+def winograd_f25_tile_weights(w):
+    """[Cout, Cin, 3, 3] -> the F(2x5, 3x3) filter transform U = G2 g G5^T (fp64, rounded once to fp32) in the tiling of
+    csrc/convnet_w25.hip: [i][k-step][N-tile][448] with, per (row component i, k-step, N-tile), the column components j = 0..3 as
+    [lk][li][4], then j = 4, 5 as [lk][li][2], then j = 6 as [lk][li]; value U[i][j][16 n + li][4 ks + lk].  28 * Cout * Cin floats
+    (buf_winograd_f25_tile_weights is the same function on the C side)."""
+    cout, cin = w.shape[0], w.shape[1]
+    assert cin % 4 == 0 and cout % 16 == 0
+    U = winograd_f25_filters(w).reshape(4, 7, cout // 16, 16, cin // 4, 4)           # [i, j, n, li, ks, lk]
+    U = np.transpose(U, (0, 4, 2, 5, 3, 1))                                          # [i, ks, n, lk, li, j]
+    lead = U.shape[:3]
+    parts = [U[..., 0:4].reshape(*lead, 256), U[..., 4:6].reshape(*lead, 128), U[..., 6:7].reshape(*lead, 64)]
+    return np.ascontiguousarray(np.concatenate(parts, axis=-1), dtype=np.float32).reshape(-1)
+
+
 F24_FLAG = 2          # relu_host[l] bit 1 of buf_cylindrical_net_wg: the layer's buffer holds the F(2x4) set behind the F(2x2) set
 F24K_FLAG = 4         # bit 2: the same for a layer with 64 output channels and Cin % 64 == 0 (k_cyl_net_w24k / k_cyl_net_w24p)
 F24P_DEFAULT = True   # the form of the bit-2 layers: pass split (k_cyl_net_w24p) | K split (k_cyl_net_w24k); profiles/f24p_ab.md
@@ -1014,6 +1060,41 @@ F24P_DEFAULT = True   # the form of the bit-2 layers: pass split (k_cyl_net_w24p
 # 32-output layers; 'off' or None: k_cyl_net_w24p as it is.  The argument f24a= of the two classes picks one per net.
 F24A_DEFAULT = 'all'
 F24A_PARTS = {'all': (64, 32), 'out64': (64,), 'out32': (32,), 'off': (), None: ()}
+
+
+# F(2x5) tiles (k_cyl_net_w25, csrc/convnet_w25.hip; profiles/f25_ab.md): the layers of these output widths run on an F(2x5) set of their
+# own -- 'all': the 64- and the 32-output layers, 'out64' / 'out32': one of the two, 'off' or None: k_cyl_net_w24a as it is, bit for bit.
+# The 128-output form ('out128') is not built.  The argument f25= of the two classes picks one per net.  The default is the part that met
+# both rules of the A/B (profiles/f25_ab.md): the 64-output layers; the 32-output form measured slower than its F(2x4) twin and stays off.
+F25_DEFAULT = 'out64'
+F25_PARTS = {'all': (64, 32), 'out64': (64,), 'out32': (32,), 'off': (), None: ()}
+
+
+def cyl_f25_parts(f24, f24k, f24p, f25):
+    """The output widths whose layers get an F(2x5) set (k_cyl_net_w25).  An explicit f24 / f24k / f24p asks for one of the older
+    kernels: no such layers then, and asking for both is an error."""
+    explicit = not (f24 is None and f24k is None and f24p is None)
+    if f25 is None:
+        f25 = None if explicit else F25_DEFAULT
+    if f25 is True:
+        f25 = 'all'
+    if f25 is False:
+        f25 = 'off'
+    if f25 == 'out128':
+        raise ValueError("f25 = 'out128': the 128-output layers have no F(2x5) form (csrc/convnet_w25.hip)")
+    if f25 not in F25_PARTS:
+        raise ValueError(f"f25 = {f25!r}: one of 'all', 'out64', 'out32', 'off'")
+    if F25_PARTS[f25] and explicit and not (f24 in (None, True) and f24k in (None, True) and f24p in (None, True)):
+        raise ValueError("f25 goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
+    return F25_PARTS[f25]
+
+
+def cyl_f25_filters(layers, parts, device):
+    """Per layer the F(2x5) set in a buffer of its own (a tensor on `device`) where the layer has one of the output widths `parts` and
+    Cin % 16 == 0, else None; and the pointer array buf_cylindrical_net_w25 takes."""
+    sets = [torch.from_numpy(winograd_f25_tile_weights(w)).to(device)
+            if (w.shape[0] in parts and w.shape[0] in (32, 64) and w.shape[1] % 16 == 0) else None for w, _, _ in layers]
+    return sets, (C.c_void_p * len(sets))(*[None if t is None else t.data_ptr() for t in sets])
 
 
 def cyl_layer_filters(w, f24k=True):
@@ -1063,12 +1144,15 @@ class CylindricalNet:
     csrc/convnet_w24a.hip: per layer U = G g G^T in the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu
     word; for k_cyl_net_w24a the remaining layers' F(2x4) sets in buffers of their own, `wt24`), biases."""
 
-    def __init__(self, layers, device, f24=None, f24k=None, f24p=None, f24a=None):
+    def __init__(self, layers, device, f24=None, f24k=None, f24p=None, f24a=None, f25=None):
         """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  No form argument: k_cyl_net_w24a with F(2x4)
         tiles in every layer (F24A_DEFAULT; f24a = 'all' | 'out64' | 'out32' | 'off' picks the parts).  An explicit f24, f24k or f24p gives
         one of the older kernels with the defaults f24 = f24k = True, f24p = F24P_DEFAULT: f24 = False: the F(2x2) form in every
         layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B); f24k = False: F(2x4) in the 128-output layers
-        only (k_cyl_net_w24); f24p: the flagged 64-output layers in the pass-split form (k_cyl_net_w24p), else K split (k_cyl_net_w24k)."""
+        only (k_cyl_net_w24); f24p: the flagged 64-output layers in the pass-split form (k_cyl_net_w24p), else K split (k_cyl_net_w24k).
+        f25 = 'all' | 'out64' | 'out32' | 'off' (F25_DEFAULT): F(2x5) tiles in the layers of those output widths (k_cyl_net_w25); the
+        other layers as the remaining arguments say."""
+        parts25 = cyl_f25_parts(f24, f24k, f24p, f25)
         f24, f24k, f24p, parts = cyl_f24a_parts(f24, f24k, f24p, f24a)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_wg"
@@ -1091,6 +1175,9 @@ class CylindricalNet:
         self.wt24, self._w24p = cyl_f24a_filters(layers, flags, parts, device)
         self.f24_layers = [l for l, t in enumerate(self.wt24) if t is not None]
         self.f24_all = bool(self.f24_layers) and all(f or t is not None for f, t in zip(flags, self.wt24))
+        # the layers k_cyl_net_w25 runs on an F(2x5) set (it wins over the layer's F(2x4) flag or set)
+        self.wt25, self._w25p = cyl_f25_filters(layers, parts25, device)
+        self.f25_layers = [l for l, t in enumerate(self.wt25) if t is not None]
 
     def __call__(self, x):
         """x f32[P,16,420] (or [P,48,140]) -> f32[P,32,7,20]"""
@@ -1098,6 +1185,10 @@ class CylindricalNet:
         x = x.contiguous()
         P = x.shape[0]
         y = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
+        if self.f25_layers:
+            check(L.buf_cylindrical_net_w25(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self._w24p, self._w25p, _ptr(y), _stream()),
+                  "buf_cylindrical_net_w25")
+            return y
         if self.f24_layers:
             check(L.buf_cylindrical_net_wg_all(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self._w24p, _ptr(y), _stream()),
                   "buf_cylindrical_net_wg_all")
@@ -1127,12 +1218,14 @@ class CylindricalNetSplit:
     kernel.  For widths the fp32 kernel is not built for (the released network's are) the old contract stays: `check_range()` raises if
     the status word was set."""
 
-    def __init__(self, layers, device, f24k=None, f24p=None, f24a=None):
-        """f24k, f24p, f24a: the fp32 re-run's kernel, as in CylindricalNet (no form argument: k_cyl_net_w24a_rerun)"""
+    def __init__(self, layers, device, f24k=None, f24p=None, f24a=None, f25=None):
+        """f24k, f24p, f24a, f25: the fp32 re-run's kernel, as in CylindricalNet (no form argument: k_cyl_net_w24a_rerun, or
+        k_cyl_net_w25_rerun where F25_DEFAULT names layers)"""
+        parts25 = cyl_f25_parts(None, f24k, f24p, f25)
         _, f24k, f24p, parts = cyl_f24a_parts(None, f24k, f24p, f24a)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_split"
-        self.f24_layers, self.f24_all = [], False
+        self.f24_layers, self.f24_all, self.f25_layers = [], False, []
         self.form = 1 if f24p else 0                     # of the fp32 re-run, as in CylindricalNet
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
@@ -1157,6 +1250,8 @@ class CylindricalNetSplit:
             self.wt24, self._w24p = cyl_f24a_filters(layers, [f for _, f in tiled], parts, device)
             self.f24_layers = [l for l, t in enumerate(self.wt24) if t is not None]
             self.f24_all = bool(self.f24_layers) and all(f or t is not None for (_, f), t in zip(tiled, self.wt24))
+            self.wt25, self._w25p = cyl_f25_filters(layers, parts25, device)
+            self.f25_layers = [l for l, t in enumerate(self.wt25) if t is not None]
 
     def _safe_call(self, x, head):
         L = _lib.lib()
@@ -1165,6 +1260,11 @@ class CylindricalNetSplit:
         out = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
         desc = torch.empty((P, 32), dtype=torch.float32, device=x.device) if head is not None else None
         self.last_flags = torch.empty((max(P, 1),), dtype=torch.int32, device=x.device)
+        if self.f25_layers:
+            check(L.buf_cylindrical_net_split_safe_w25(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self._w24p,
+                                                       self._w25p, _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc),
+                                                       _ptr(self.status), _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe_w25")
+            return (desc, out) if head is not None else out
         if self.f24_layers:
             check(L.buf_cylindrical_net_split_safe_all(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self._w24p,
                                                        _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),

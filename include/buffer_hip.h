@@ -354,6 +354,21 @@ int     buf_cylindrical_net_wg_all_flags(const int* cin_host, const int* cout_ho
 int     buf_cylindrical_net_wg_all(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                    const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
                                    float* y, void* stream);
+/* F(2x5, 3x3) tiles (csrc/convnet_w25.hip, kernel k_cyl_net_w25): tiles of 2 rows x 5 azimuth columns carry the 7 x 20 map with 4 x 4
+ * regular tiles, 28 matrix instructions per 4 input x 16 output channels and no direct round of row 6 (F(2x4): 24 + 6).
+ * buf_cylindrical_net_wg_all with one more array, wt25_host[8]: per layer null, or the 28*Cout*Cin floats of
+ * buf_winograd_f25_tile_weights -- U = G2 g G5^T (4 row x 7 column components; points 0, +-1, +-2, +-1/2; fp64 on the host) tiled
+ * [i][k-step][N-tile][448] with, per (row component, k-step, N-tile), the column components j = 0..3 as [lk][li][4], j = 4, 5 as
+ * [lk][li][2] and j = 6 as [lk][li] -- in a buffer of their own.  Allowed on a layer with 64 or 32 output channels and Cin a multiple of
+ * 16, whatever F(2x4) bit its relu word or entry of wt24_host it carries (the F(2x5) set wins); else BUF_EINVAL.  A layer without
+ * one runs as in buf_cylindrical_net_wg_all, and with no F(2x5) set at all the result is that entry point's, bit for bit.  A 32-output
+ * layer with an F(2x5) set counts as one with a set in the widths rule above.  buf_cylindrical_net_w25_flags: host only. */
+int     buf_winograd_f25_tile_weights(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 28*Cout*Cin floats; Cout a multiple of 16 */
+int     buf_cylindrical_net_w25_flags(const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
+                                      const float* const* wt25_host);
+int     buf_cylindrical_net_w25(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
+                                const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
+                                const float* const* wt25_host, float* y, void* stream);
 
 /* A11 (dense), split-f16 form -- the same stack with fp32-EQUIVALENT arithmetic on the f16 matrix pipe (csrc/convnet_h3.hip; opt-in,
  * the all-fp32 kernel above stays the default): every fp32 operand is split once into hi = f16(x) and lo' = f16((x - hi) 2^11)
@@ -402,6 +417,11 @@ int     buf_cylindrical_net_split_safe_all(const float* x, int npatch, const voi
                                            const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                            const float* const* wt24_host, const float* head_params, float* y_or_equi, float* desc,
                                            int* status_dev, int* flags_ws, void* stream);
+/* The same with the fp32 re-run through k_cyl_net_w25_rerun: wt24_host and wt25_host as for buf_cylindrical_net_w25 */
+int     buf_cylindrical_net_split_safe_w25(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                           const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                           const float* const* wt24_host, const float* const* wt25_host, const float* head_params,
+                                           float* y_or_equi, float* desc, int* status_dev, int* flags_ws, void* stream);
 
 /* A11 (head)  attention pooling + normalisation (models/patch_embedder.py:66-72,81-84): pool_layer
  * (Conv2d 1x1 32->16 + BN + ReLU, Conv2d 1x1 16->1 + BN + ReLU), desc = normalize(mean(y * w)),
