@@ -31,6 +31,7 @@
 #include "costnet.hip"
 #include "costnet_w24.hip"
 #include "costnet_w24b.hip"
+#include "cnn_launch.hip"             // the host side of the nine kernels above: behind all of them
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "fgr.hip"

@@ -9,7 +9,7 @@
 // Winograd M-tile would leave their wavefronts one N-tile each.
 //
 // Opt-in: bit 1 of relu_host[l] (WG_F24_FLAG) says that layer l's filter buffer holds the F(2x4) set (buf_winograd_f24_tile_weights,
-// 24 Cout Cin floats) BEHIND the F(2x2) set; wg_launch comes here if any layer carries it.  Every layer of 128 output channels must
+// 24 Cout Cin floats) BEHIND the F(2x2) set; the stack runs here if any layer carries it (cyl_kernel_for, csrc/cnn_launch.hip).  Every layer of 128 output channels must
 // carry it then, and no other layer may.
 //
 // The pair form: wavefront w owns the N-tile pair 2w, 2w+1 over the whole K.  Four passes over the row components; per k-step a pass
@@ -455,63 +455,5 @@ extern "C" int buf_winograd_f24_tile_weights(const float* w_host, int cout, int 
                 }
             }
         }
-    return BUF_OK;
-}
-
-// The flag rules of a stack that carries bit 1 or bit 2 somewhere, stated once (widths already checked): what w24_launch enforces before
-// its first device call and buf_cylindrical_net_wg_flags reports.
-static int w24_check_flags(const int* cin, const int* cout, const int* relu)
-{
-    for (int l = 0; l < WG_LAYERS; l++) {
-        BUF_REQUIRE(relu[l] >= 0 && relu[l] <= (BUF_CYL_F24K | WG_F24_FLAG | 1), BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has the relu word %d (bit 0: ReLU, bits 1 and 2: the F(2x4) flags, nothing above)", l, relu[l]);
-        BUF_REQUIRE(!(relu[l] & BUF_CYL_F24K) || (cout[l] == 64 && cin[l] % 64 == 0), BUF_EINVAL,
-                    "buf_cylindrical_net_wg: the K-split F(2x4) flag (bit 2) goes only on layers with 64 output channels and Cin %% 64 == 0 "
-                    "(layer %d: %d -> %d, flags %d)", l, cin[l], cout[l], relu[l]);
-        BUF_REQUIRE(((relu[l] & WG_F24_FLAG) != 0) == (cout[l] == 128), BUF_EINVAL,
-                    "buf_cylindrical_net_wg: the F(2x4) flag goes on every layer with 128 output channels and on no other (layer %d: %d -> %d, flags %d)",
-                    l, cin[l], cout[l], relu[l]);
-    }
-    return BUF_OK;
-}
-
-// 0 when buf_cylindrical_net_wg would accept these widths with these relu words (host only, no device call), else BUF_EINVAL with the reason
-extern "C" int buf_cylindrical_net_wg_flags(const int* cin_host, const int* cout_host, const int* relu_host)
-{
-    BUF_REQUIRE(cin_host && cout_host && relu_host, BUF_EINVAL, "buf_cylindrical_net_wg_flags: null argument");
-    if (int rc = wg_check_widths(cin_host, cout_host)) return rc;
-    for (int l = 0; l < WG_LAYERS; l++)
-        if (relu_host[l] >= 2) return w24_check_flags(cin_host, cout_host, relu_host);
-    return BUF_OK;
-}
-
-// The F(2x4) launch behind wg_launch: P as wg_launch filled it (widths checked, relu[] still with the flag bits).  Stacks that carry
-// bit 2 (BUF_CYL_F24K: the F(2x4) form of 64-output layers) go on to k_cyl_net_w24k (csrc/convnet_w24k.hip: K split) or
-// k_cyl_net_w24p (csrc/convnet_w24p.hip: pass split) as `form` says.
-#define BUF_CYL_FORM_LIBRARY BUF_CYL_FORM_PASS_SPLIT      // what BUF_CYL_FORM_DEFAULT means (profiles/f24p_ab.md)
-static int w24k_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
-static int w24p_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream);
-static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream, int form)
-{
-    if (int rc = w24_check_flags(P.cin, P.cout, P.relu)) return rc;
-    bool ksplit = false;
-    for (int l = 0; l < WG_LAYERS; l++) {
-        if (P.relu[l] & WG_F24_FLAG) P.wt[l] += W24_SET_F22(P.cin[l]);
-        ksplit |= (P.relu[l] & BUF_CYL_F24K) != 0;
-        P.relu[l] &= ~WG_F24_FLAG;
-    }
-    if (form == BUF_CYL_FORM_DEFAULT) form = BUF_CYL_FORM_LIBRARY;
-    if (ksplit) return form == BUF_CYL_FORM_PASS_SPLIT ? w24p_launch(x, npatch, P, y, stream) : w24k_launch(x, npatch, P, y, stream);
-    size_t lds = sizeof(float) * WG_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = P.only_if ? grant_dynamic_lds((const void*)k_cyl_net_w24_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_w24, lds, grant)) return rc;
-    double macs = 0;
-    for (int l = 0; l < WG_LAYERS; l++) macs += 9.0 * P.cin[l] * P.cout[l];
-    TimedSpan span;
-    bool timed = !P.only_if && timing_begin((hipStream_t)stream, &span, 2.0 * 140 * macs * npatch, BUF_TIMED_CYL_NET);   // (a masked re-run is not a full launch)
-    if (P.only_if) k_cyl_net_w24_rerun<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    else k_cyl_net_w24<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
     return BUF_OK;
 }

@@ -4,7 +4,7 @@
 // instructions per patch (k_cyl_net_w24p: 22 848).
 //
 // The layer forms, picked per layer from the widths and the kernel's relu word (bit 2 here means "P.wt[l] IS the layer's F(2x4) set";
-// the launcher sets it for the layers that carry BUF_CYL_F24K and for those with a set of their own, see w24a_prepare):
+// the launcher sets it for the layers that carry BUF_CYL_F24K and for those with a set of their own, see cyl_prepare, csrc/cnn_launch.hip):
 //   128 outputs                 w24_layer_pair (csrc/convnet_w24.hip), unchanged
 //   64 outputs, bit 2           w24p_layer_psplit (csrc/convnet_w24p.hip), unchanged: its k-loop runs Cin / 16 times, so Cin = 48 (layer 0:
 //                               three iterations), 32 and 16 (one iteration) go through it as 64 and 128 do
@@ -25,7 +25,7 @@
 // 36 quarter on: [f_w of N-tile 0: 16][f_w of N-tile 1: 16][row 6 of the upper K half: 4].  A finisher does not write what it keeps.
 // Words WG_ZERO..WG_ZERO + 3 and the two dump words of these channels are not touched, so -- unlike behind wg_layer_mksplit, whose
 // exchange runs over the zero words of the channels 64..95 -- a wider layer may follow, as long as no 32-output layer of the older form
-// has run earlier in the stack (w24a_prepare).
+// has run earlier in the stack (cyl_check, csrc/cnn_launch.hip).
 //
 // Barriers per layer, beside the one that closes every layer:
 //   1. behind the dump-word clear (the window rows in the elevation padding read six words from the zero area on: w24_layer_pair);
@@ -255,84 +255,4 @@ __global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24a_rerun(const floa
     extern __shared__ float lds[];
     if (P.only_if[blockIdx.x] == 0) return;
     cyl_net_w24a_body(x, P, y, lds);
-}
-
-// The rules of buf_cylindrical_net_wg_all for widths, relu words and the layers' own sets, stated once (host only).  wt24_host[l]
-// (nullable per layer): the layer's F(2x4) set (buf_winograd_f24_tile_weights) in a buffer of its own; allowed on a layer that carries
-// neither F(2x4) flag and has 64 or 32 output channels.  The relu words keep the rules of buf_cylindrical_net_wg.
-static int w24a_check(const int* cin, const int* cout, const int* relu, const float* const* wt24_host)
-{
-    if (int rc = wg_check_widths(cin, cout, false)) return rc;
-    if (int rc = w24_check_flags(cin, cout, relu)) return rc;
-    bool f22_ran = false;
-    int f22_layer = -1;
-    for (int l = 0; l < WG_LAYERS; l++) {
-        BUF_REQUIRE(!wt24_host[l] || (!(relu[l] & (WG_F24_FLAG | W24K_FLAG)) && (cout[l] == 64 || cout[l] == 32)), BUF_EINVAL,
-                    "buf_cylindrical_net_wg_all: layer %d (%d -> %d, flags %d) takes no F(2x4) set of its own (64 or 32 output channels, no F(2x4) flag)",
-                    l, cin[l], cout[l], relu[l]);
-        // wg_layer_mksplit hands its partial sums over through the zero words of the channels 64..95, which are written once per kernel
-        // (see wg_check_widths): once a 32-output layer WITHOUT a set has run, only 32-output layers may follow, to the end of the stack
-        BUF_REQUIRE(!f22_ran || cout[l] == 32, BUF_EINVAL,
-                    "buf_cylindrical_net_wg_all: layer %d has unsupported widths %d -> %d (once a 32-output layer in the F(2x2) form has run, layer %d here, "
-                    "only 32-output layers may follow)", l, cin[l], cout[l], f22_layer);
-        if (cout[l] == 32 && !wt24_host[l] && !f22_ran) { f22_ran = true; f22_layer = l; }
-    }
-    return BUF_OK;
-}
-
-// 0 when buf_cylindrical_net_wg_all would accept these widths, relu words and sets (host only, no device call; only whether an entry of
-// wt24_host is null is looked at), else BUF_EINVAL with the reason
-extern "C" int buf_cylindrical_net_wg_all_flags(const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host)
-{
-    BUF_REQUIRE(cin_host && cout_host && relu_host && wt24_host, BUF_EINVAL, "buf_cylindrical_net_wg_all_flags: null argument");
-    return w24a_check(cin_host, cout_host, relu_host, wt24_host);
-}
-
-// Everything buf_cylindrical_net_wg_all checks, and the kernel's parameters, without a device call
-static int w24a_prepare(const float* const* wt_host, const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
-                        const float* const* wt24_host, CylWgParams& P)
-{
-    BUF_REQUIRE(wt_host && bias_host && cin_host && cout_host && relu_host && wt24_host, BUF_EINVAL, "buf_cylindrical_net_wg_all: null argument");
-    for (int l = 0; l < WG_LAYERS; l++) {
-        P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
-        P.cin[l] = cin_host[l]; P.cout[l] = cout_host[l]; P.relu[l] = relu_host[l];
-        BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "buf_cylindrical_net_wg_all: null weights for layer %d", l);
-    }
-    if (int rc = w24a_check(P.cin, P.cout, P.relu, wt24_host)) return rc;
-    for (int l = 0; l < WG_LAYERS; l++) {
-        if (P.relu[l] & WG_F24_FLAG) P.wt[l] += W24_SET_F22(P.cin[l]);
-        else if (P.relu[l] & W24K_FLAG) P.wt[l] += WG_BLOCKS * P.cout[l] * P.cin[l];       // behind the layer's F(2x2) set
-        else if (wt24_host[l]) { P.wt[l] = wt24_host[l]; P.relu[l] |= W24K_FLAG; }
-        P.relu[l] &= ~WG_F24_FLAG;
-    }
-    P.only_if = nullptr;
-    return BUF_OK;
-}
-
-static int w24a_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream)
-{
-    size_t lds = sizeof(float) * WG_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = P.only_if ? grant_dynamic_lds((const void*)k_cyl_net_w24a_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_w24a, lds, grant)) return rc;
-    double macs = 0;
-    for (int l = 0; l < WG_LAYERS; l++) macs += 9.0 * P.cin[l] * P.cout[l];
-    TimedSpan span;
-    bool timed = !P.only_if && timing_begin((hipStream_t)stream, &span, 2.0 * 140 * macs * npatch, BUF_TIMED_CYL_NET);   // (a masked re-run is not a full launch)
-    if (P.only_if) k_cyl_net_w24a_rerun<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    else k_cyl_net_w24a<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-    return BUF_OK;
-}
-
-// x f32[np,Cin0,140] -> y f32[np,32,140] through k_cyl_net_w24a: buf_cylindrical_net_wg with, per layer, an optional F(2x4) set of its own
-extern "C" int buf_cylindrical_net_wg_all(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
-                                          const int* cout_host, const int* relu_host, const float* const* wt24_host, float* y, void* stream)
-{
-    BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "buf_cylindrical_net_wg_all: npatch=%d", npatch);
-    if (npatch == 0) return BUF_OK;
-    BUF_REQUIRE(x && y, BUF_EINVAL, "buf_cylindrical_net_wg_all: null argument");
-    CylWgParams P;
-    if (int rc = w24a_prepare(wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, P)) return rc;
-    return w24a_launch(x, npatch, P, y, stream);
 }

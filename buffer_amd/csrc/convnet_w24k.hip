@@ -152,22 +152,3 @@ __global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24k_rerun(const floa
     if (P.only_if[blockIdx.x] == 0) return;
     cyl_net_w24k_body(x, P, y, lds);
 }
-
-// The launch behind w24_launch for stacks that carry bit 2: flags checked (w24_check_flags, csrc/convnet_w24.hip), P.wt[] of the layers with bit 1 already behind their F(2x2) set
-static int w24k_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream)
-{
-    for (int l = 0; l < WG_LAYERS; l++)
-        if (P.relu[l] & W24K_FLAG) P.wt[l] += WG_BLOCKS * P.cout[l] * P.cin[l];      // behind the layer's F(2x2) set
-    size_t lds = sizeof(float) * WG_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = P.only_if ? grant_dynamic_lds((const void*)k_cyl_net_w24k_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_w24k, lds, grant)) return rc;
-    double macs = 0;
-    for (int l = 0; l < WG_LAYERS; l++) macs += 9.0 * P.cin[l] * P.cout[l];
-    TimedSpan span;
-    bool timed = !P.only_if && timing_begin((hipStream_t)stream, &span, 2.0 * 140 * macs * npatch, BUF_TIMED_CYL_NET);   // (a masked re-run is not a full launch)
-    if (P.only_if) k_cyl_net_w24k_rerun<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    else k_cyl_net_w24k<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-    return BUF_OK;
-}

@@ -416,93 +416,3 @@ extern "C" int buf_winograd_f25_tile_weights(const float* w_host, int cout, int 
         }
     return BUF_OK;
 }
-
-// The rules of buf_cylindrical_net_w25 beside those of buf_cylindrical_net_wg_all (host only).  wt25_host[l] (nullable per layer): the
-// layer's F(2x5) set (buf_winograd_f25_tile_weights) in a buffer of its own; allowed on a layer with 64 or 32 output channels and
-// Cin % 16 == 0, whatever F(2x4) flag or set it carries (the F(2x5) set wins; the layer's other buffers are not read).  A 32-output
-// layer with an F(2x5) set leaves the zero words alone, as one with an F(2x4) set does: wider layers may follow it.
-static int w25_check(const int* cin, const int* cout, const int* relu, const float* const* wt24_host, const float* const* wt25_host)
-{
-    const float* either[WG_LAYERS];
-    for (int l = 0; l < WG_LAYERS; l++) {
-        BUF_REQUIRE(!wt25_host[l] || ((cout[l] == 64 || cout[l] == 32) && cin[l] > 0 && cin[l] % 16 == 0), BUF_EINVAL,
-                    "buf_cylindrical_net_w25: layer %d (%d -> %d) takes no F(2x5) set (64 or 32 output channels, Cin %% 16 == 0)", l, cin[l], cout[l]);
-        either[l] = wt25_host[l] ? wt25_host[l] : wt24_host[l];
-    }
-    // w24a_check with the F(2x5) layers counted among those that run no older 32-output form; its rule for a set of the layer's own
-    // (no F(2x4) flag) holds for the F(2x4) sets only
-    if (int rc = wg_check_widths(cin, cout, false)) return rc;
-    if (int rc = w24_check_flags(cin, cout, relu)) return rc;
-    bool f22_ran = false;
-    int f22_layer = -1;
-    for (int l = 0; l < WG_LAYERS; l++) {
-        BUF_REQUIRE(!wt24_host[l] || (!(relu[l] & (WG_F24_FLAG | W24K_FLAG)) && (cout[l] == 64 || cout[l] == 32)), BUF_EINVAL,
-                    "buf_cylindrical_net_w25: layer %d (%d -> %d, flags %d) takes no F(2x4) set of its own (64 or 32 output channels, no F(2x4) flag)",
-                    l, cin[l], cout[l], relu[l]);
-        BUF_REQUIRE(!f22_ran || cout[l] == 32, BUF_EINVAL,
-                    "buf_cylindrical_net_w25: layer %d has unsupported widths %d -> %d (once a 32-output layer in the F(2x2) form has run, layer %d here, "
-                    "only 32-output layers may follow)", l, cin[l], cout[l], f22_layer);
-        if (cout[l] == 32 && !either[l] && !f22_ran) { f22_ran = true; f22_layer = l; }
-    }
-    return BUF_OK;
-}
-
-// 0 when buf_cylindrical_net_w25 would accept these widths, relu words and sets (host only, no device call; only whether an entry of
-// wt24_host / wt25_host is null is looked at), else BUF_EINVAL with the reason
-extern "C" int buf_cylindrical_net_w25_flags(const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
-                                             const float* const* wt25_host)
-{
-    BUF_REQUIRE(cin_host && cout_host && relu_host && wt24_host && wt25_host, BUF_EINVAL, "buf_cylindrical_net_w25_flags: null argument");
-    return w25_check(cin_host, cout_host, relu_host, wt24_host, wt25_host);
-}
-
-// Everything buf_cylindrical_net_w25 checks, and the kernel's parameters, without a device call
-static int w25_prepare(const float* const* wt_host, const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
-                       const float* const* wt24_host, const float* const* wt25_host, CylWgParams& P)
-{
-    BUF_REQUIRE(wt_host && bias_host && cin_host && cout_host && relu_host && wt24_host && wt25_host, BUF_EINVAL, "buf_cylindrical_net_w25: null argument");
-    for (int l = 0; l < WG_LAYERS; l++) {
-        P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
-        P.cin[l] = cin_host[l]; P.cout[l] = cout_host[l]; P.relu[l] = relu_host[l];
-        BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "buf_cylindrical_net_w25: null weights for layer %d", l);
-    }
-    if (int rc = w25_check(P.cin, P.cout, P.relu, wt24_host, wt25_host)) return rc;
-    for (int l = 0; l < WG_LAYERS; l++) {
-        if (wt25_host[l]) { P.wt[l] = wt25_host[l]; P.relu[l] = (P.relu[l] & 1) | W25_FLAG; }
-        else if (P.relu[l] & WG_F24_FLAG) P.wt[l] += W24_SET_F22(P.cin[l]);
-        else if (P.relu[l] & W24K_FLAG) P.wt[l] += WG_BLOCKS * P.cout[l] * P.cin[l];       // behind the layer's F(2x2) set
-        else if (wt24_host[l]) { P.wt[l] = wt24_host[l]; P.relu[l] |= W24K_FLAG; }
-        P.relu[l] &= ~WG_F24_FLAG;
-    }
-    P.only_if = nullptr;
-    return BUF_OK;
-}
-
-static int w25_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream)
-{
-    size_t lds = sizeof(float) * WG_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = P.only_if ? grant_dynamic_lds((const void*)k_cyl_net_w25_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_w25, lds, grant)) return rc;
-    double macs = 0;
-    for (int l = 0; l < WG_LAYERS; l++) macs += 9.0 * P.cin[l] * P.cout[l];
-    TimedSpan span;
-    bool timed = !P.only_if && timing_begin((hipStream_t)stream, &span, 2.0 * 140 * macs * npatch, BUF_TIMED_CYL_NET);   // (a masked re-run is not a full launch)
-    if (P.only_if) k_cyl_net_w25_rerun<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    else k_cyl_net_w25<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-    return BUF_OK;
-}
-
-// x f32[np,Cin0,140] -> y f32[np,32,140] through k_cyl_net_w25: buf_cylindrical_net_wg_all with, per layer, an optional F(2x5) set
-extern "C" int buf_cylindrical_net_w25(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
-                                       const int* cout_host, const int* relu_host, const float* const* wt24_host, const float* const* wt25_host, float* y,
-                                       void* stream)
-{
-    BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "buf_cylindrical_net_w25: npatch=%d", npatch);
-    if (npatch == 0) return BUF_OK;
-    BUF_REQUIRE(x && y, BUF_EINVAL, "buf_cylindrical_net_w25: null argument");
-    CylWgParams P;
-    if (int rc = w25_prepare(wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, P)) return rc;
-    return w25_launch(x, npatch, P, y, stream);
-}

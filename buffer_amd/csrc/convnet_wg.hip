@@ -772,116 +772,3 @@ extern "C" int buf_winograd_tile_weights(const float* w_host, int cout, int cin,
 
 // N-tiles per group in the filter tiling of a layer with these widths (the Python side asks instead of restating the rule)
 extern "C" int buf_winograd_group(int cin, int cout) { return wg_group(cin, cout); }
-
-// The widths k_cyl_net_wg is built for, stated once: what buf_cylindrical_net_wg accepts and buf_cylindrical_net_wg_supports reports.
-// follow: the rule that only 32-output layers follow a 32-output layer (buf_cylindrical_net_wg_all states it per layer form instead).
-static int wg_check_widths(const int* cin, const int* cout, bool follow = true)
-{
-    for (int l = 0; l < WG_LAYERS; l++) {
-        const int ci = cin[l], co = cout[l];
-        BUF_REQUIRE(ci > 0 && ci % 16 == 0 && ci <= WG_MAXC && (co == 32 || co == 64 || co == 128), BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d", l, ci, co);
-        BUF_REQUIRE(co != 128 || ci % 32 == 0, BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (128 output channels need Cin %% 32 == 0)", l, ci, co);
-        BUF_REQUIRE(co != 32 || (ci % 32 == 0 && ci <= 64), BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (32 output channels need Cin = 32 or 64)", l, ci, co);
-        BUF_REQUIRE(l == 0 || ci == cout[l - 1], BUF_EINVAL, "buf_cylindrical_net_wg: layer %d width mismatch", l);
-        // The 32-output layers hand their K-split partial sums over through the rows of the channels 64..95, zero words included
-        // (wg_layer_mksplit); those words are written once at kernel start, so no wider layer may follow.
-        BUF_REQUIRE(!follow || l == 0 || cout[l - 1] != 32 || co == 32, BUF_EINVAL,
-                    "buf_cylindrical_net_wg: layer %d has unsupported widths %d -> %d (only 32-output layers may follow a 32-output layer)", l, ci, co);
-    }
-    BUF_REQUIRE(cout[WG_LAYERS - 1] == 32, BUF_EINVAL, "buf_cylindrical_net_wg: the last layer must have 32 channels");
-    return BUF_OK;
-}
-
-// 0 when the Winograd fp32 kernel is built for this stack of widths (what buf_cylindrical_net_wg would accept), else BUF_EINVAL with the reason
-extern "C" int buf_cylindrical_net_wg_supports(const int* cin_host, const int* cout_host)
-{
-    BUF_REQUIRE(cin_host && cout_host, BUF_EINVAL, "buf_cylindrical_net_wg_supports: null argument");
-    return wg_check_widths(cin_host, cout_host);
-}
-
-// relu_host[l] bit 1 (WG_F24_FLAG): the layer's filter buffer holds the F(2x4) set behind the F(2x2) set and the stack runs in
-// k_cyl_net_w24 (csrc/convnet_w24.hip), which launches it: w24_launch.  Bit 2 (BUF_CYL_F24K) likewise for the K-split F(2x4) form of
-// 64-output layers (csrc/convnet_w24k.hip; `form` picks the pass-split form of csrc/convnet_w24p.hip instead).  Every word above 1 goes to w24_launch, which checks the flag rules; callers that pass
-// 0 / 1 never reach it.
-#define WG_F24_FLAG BUF_CYL_F24
-static inline bool wg_f24_flagged(int relu) { return relu >= 2; }
-static int w24_launch(const float* x, int npatch, CylWgParams P, float* y, void* stream, int form);
-
-// x f32[np,48,140] -> y f32[np,32,140]; weights in the Winograd-domain tiling (see CylWgParams).
-static int wg_launch(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
-                     const int* cout_host, const int* relu_host, float* y, const int* only_if, void* stream, int form)
-{
-    BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "buf_cylindrical_net_wg: npatch=%d", npatch);
-    BUF_REQUIRE(form >= BUF_CYL_FORM_DEFAULT && form <= BUF_CYL_FORM_PASS_SPLIT, BUF_EINVAL,
-                "buf_cylindrical_net_wg: form=%d (-1: the library's default, 0: K split, 1: pass split)", form);
-    if (npatch == 0) return BUF_OK;
-    BUF_REQUIRE(x && y && wt_host && bias_host && cin_host && cout_host && relu_host, BUF_EINVAL, "buf_cylindrical_net_wg: null argument");
-    CylWgParams P;
-    for (int l = 0; l < WG_LAYERS; l++) {
-        P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
-        P.cin[l] = cin_host[l]; P.cout[l] = cout_host[l]; P.relu[l] = relu_host[l];
-        BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "buf_cylindrical_net_wg: null weights for layer %d", l);
-    }
-    if (int rc = wg_check_widths(P.cin, P.cout)) return rc;
-    P.only_if = only_if;
-    for (int l = 0; l < WG_LAYERS; l++)
-        if (wg_f24_flagged(relu_host[l])) return w24_launch(x, npatch, P, y, stream, form);
-    size_t lds = sizeof(float) * WG_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = only_if ? grant_dynamic_lds((const void*)k_cyl_net_wg_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cyl_net_wg, lds, grant)) return rc;
-    double macs = 0;
-    for (int l = 0; l < WG_LAYERS; l++) macs += 9.0 * P.cin[l] * P.cout[l];
-    TimedSpan span;
-    bool timed = !only_if && timing_begin((hipStream_t)stream, &span, 2.0 * 140 * macs * npatch, BUF_TIMED_CYL_NET);   // (a masked re-run is not a full launch)
-#ifdef WG_STAMP
-    BUF_CHECK_HIP(hipMalloc(&P.stamps, (size_t)npatch * (4 * 20 + 4) * sizeof(long long)));
-#endif
-    if (only_if) k_cyl_net_wg_rerun<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    else k_cyl_net_wg<<<npatch, WG_THREADS, lds, (hipStream_t)stream>>>(x, P, y);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-#ifdef WG_STAMP
-    {   // per-layer wave cycles (to the wave's arrival at the closing barrier | wait there), second half of the workgroups
-        BUF_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-        long long* h = (long long*)malloc((size_t)npatch * (4 * 20 + 4) * sizeof(long long));
-        BUF_CHECK_HIP(hipMemcpy(h, P.stamps, (size_t)npatch * (4 * 20 + 4) * sizeof(long long), hipMemcpyDeviceToHost));
-        double comp[WG_LAYERS][4] = {}, wait[WG_LAYERS][4] = {}, tot = 0, pre = 0; long n = 0;
-        for (int b = npatch / 2; b < npatch; b++, n++)
-            for (int w = 0; w < 4; w++) {
-                const long long* q = h + ((size_t)b * 4 + w) * 20;
-                for (int l = 0; l < WG_LAYERS; l++) { comp[l][w] += (double)(q[2 * l + 1] - q[2 * l]); wait[l][w] += (double)(q[2 * l + 2] - q[2 * l + 1]); }
-                if (w == 0) { tot += (double)(q[2 * WG_LAYERS] - q[0]); pre += (double)(q[0] - q[17]); }
-            }
-        if (n && npatch >= 1024) {
-            double dc = 0, dr = 0;
-            for (int b = npatch / 2; b < npatch; b++) { const long long* q = h + (size_t)npatch * 80 + (size_t)b * 4; dc += (double)(q[2] - q[0]); dr += (double)(q[3] - q[1]); }
-            fprintf(stderr, "  WG_STAMP in-kernel clock: %.0f shader cycles per workgroup over %.0f ticks of the 100 MHz counter -> %.3f GHz\n", dc / n, dr / n, dc / dr * 0.1);
-            fprintf(stderr, "WG_STAMP: %ld workgroups, layers total %.0f cycles per patch, input phase %.0f\n", n, tot / n, pre / n);
-            for (int l = 0; l < WG_LAYERS; l++) {
-                const double mf = 38.0 * (P.cin[l] / 4) * (P.cout[l] / 16) / 4;     // MFMAs per wave
-                fprintf(stderr, "  layer %d %3d->%3d: MFMAs/wave %5.0f | to barrier %7.0f %7.0f %7.0f %7.0f | wait %6.0f %6.0f %6.0f %6.0f | cycles per MFMA slot %.1f\n",
-                        l, P.cin[l], P.cout[l], mf, comp[l][0] / n, comp[l][1] / n, comp[l][2] / n, comp[l][3] / n, wait[l][0] / n, wait[l][1] / n,
-                        wait[l][2] / n, wait[l][3] / n, (comp[l][0] + wait[l][0]) / n / (2 * mf));
-            }
-        }
-        free(h); (void)hipFree(P.stamps);
-    }
-#endif
-    return BUF_OK;
-}
-
-extern "C" int buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
-                                      const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream)
-{
-    return wg_launch(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, y, nullptr, stream, BUF_CYL_FORM_DEFAULT);
-}
-
-// The same with the form of the layers that carry bit 2 stated by the caller (BUF_CYL_FORM_*; stacks without bit 2 run as they do above)
-extern "C" int buf_cylindrical_net_wg_form(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
-                                           const int* cin_host, const int* cout_host, const int* relu_host, int form, float* y, void* stream)
-{
-    return wg_launch(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, y, nullptr, stream, form);
-}

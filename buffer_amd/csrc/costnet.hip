@@ -579,99 +579,3 @@ extern "C" int buf_cost_winograd_group(int layer)
     static const int group[6] = { 0, 2, 2, 2, 2, 1 };
     return layer >= 0 && layer <= 5 ? group[layer] : 0;
 }
-
-// The kernel parameters of a launch (shared with csrc/costnet_w24.hip)
-static int cost_net_params(CostNetParams& P, const float* const* wt_host, const float* const* bias_host, const long long* s_rows,
-                           const long long* t_rows, int ele_n, const int* only_if, const char* who)
-{
-    for (int l = 0; l < CV_LAYERS; l++) {
-        P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
-        BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "%s: null weights for layer %d", who, l);
-    }
-    P.s_rows = s_rows; P.t_rows = t_rows;
-    P.chan_floats = s_rows ? ele_n * 20 : 100;
-    P.row_floats = 32 * P.chan_floats;
-    P.skip_floats = s_rows ? 20 : 0;                         // elevation row 0 of every channel is not part of the cost volume
-    P.only_if = only_if;
-    return BUF_OK;
-}
-
-// EXECUTED flops per match: layer 0 in its separated form (S-term 60 x 480 x 32, T-term 54 x 288 x 32 MAC instead of the
-// dense 972 x 864 x 32), then the valid convolutions 18x3x18 -> 16x1x16 -> 14 -> 12 -> 10 -> 8 -> 6 -> 4 -> 2 -> 1:
-// 2 * sum(out positions * K * Cout), layers 1..5 with 16 products per 2 x 2 output tile (Winograd) = 0.0519 GFLOP.  The dense algorithmic count of SURVEY 8d is 0.160 GFLOP/match
-// (bench.py reports both; the roofline fraction is taken on the executed count).
-static const double cost_net_macs_per_match =
-    60.0 * 480 * 32 + 54.0 * 288 * 32 + 16.0 * 64 * 96 * 64 +
-    16.0 * (49.0 * 64 * 64 + 36.0 * 64 * 128 + 25.0 * 128 * 128 + 16.0 * 128 * 64) +        // layers 2..5: 16 components per 2 x 2 tile
-    36.0 * 576 * 64 + 16.0 * 576 * 32 + 4.0 * 288 * 32 + 1.0 * 128 * 20;
-
-#ifdef CV_STAMP
-static int cv_stamp_begin(int m, long long** stamps)
-{
-    BUF_CHECK_HIP(hipMalloc(stamps, (size_t)m * 16 * sizeof(long long)));
-    BUF_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cv_stamp_ptr), stamps, sizeof(*stamps)));
-    return BUF_OK;
-}
-static int cv_stamp_end(int m, long long* stamps, void* stream, const char* kernel)
-{
-    if (m >= 2048) {
-        BUF_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-        long long* h = (long long*)malloc((size_t)m * 16 * sizeof(long long));
-        BUF_CHECK_HIP(hipMemcpy(h, stamps, (size_t)m * 16 * sizeof(long long), hipMemcpyDeviceToHost));
-        static const char* name[8] = { "A.1 (layer 0 maps)", "A.2 (layer 1)", "layer 2", "layer 3", "layer 4", "layer 5", "layer 6", "layers 7-9" };
-        double d[8] = {};
-        for (int b = m / 2; b < m; b++)
-            for (int i = 0; i < 8; i++) d[i] += (double)(h[(size_t)b * 16 + i + 1] - h[(size_t)b * 16 + i]);
-        for (int i = 0; i < 8; i++) fprintf(stderr, "  CV_STAMP %s %-20s %8.0f cycles per match\n", kernel, name[i], d[i] / (m - m / 2));
-        free(h);
-    }
-    (void)hipFree(stamps);
-    return BUF_OK;
-}
-#endif
-
-static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
-                           const long long* s_rows, const long long* t_rows, int ele_n, float* ind_out, void* stream, const char* who,
-                           const int* only_if = nullptr)
-{
-    CostNetParams P;
-    if (int rc = cost_net_params(P, wt_host, bias_host, s_rows, t_rows, ele_n, only_if, who)) return rc;
-    size_t lds = sizeof(float) * CV_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = only_if ? grant_dynamic_lds((const void*)k_cost_net_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cost_net, lds, grant)) return rc;
-    TimedSpan span;
-    bool timed = !only_if && timing_begin((hipStream_t)stream, &span, 2.0 * cost_net_macs_per_match * m, BUF_TIMED_COST_NET);   // (a masked re-run is not a full launch)
-#ifdef CV_STAMP
-    long long* stamps = nullptr;
-    if (int rc = cv_stamp_begin(m, &stamps)) return rc;
-#endif
-    if (only_if) k_cost_net_rerun<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, P, ind_out);
-    else k_cost_net<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, P, ind_out);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-#ifdef CV_STAMP
-    if (int rc = cv_stamp_end(m, stamps, stream, "k_cost_net")) return rc;
-#endif
-    return BUF_OK;
-}
-
-// s_eq, t_eq f32[m,32,5,20] (elevation rows 1..5 of the equivariant maps) -> ind f32[m]
-extern "C" int buf_cost_volume_net(const float* s_eq, const float* t_eq, int m, const float* const* wt_host,
-                                   const float* const* bias_host, float* ind_out, void* stream)
-{
-    BUF_REQUIRE(m >= 0, BUF_EINVAL, "buf_cost_volume_net: m=%d", m);
-    if (m == 0) return BUF_OK;
-    BUF_REQUIRE(s_eq && t_eq && wt_host && bias_host && ind_out, BUF_EINVAL, "buf_cost_volume_net: null argument");
-    return cost_net_launch(s_eq, t_eq, m, wt_host, bias_host, nullptr, nullptr, 7, ind_out, stream, "buf_cost_volume_net");
-}
-
-// The same with the gather fused in: equi f32[rows,32,ele_n,20] holds the FULL equivariant maps of all keypoints, match i pairs
-// row s_rows[i] with row t_rows[i] (int64, device) and the kernel reads elevation rows 1..5 of each (ele_n = 7) directly.
-extern "C" int buf_cost_volume_net_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
-                                          const float* const* wt_host, const float* const* bias_host, float* ind_out, void* stream)
-{
-    BUF_REQUIRE(m >= 0 && ele_n == 7, BUF_EINVAL, "buf_cost_volume_net_gather: m=%d ele_n=%d (the kernel is built for ele_n = 7)", m, ele_n);
-    if (m == 0) return BUF_OK;
-    BUF_REQUIRE(equi && s_rows && t_rows && wt_host && bias_host && ind_out, BUF_EINVAL, "buf_cost_volume_net_gather: null argument");
-    return cost_net_launch(equi, equi, m, wt_host, bias_host, s_rows, t_rows, ele_n, ind_out, stream, "buf_cost_volume_net_gather");
-}

@@ -17,7 +17,7 @@
 // columns through A4^T is that of any other window word.
 //
 // Every layer is switched by its filter set: a null set runs the layer as k_cost_net does.  The kernel is cost_net_body<true> of
-// csrc/costnet.hip; this file has the F(2x4) layer, the kernels and their entry points.
+// csrc/costnet.hip; this file has the F(2x4) layer and the kernels; their entry points: csrc/cnn_launch.hip.
 #include "common.h"
 
 struct CostNetW24Params {
@@ -105,53 +105,4 @@ __global__ void __launch_bounds__(CV_THREADS, 2) k_cost_net_w24_rerun(const floa
     extern __shared__ float lds[];
     if (Q.P.only_if[blockIdx.x] == 0) return;
     cost_net_body<true>(s_eq, t_eq, Q.P, ind_out, lds, Q.f24);
-}
-
-static int cost_net_w24_launch(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
-                               const float* const* f24_host, const long long* s_rows, const long long* t_rows, int ele_n, float* ind_out,
-                               void* stream, const char* who, const int* only_if = nullptr)
-{
-    CostNetW24Params Q;
-    if (int rc = cost_net_params(Q.P, wt_host, bias_host, s_rows, t_rows, ele_n, only_if, who)) return rc;
-    for (int i = 0; i < 3; i++) Q.f24[i] = f24_host[i];
-    size_t lds = sizeof(float) * CV_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = only_if ? grant_dynamic_lds((const void*)k_cost_net_w24_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cost_net_w24, lds, grant)) return rc;
-    // the span keeps k_cost_net's figure (16 products per 2 x 2 tile in layers 1..5, layer 6 direct): bench.py counts the matches of a launch by it
-    TimedSpan span;
-    bool timed = !only_if && timing_begin((hipStream_t)stream, &span, 2.0 * cost_net_macs_per_match * m, BUF_TIMED_COST_NET);
-#ifdef CV_STAMP
-    long long* stamps = nullptr;
-    if (int rc = cv_stamp_begin(m, &stamps)) return rc;
-#endif
-    if (only_if) k_cost_net_w24_rerun<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, Q, ind_out);
-    else k_cost_net_w24<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, Q, ind_out);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-#ifdef CV_STAMP
-    if (int rc = cv_stamp_end(m, stamps, stream, "k_cost_net_w24")) return rc;
-#endif
-    return BUF_OK;
-}
-
-// buf_cost_volume_net with f24_host[3] (nullable entries, DEVICE pointers): the F(2x4) sets of layers 2 and 4 (buf_winograd_f24_tile_weights
-// of the [Cout][Cin][3][3] filters) and the F(2x2) set of layer 6 (buf_winograd_tile_filters, group 1).  A layer without a set runs as in
-// k_cost_net from wt_host.
-extern "C" int buf_cost_volume_net_w24(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
-                                       const float* const* f24_host, float* ind_out, void* stream)
-{
-    BUF_REQUIRE(m >= 0, BUF_EINVAL, "buf_cost_volume_net_w24: m=%d", m);
-    if (m == 0) return BUF_OK;
-    BUF_REQUIRE(s_eq && t_eq && wt_host && bias_host && f24_host && ind_out, BUF_EINVAL, "buf_cost_volume_net_w24: null argument");
-    return cost_net_w24_launch(s_eq, t_eq, m, wt_host, bias_host, f24_host, nullptr, nullptr, 7, ind_out, stream, "buf_cost_volume_net_w24");
-}
-
-extern "C" int buf_cost_volume_net_w24_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
-                                              const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
-                                              float* ind_out, void* stream)
-{
-    BUF_REQUIRE(m >= 0 && ele_n == 7, BUF_EINVAL, "buf_cost_volume_net_w24_gather: m=%d ele_n=%d (the kernel is built for ele_n = 7)", m, ele_n);
-    if (m == 0) return BUF_OK;
-    BUF_REQUIRE(equi && s_rows && t_rows && wt_host && bias_host && f24_host && ind_out, BUF_EINVAL, "buf_cost_volume_net_w24_gather: null argument");
-    return cost_net_w24_launch(equi, equi, m, wt_host, bias_host, f24_host, s_rows, t_rows, ele_n, ind_out, stream, "buf_cost_volume_net_w24_gather");
 }

@@ -274,52 +274,3 @@ __global__ void __launch_bounds__(CV_THREADS, 2) k_cost_net_w24b_rerun(const flo
     if (Q.P.only_if[blockIdx.x] == 0) return;
     cost_net_body<true, true>(s_eq, t_eq, Q.P, ind_out, lds, Q.f24);
 }
-
-static int cost_net_w24b_launch(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
-                                const float* const* f24_host, const long long* s_rows, const long long* t_rows, int ele_n, float* ind_out,
-                                void* stream, const char* who, const int* only_if = nullptr)
-{
-    CostNetW24BParams Q;
-    if (int rc = cost_net_params(Q.P, wt_host, bias_host, s_rows, t_rows, ele_n, only_if, who)) return rc;
-    for (int i = 0; i < 5; i++) Q.f24[i] = f24_host[i];
-    size_t lds = sizeof(float) * CV_BUF;
-    static LdsGrant grant, grant_rerun;
-    if (int rc = only_if ? grant_dynamic_lds((const void*)k_cost_net_w24b_rerun, lds, grant_rerun) : grant_dynamic_lds((const void*)k_cost_net_w24b, lds, grant)) return rc;
-    // the span keeps k_cost_net's figure: bench.py counts the matches of a launch by it
-    TimedSpan span;
-    bool timed = !only_if && timing_begin((hipStream_t)stream, &span, 2.0 * cost_net_macs_per_match * m, BUF_TIMED_COST_NET);
-#ifdef CV_STAMP
-    long long* stamps = nullptr;
-    if (int rc = cv_stamp_begin(m, &stamps)) return rc;
-#endif
-    if (only_if) k_cost_net_w24b_rerun<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, Q, ind_out);
-    else k_cost_net_w24b<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, Q, ind_out);
-    if (timed) timing_end((hipStream_t)stream, &span);
-    BUF_LAUNCH_CHECK();
-#ifdef CV_STAMP
-    if (int rc = cv_stamp_end(m, stamps, stream, "k_cost_net_w24b")) return rc;
-#endif
-    return BUF_OK;
-}
-
-// buf_cost_volume_net_w24 with f24_host[5] (nullable entries, DEVICE pointers): the three sets of that entry point, then the F(2x4) sets
-// (buf_winograd_f24_tile_weights) of layer 1's collapsed filter [64][96 = (dk, c)][dn][dl] and of layer 3's [128][64][3][3].  A layer
-// without a set runs as in k_cost_net_w24.
-extern "C" int buf_cost_volume_net_w24b(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
-                                        const float* const* f24_host, float* ind_out, void* stream)
-{
-    BUF_REQUIRE(m >= 0, BUF_EINVAL, "buf_cost_volume_net_w24b: m=%d", m);
-    if (m == 0) return BUF_OK;
-    BUF_REQUIRE(s_eq && t_eq && wt_host && bias_host && f24_host && ind_out, BUF_EINVAL, "buf_cost_volume_net_w24b: null argument");
-    return cost_net_w24b_launch(s_eq, t_eq, m, wt_host, bias_host, f24_host, nullptr, nullptr, 7, ind_out, stream, "buf_cost_volume_net_w24b");
-}
-
-extern "C" int buf_cost_volume_net_w24b_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
-                                               const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
-                                               float* ind_out, void* stream)
-{
-    BUF_REQUIRE(m >= 0 && ele_n == 7, BUF_EINVAL, "buf_cost_volume_net_w24b_gather: m=%d ele_n=%d (the kernel is built for ele_n = 7)", m, ele_n);
-    if (m == 0) return BUF_OK;
-    BUF_REQUIRE(equi && s_rows && t_rows && wt_host && bias_host && f24_host && ind_out, BUF_EINVAL, "buf_cost_volume_net_w24b_gather: null argument");
-    return cost_net_w24b_launch(equi, equi, m, wt_host, bias_host, f24_host, s_rows, t_rows, ele_n, ind_out, stream, "buf_cost_volume_net_w24b_gather");
-}

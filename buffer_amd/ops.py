@@ -1070,23 +1070,24 @@ F25_DEFAULT = 'out64'
 F25_PARTS = {'all': (64, 32), 'out64': (64,), 'out32': (32,), 'off': (), None: ()}
 
 
+def form_parts(name, value, default, table):
+    """What a form argument of the four net classes names in `table`: None -> `default`, True -> 'all', False -> 'off', else a key."""
+    value = default if value is None else 'all' if value is True else 'off' if value is False else value
+    if value not in table:
+        raise ValueError(f"{name} = {value!r}: one of " + ", ".join(repr(k) for k in table if k is not None))
+    return table[value]
+
+
 def cyl_f25_parts(f24, f24k, f24p, f25):
     """The output widths whose layers get an F(2x5) set (k_cyl_net_w25).  An explicit f24 / f24k / f24p asks for one of the older
     kernels: no such layers then, and asking for both is an error."""
     explicit = not (f24 is None and f24k is None and f24p is None)
-    if f25 is None:
-        f25 = None if explicit else F25_DEFAULT
-    if f25 is True:
-        f25 = 'all'
-    if f25 is False:
-        f25 = 'off'
     if f25 == 'out128':
         raise ValueError("f25 = 'out128': the 128-output layers have no F(2x5) form (csrc/convnet_w25.hip)")
-    if f25 not in F25_PARTS:
-        raise ValueError(f"f25 = {f25!r}: one of 'all', 'out64', 'out32', 'off'")
-    if F25_PARTS[f25] and explicit and not (f24 in (None, True) and f24k in (None, True) and f24p in (None, True)):
+    parts = form_parts('f25', f25, None if explicit else F25_DEFAULT, F25_PARTS)
+    if parts and explicit and not (f24 in (None, True) and f24k in (None, True) and f24p in (None, True)):
         raise ValueError("f25 goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
-    return F25_PARTS[f25]
+    return parts
 
 
 def cyl_f25_filters(layers, parts, device):
@@ -1117,17 +1118,10 @@ def cyl_f24a_parts(f24, f24k, f24p, f24a):
     their defaults filled in.  An explicit f24 / f24k / f24p asks for one of the older kernels: no such layers then."""
     explicit = not (f24 is None and f24k is None and f24p is None)
     f24, f24k, f24p = (True if f24 is None else f24), (True if f24k is None else f24k), (F24P_DEFAULT if f24p is None else f24p)
-    if f24a is None:
-        f24a = None if explicit else F24A_DEFAULT
-    if f24a is True:
-        f24a = 'all'
-    if f24a is False:
-        f24a = 'off'
-    if f24a not in F24A_PARTS:
-        raise ValueError(f"f24a = {f24a!r}: one of 'all', 'out64', 'out32', 'off'")
-    if F24A_PARTS[f24a] and not (f24 and f24k and f24p):
+    parts = form_parts('f24a', f24a, None if explicit else F24A_DEFAULT, F24A_PARTS)
+    if parts and not (f24 and f24k and f24p):
         raise ValueError("f24a goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
-    return f24, f24k, f24p, F24A_PARTS[f24a]
+    return f24, f24k, f24p, parts
 
 
 def cyl_f24a_filters(layers, flags, parts, device):
@@ -1155,7 +1149,7 @@ class CylindricalNet:
         parts25 = cyl_f25_parts(f24, f24k, f24p, f25)
         f24, f24k, f24p, parts = cyl_f24a_parts(f24, f24k, f24p, f24a)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
-        self.entry = "buf_cylindrical_net_wg"
+        self.entry = "buf_cylindrical_net_wg"            # the family (CylindricalNetSplit: "buf_cylindrical_net_split"); self.fn is what is called
         self.form = 1 if f24p else 0
         flags = []
         for w, b, relu in layers:
@@ -1178,22 +1172,22 @@ class CylindricalNet:
         # the layers k_cyl_net_w25 runs on an F(2x5) set (it wins over the layer's F(2x4) flag or set)
         self.wt25, self._w25p = cyl_f25_filters(layers, parts25, device)
         self.f25_layers = [l for l, t in enumerate(self.wt25) if t is not None]
+        # The entry point, chosen once: the fp32 call, the split-safe call of CylindricalNetSplit, and what both take between the relu
+        # words and the outputs
+        if self.f25_layers:
+            fn, safe, self._extra = "w25", "split_safe_w25", (self._w24p, self._w25p)
+        elif self.f24_layers:
+            fn, safe, self._extra = "wg_all", "split_safe_all", (self._w24p,)
+        else:
+            fn, safe, self._extra = "wg_form", "split_safe_form", (self.form,)
+        self.fn, self.fn_split_safe = "buf_cylindrical_net_" + fn, "buf_cylindrical_net_" + safe
 
     def __call__(self, x):
         """x f32[P,16,420] (or [P,48,140]) -> f32[P,32,7,20]"""
-        L = _lib.lib()
         x = x.contiguous()
         P = x.shape[0]
         y = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
-        if self.f25_layers:
-            check(L.buf_cylindrical_net_w25(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self._w24p, self._w25p, _ptr(y), _stream()),
-                  "buf_cylindrical_net_w25")
-            return y
-        if self.f24_layers:
-            check(L.buf_cylindrical_net_wg_all(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self._w24p, _ptr(y), _stream()),
-                  "buf_cylindrical_net_wg_all")
-            return y
-        check(L.buf_cylindrical_net_wg_form(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, self.form, _ptr(y), _stream()), self.entry)
+        check(getattr(_lib.lib(), self.fn)(_ptr(x), P, self._wp, self._bp, self._ci, self._co, self._re, *self._extra, _ptr(y), _stream()), self.fn)
         return y
 
 
@@ -1221,12 +1215,12 @@ class CylindricalNetSplit:
     def __init__(self, layers, device, f24k=None, f24p=None, f24a=None, f25=None):
         """f24k, f24p, f24a, f25: the fp32 re-run's kernel, as in CylindricalNet (no form argument: k_cyl_net_w24a_rerun, or
         k_cyl_net_w25_rerun where F25_DEFAULT names layers)"""
-        parts25 = cyl_f25_parts(None, f24k, f24p, f25)
-        _, f24k, f24p, parts = cyl_f24a_parts(None, f24k, f24p, f24a)
+        cyl_f25_parts(None, f24k, f24p, f25)             # (the arguments are checked whether or not the fp32 side gets built)
+        form = cyl_f24a_parts(None, f24k, f24p, f24a)[2]
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_split"
         self.f24_layers, self.f24_all, self.f25_layers = [], False, []
-        self.form = 1 if f24p else 0                     # of the fp32 re-run, as in CylindricalNet
+        self.form = 1 if form else 0                     # of the fp32 re-run, as in CylindricalNet
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
             self.wt.append(torch.from_numpy(split_tile_filters(w).view(np.int16)).to(device))
@@ -1240,39 +1234,26 @@ class CylindricalNetSplit:
         self._co = (C.c_int * n)(*self.cout)
         self._re = (C.c_int * n)(*self.relu)
         self.last_flags = None
-        # the fp32 re-run needs the Winograd tiling of the same filters; widths it is not built for keep the raising contract
+        # the fp32 re-run is a CylindricalNet over the same layers (the split kernel itself takes the relu words 0 / 1); widths it is not
+        # built for keep the raising contract
         self.safe = n == 8 and _lib.lib().buf_cylindrical_net_wg_supports(self._ci, self._co) == 0 and not os.environ.get('BUF_SPLIT_UNSAFE')
+        self.f32 = CylindricalNet(layers, device, f24k=f24k, f24p=f24p, f24a=f24a, f25=f25) if self.safe else None
         if self.safe:
-            tiled = [cyl_layer_filters(w, f24k) for w, _, _ in layers]
-            self.wt_wg = [torch.from_numpy(wt).to(device) for wt, _ in tiled]
-            self._wwp = (C.c_void_p * n)(*[t.data_ptr() for t in self.wt_wg])
-            self._re_safe = (C.c_int * n)(*[r | f for r, (_, f) in zip(self.relu, tiled)])     # (the split kernel itself takes 0 / 1)
-            self.wt24, self._w24p = cyl_f24a_filters(layers, [f for _, f in tiled], parts, device)
-            self.f24_layers = [l for l, t in enumerate(self.wt24) if t is not None]
-            self.f24_all = bool(self.f24_layers) and all(f or t is not None for (_, f), t in zip(tiled, self.wt24))
-            self.wt25, self._w25p = cyl_f25_filters(layers, parts25, device)
-            self.f25_layers = [l for l, t in enumerate(self.wt25) if t is not None]
+            f = self.f32
+            self.wt_wg, self._wwp, self._re_safe = f.wt, f._wp, f._re
+            self.wt24, self._w24p, self.f24_layers, self.f24_all = f.wt24, f._w24p, f.f24_layers, f.f24_all
+            self.wt25, self._w25p, self.f25_layers = f.wt25, f._w25p, f.f25_layers
+            self.fn = f.fn_split_safe
 
     def _safe_call(self, x, head):
-        L = _lib.lib()
         x = x.contiguous()
         P = x.shape[0]
         out = torch.empty((P, self.cout[-1], 7, 20), dtype=torch.float32, device=x.device)
         desc = torch.empty((P, 32), dtype=torch.float32, device=x.device) if head is not None else None
         self.last_flags = torch.empty((max(P, 1),), dtype=torch.int32, device=x.device)
-        if self.f25_layers:
-            check(L.buf_cylindrical_net_split_safe_w25(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self._w24p,
-                                                       self._w25p, _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc),
-                                                       _ptr(self.status), _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe_w25")
-            return (desc, out) if head is not None else out
-        if self.f24_layers:
-            check(L.buf_cylindrical_net_split_safe_all(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self._w24p,
-                                                       _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
-                                                       _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe_all")
-            return (desc, out) if head is not None else out
-        check(L.buf_cylindrical_net_split_safe_form(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, self.form,
-                                                    _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
-                                                    _ptr(self.last_flags), _stream()), "buf_cylindrical_net_split_safe_form")
+        check(getattr(_lib.lib(), self.fn)(_ptr(x), P, self._wp, self._wwp, self._bp, self._ci, self._co, self._re_safe, *self.f32._extra,
+                                           _ptr(head.params) if head is not None else None, _ptr(out), _ptr(desc), _ptr(self.status),
+                                           _ptr(self.last_flags), _stream()), self.fn)
         return (desc, out) if head is not None else out
 
     def __call__(self, x):
@@ -1369,15 +1350,7 @@ COST_F24_PARTS = {'all': (2, 4, 6), 'l2': (2,), 'l4': (4,), 'l6': (6,), 'off': (
 
 
 def cost_f24_parts(f24):
-    if f24 is None:
-        f24 = COST_F24_DEFAULT
-    if f24 is True:
-        f24 = 'all'
-    if f24 is False:
-        f24 = 'off'
-    if f24 not in COST_F24_PARTS:
-        raise ValueError(f"f24 = {f24!r}: one of 'all', 'l2', 'l4', 'l6', 'off'")
-    return COST_F24_PARTS[f24]
+    return form_parts('f24', f24, COST_F24_DEFAULT, COST_F24_PARTS)
 
 
 def cost_f24_filters(layers, parts):
@@ -1404,15 +1377,7 @@ COST_F24B_PARTS = {'all': (1, 3), 'l1': (1,), 'l3': (3,), 'off': ()}
 
 
 def cost_f24b_parts(f24, f24b):
-    if f24b is None:
-        f24b = COST_F24B_DEFAULT if f24 is None else 'off'
-    if f24b is True:
-        f24b = 'all'
-    if f24b is False:
-        f24b = 'off'
-    if f24b not in COST_F24B_PARTS:
-        raise ValueError(f"f24b = {f24b!r}: one of 'all', 'l1', 'l3', 'off'")
-    return COST_F24B_PARTS[f24b]
+    return form_parts('f24b', f24b, COST_F24B_DEFAULT if f24 is None else 'off', COST_F24B_PARTS)
 
 
 def cost_f24b_filters(layers, parts):
@@ -1481,46 +1446,35 @@ class CostVolumeNet:
             self.bias.append(torch.from_numpy(np.ascontiguousarray(b)).to(device))
         self._wp = (C.c_void_p * 10)(*[t.data_ptr() for t in self.wt])
         self._bp = (C.c_void_p * 10)(*[t.data_ptr() for t in self.bias])
+        # The kernel, chosen once: the suffix of its dense, gathered and split-safe entry points and the sets they take behind the biases
+        if self.parts_b:
+            self.kernel, self._sets = "_w24b", (self._fpb,)
+        elif self.parts:
+            self.kernel, self._sets = "_w24", (self._fp,)
+        else:
+            self.kernel, self._sets = "", ()
+
+    def _run(self, s_eq, t_eq, s_rows, t_rows, m):
+        """dense (s_rows is None) or gathered (s_eq = t_eq = the full maps)"""
+        out = torch.empty((m,), dtype=torch.float32, device=s_eq.device)
+        fn = "buf_cost_volume_net" + self.kernel + ("" if s_rows is None else "_gather")
+        head = (_ptr(s_eq), _ptr(t_eq), m) if s_rows is None else (_ptr(s_eq), 7, _ptr(s_rows), _ptr(t_rows), m)
+        check(getattr(_lib.lib(), fn)(*head, self._wp, self._bp, *self._sets, _ptr(out), _stream()), fn)
+        return out
 
     def __call__(self, s_eq, t_eq):
         """s_eq, t_eq f32[M,32,5,20] -> f32[M]"""
-        L = _lib.lib()
         s_eq, t_eq = s_eq.contiguous(), t_eq.contiguous()
-        m = s_eq.shape[0]
-        out = torch.empty((m,), dtype=torch.float32, device=s_eq.device)
-        if self.parts_b:
-            check(L.buf_cost_volume_net_w24b(_ptr(s_eq), _ptr(t_eq), m, self._wp, self._bp, self._fpb, _ptr(out), _stream()),
-                  "buf_cost_volume_net_w24b")
-            return out
-        if self.parts:
-            check(L.buf_cost_volume_net_w24(_ptr(s_eq), _ptr(t_eq), m, self._wp, self._bp, self._fp, _ptr(out), _stream()),
-                  "buf_cost_volume_net_w24")
-            return out
-        check(L.buf_cost_volume_net(_ptr(s_eq), _ptr(t_eq), m, self._wp, self._bp, _ptr(out), _stream()),
-              "buf_cost_volume_net")
-        return out
+        return self._run(s_eq, t_eq, None, None, s_eq.shape[0])
 
     def gathered(self, equi, s_rows, t_rows):
         """equi f32[rows,32,7,20] (full maps of all keypoints), s_rows / t_rows int64[M] -> f32[M]: the row gather and the
         elevation slice 1..5 (BUFFER.py:291-292) happen inside the kernel."""
-        L = _lib.lib()
         equi = _dev(equi, torch.float32, "CostVolumeNet.gathered")
         if equi.dim() != 4 or tuple(equi.shape[1:]) != (32, 7, 20):
             raise _lib.BufferHipError(f"CostVolumeNet.gathered: expected [rows,32,7,20] maps, got {tuple(equi.shape)}")
         s_rows, t_rows = _dev(s_rows, torch.int64, "s_rows"), _dev(t_rows, torch.int64, "t_rows")
-        m = int(s_rows.shape[0])
-        out = torch.empty((m,), dtype=torch.float32, device=equi.device)
-        if self.parts_b:
-            check(L.buf_cost_volume_net_w24b_gather(_ptr(equi), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self._fpb, _ptr(out),
-                                                    _stream()), "buf_cost_volume_net_w24b_gather")
-            return out
-        if self.parts:
-            check(L.buf_cost_volume_net_w24_gather(_ptr(equi), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self._fp, _ptr(out),
-                                                   _stream()), "buf_cost_volume_net_w24_gather")
-            return out
-        check(L.buf_cost_volume_net_gather(_ptr(equi), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, _ptr(out), _stream()),
-              "buf_cost_volume_net_gather")
-        return out
+        return self._run(equi, equi, s_rows, t_rows, int(s_rows.shape[0]))
 
 
 class CostVolumeNetSplit:
@@ -1564,22 +1518,11 @@ class CostVolumeNetSplit:
         self.last_flags = None
 
     def _safe(self, s_eq, t_eq, s_rows, t_rows, m, dev):
-        L = _lib.lib()
         out = torch.empty((m,), dtype=torch.float32, device=dev)
         self.last_flags = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
-        if self.parts_b:
-            check(L.buf_cost_volume_net_split_safe_w24b(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp,
-                                                        self.f32._bp, self.f32._fpb, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()),
-                  "buf_cost_volume_net_split_safe_w24b")
-            return out
-        if self.parts:
-            check(L.buf_cost_volume_net_split_safe_w24(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp,
-                                                       self.f32._bp, self.f32._fp, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()),
-                  "buf_cost_volume_net_split_safe_w24")
-            return out
-        check(L.buf_cost_volume_net_split_safe(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp,
-                                               self.f32._bp, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()),
-              "buf_cost_volume_net_split_safe")
+        fn = "buf_cost_volume_net_split_safe" + self.f32.kernel
+        check(getattr(_lib.lib(), fn)(_ptr(s_eq), _ptr(t_eq), 7, _ptr(s_rows), _ptr(t_rows), m, self._wp, self._bp, self.f32._wp, self.f32._bp,
+                                      *self.f32._sets, _ptr(out), _ptr(self.status), _ptr(self.last_flags), _stream()), fn)
         return out
 
     def __call__(self, s_eq, t_eq):

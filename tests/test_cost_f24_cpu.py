@@ -36,8 +36,8 @@ def test_resources(code_object, name):
     assert m['group_segment_fixed_size'] == 0, 'static LDS beside the dynamic buffer'
     src = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'costnet.hip')).read()
     cv_buf = int(re.search(r'#define CV_BUF (\d+)', src).group(1))
-    w24 = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'costnet_w24.hip')).read()
-    assert w24.count('size_t lds = sizeof(float) * CV_BUF;') == 1 and 2 * 4 * cv_buf <= 160 * 1024
+    launch = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'cnn_launch.hip')).read()      # (the cost kernels' one launcher)
+    assert launch.count('size_t lds = sizeof(float) * CV_BUF;') == 1 and 2 * 4 * cv_buf <= 160 * 1024
     text = kernel_text(asm, name)
     assert not [op for _, op, _ in text if re.match(r'v_pk_(mul|add|fma)_f32', op)]
     assert not [op for _, op, _ in text if op.startswith('scratch_')]

@@ -30,7 +30,8 @@ def test_resources(code_object, name):
     src = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'costnet.hip')).read()
     cv_buf = int(re.search(r'#define CV_BUF (\d+)', src).group(1))
     w24b = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'costnet_w24b.hip')).read()
-    assert w24b.count('size_t lds = sizeof(float) * CV_BUF;') == 1 and 2 * 4 * cv_buf <= 160 * 1024
+    launch = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'cnn_launch.hip')).read()      # (the cost kernels' one launcher)
+    assert launch.count('size_t lds = sizeof(float) * CV_BUF;') == 1 and 2 * 4 * cv_buf <= 160 * 1024
     # layer 1's resident plane: in front of the layer-0 maps, even strides, the bank plan of the file's head
     rs, cs = (int(re.search(rf'#define {n} (\d+)', w24b).group(1)) for n in ('CWB_RS1', 'CWB_CS1'))
     sm = int(re.search(r'#define CVA_SM (\d+)', src).group(1))
