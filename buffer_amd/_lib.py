@@ -132,6 +132,7 @@ _SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "buf_fpfh_ws_bytes": (_sz, [_i]),
     "buf_fpfh": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "buf_iss_keypoints": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "buf_fgr_ws_bytes": (_sz, [_i, _i, _i]),
     "buf_fgr_batched": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.c_double, _i, _i, C.c_double, C.c_double, _i, C.c_double, _i, _i,
                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

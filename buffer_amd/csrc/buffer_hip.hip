@@ -34,6 +34,7 @@
 #include "cnn_launch.hip"             // the host side of the nine kernels above: behind all of them
 #include "split_safe.hip"
 #include "fpfh.hip"
+#include "iss.hip"
 #include "fgr.hip"
 #include "sc2.hip"
 #include "clique.hip"

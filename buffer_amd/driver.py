@@ -179,6 +179,10 @@ def add_descriptor_args(ap):
                          'spatial-compatibility consensus, one batched call per chunk (buffer_amd/sc2.py).  clique: greedy maximum clique of the '
                          'compatibility graph + truncated least squares, one batched call per chunk (buffer_amd/clique.py), also reporting '
                          '"certified_pairs" = the pairs whose clique reaches the k-core bound; the summary carries "estimator"')
+    ap.add_argument('--keypoints', default='all', choices=('all', 'iss'),
+                    help='the points --descriptor fpfh matches.  all: every point of the second-level clouds (default).  iss: their ISS '
+                         'keypoints (buffer_amd/keypoints.py: salient radius 6 voxels, non-max radius 4 voxels); the summary carries '
+                         '"keypoints" = the detector, the two radii and the mean keypoints per cloud')
 
 
 def parse_with_preset(ap, argv, driver_name):
@@ -191,6 +195,8 @@ def parse_with_preset(ap, argv, driver_name):
         ap.error('--stage-metrics measures the stages of the learned path: not available with --descriptor fpfh')
     if a.estimator != 'ransac' and a.descriptor != 'fpfh':
         ap.error(f'--estimator {a.estimator} chooses the estimator of the classical baseline: it needs --descriptor fpfh')
+    if a.keypoints != 'all' and a.descriptor != 'fpfh':
+        ap.error(f'--keypoints {a.keypoints} chooses the detector of the classical baseline: it needs --descriptor fpfh')
     if a.refine == 'voxelized' and a.descriptor == 'fpfh':
         ap.error('--refine voxelized refines the learned path: not available with --descriptor fpfh')
     if a.refine_voxel is not None and not (0.0 < a.refine_voxel < float('inf')):
@@ -214,7 +220,7 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
     --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor" and
     "estimator", --estimator choosing its RANSAC, its Fast Global Registration, its SC2-PCR or its max-clique + TLS estimator, which adds
-    "certified_pairs").
+    "certified_pairs"; --keypoints iss makes it match ISS keypoints instead of every point and adds "keypoints").
     --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
     unrefined poses.
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
@@ -224,7 +230,9 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     fpfh = getattr(a, 'descriptor', 'buffer') == 'fpfh'
     if fpfh:
         from .fpfh import FpfhRegistration
-        pipe = FpfhRegistration(cfg, dev, estimator=getattr(a, 'estimator', 'ransac'))     # no neighbourhood limits: nothing to calibrate
+        iss = getattr(a, 'keypoints', 'all') == 'iss'
+        pipe = FpfhRegistration(cfg, dev, estimator=getattr(a, 'estimator', 'ransac'),     # no neighbourhood limits: nothing to calibrate
+                                keypoints='iss' if iss else None)
     else:
         pipe = BufferPipeline(cfg, dev)
     if a.limits and not fpfh:
@@ -278,6 +286,10 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
             out['estimator'] = getattr(a, 'estimator', 'ransac')
             if certified is not None:
                 out['certified_pairs'] = int((certified == 1).sum())
+            if pipe.keypoints == 'iss':                      # (the mean is this rank's: the counts stay on the rank that found them)
+                kc = np.concatenate(pipe.keypoint_counts_log or [np.zeros(0, np.int64)])
+                out['keypoints'] = dict(detector='iss', salient_radius=pipe.iss_salient_radius, non_max_radius=pipe.iss_non_max_radius,
+                                        mean_per_cloud=float(kc.mean()) if len(kc) else 0.0)
         if ref_out is not None:
             out['refined'] = ref_out
         overlaps = None

@@ -8,7 +8,8 @@ from its published form (include/buffer_hip.h, N6; parity unpinned).
     FpfhRegistration    estimator='ransac' (default), 'fgr' (buffer_amd/fgr.py: one batched Fast Global Registration call per
                         batch on the concatenated match lists), 'sc2' (buffer_amd/sc2.py: one batched SC2-PCR call per batch on the
                         same lists) or 'clique' (buffer_amd/clique.py: one batched max-clique + TLS call per batch on the same
-                        lists); register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
+                        lists); keypoints='iss': matching and the estimator on ISS keypoints (buffer_amd/keypoints.py) instead of every
+                        point; register_batch / register_batches with the return shapes of pipeline.BufferPipeline, on the second-level
                         clouds and normals of driver.upload's dicts
 """
 import numpy as np
@@ -19,12 +20,14 @@ from . import ops
 ESTIMATORS = ('ransac', 'fgr')
 ALL_ESTIMATORS = ESTIMATORS + ('sc2',)
 KNOWN_ESTIMATORS = ALL_ESTIMATORS + ('clique',)
+KEYPOINTS = (None, 'iss')
 
 
-def compute_fpfh(points, normals, radius, max_nn=100, lengths=None):
+def compute_fpfh(points, normals, radius, max_nn=100, lengths=None, grid=None):
     """points, normals f32[n,3] (device; several clouds stacked when `lengths` int[nc] is given) -> FPFH f64[n,33]: the neighbours
     of a point are the max_nn nearest inside `radius` within its own cloud, itself included (open3d's KDTreeSearchParamHybrid).
-    One CellGrid over the stacked clouds, one query with k = max_nn, one buf_fpfh call for all clouds."""
+    One CellGrid over the stacked clouds, one query with k = max_nn, one buf_fpfh call for all clouds.  grid: a CellGrid over the same
+    points and lengths with a radius no smaller (shared with keypoints.iss_keypoints); the rows, and so the result, are the same."""
     points = ops._dev(points, torch.float32, "compute_fpfh.points")
     n = int(points.shape[0])
     lens = np.array([n], np.int32) if lengths is None else np.asarray(lengths, np.int32).reshape(-1)
@@ -34,8 +37,11 @@ def compute_fpfh(points, normals, radius, max_nn=100, lengths=None):
         raise ValueError(f"compute_fpfh: max_nn={max_nn} (2..128)")
     if n == 0:
         return torch.zeros((0, 33), dtype=torch.float64, device=points.device)
-    grid = ops.CellGrid(points, lens, float(radius))
-    nbr = grid.query(points, lens, int(max_nn), q_order=grid.order)
+    if grid is None:
+        grid = ops.CellGrid(points, lens, float(radius))
+    elif grid.radius < float(radius) or grid.ns != n or not np.array_equal(grid.s_lengths, lens):
+        raise ValueError("compute_fpfh: the given grid does not cover these clouds at this radius")
+    nbr = grid.query(points, lens, int(max_nn), radius=float(radius), q_order=grid.order)
     return ops.fpfh(points, normals, nbr, int(max_nn))
 
 
@@ -74,10 +80,24 @@ class FpfhRegistration:
     ops.SC2_MAX_ROWS (16 384) matches is an error, not a truncation.
     estimator='clique': the max-clique + TLS estimator on the same matches (deterministic as well), with d_thr = tim_thr = inlier_thr =
     the same dist_factor * cfg.voxel_size_0, t_thr = half of it and CliqueOptions' defaults otherwise, under the same row limit; the
-    last call's `certified` (bool[B]: the clique reaches the k-core bound) and `bound` (int32[B]) stay on the object, on the device."""
+    last call's `certified` (bool[B]: the clique reaches the k-core bound) and `bound` (int32[B]) stay on the object, on the device.
+    keypoints=None (default): every point is described and matched.  keypoints='iss': ISS keypoints (buffer_amd/keypoints.py) with the
+    salient / non-max radii iss_salient_factor / iss_non_max_factor * cfg.voxel_size_0 (open3d's 6 x / 4 x resolution heuristic, the
+    voxel size standing in for the resolution), iss_gamma = (gamma_21, gamma_32) and iss_min_neighbors; FPFH is still computed for
+    every point, matching and the estimator then run on the keypoints' rows alone (fewer than 3 matches: the identity, as ever).
+    `keypoint_counts` keeps the last call's keypoints per cloud (int64[2B], host); refine_batch goes on refining on the dense clouds."""
 
-    def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac'):
+    def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac',
+                 keypoints=None, iss_salient_factor=6.0, iss_non_max_factor=4.0, iss_gamma=(0.975, 0.975), iss_min_neighbors=5):
         self.cfg, self.device = cfg, torch.device(device)
+        if keypoints not in KEYPOINTS:
+            raise ValueError(f'FpfhRegistration: unknown keypoints {keypoints!r} (one of {KEYPOINTS})')
+        self.keypoints = keypoints
+        self.iss_salient_radius = float(iss_salient_factor) * cfg.voxel_size_0
+        self.iss_non_max_radius = float(iss_non_max_factor) * cfg.voxel_size_0
+        self.iss_gamma, self.iss_min_neighbors = (float(iss_gamma[0]), float(iss_gamma[1])), int(iss_min_neighbors)
+        self.keypoint_counts = None          # keypoints='iss': int64[2B] per-cloud keypoints of the last register_batch call (host)
+        self.keypoint_counts_log = []        # and of every call so far, in call order (the drivers average it)
         if self.device.type != 'cuda':
             raise RuntimeError('FpfhRegistration runs on a HIP device only (no CPU path)')
         if estimator not in KNOWN_ESTIMATORS:
@@ -109,7 +129,10 @@ class FpfhRegistration:
         pts = torch.cat([i['points'] for i in inps]).float().contiguous()
         nrm = torch.cat([i['features'][:, :3] for i in inps]).float().contiguous()
         lens = np.concatenate([np.asarray(i['lengths'], np.int32).reshape(2) for i in inps])
-        F = compute_fpfh(pts, nrm, self.radius, self.max_nn, lens)
+        if self.keypoints == 'iss':
+            pts, lens, F = self._iss_sets(pts, nrm, lens)
+        else:
+            F = compute_fpfh(pts, nrm, self.radius, self.max_nn, lens)
         off = np.concatenate([[0], np.cumsum(lens)])
         if self.estimator == 'fgr':
             return self._fgr_batch(pts, lens, off, F, seeds)
@@ -124,6 +147,19 @@ class FpfhRegistration:
             out.append(ransac_on_matches(pts[s0:t0], pts[t0:t1], corr, self.cfg.ransac_hypotheses, seeds[b], self.max_dist,
                                          self.edge_similarity))
         return out
+
+    def _iss_sets(self, pts, nrm, lens):
+        """keypoints='iss': FPFH of EVERY point (a descriptor needs the SPFH of all its neighbours) and the ISS keypoints on one shared
+        grid, then the keypoints' coordinates and descriptor rows -> (points f32[K,3], per-cloud keypoint counts int32[2B], F f64[K,33]):
+        what matching and the estimators then see in place of the dense clouds"""
+        from . import keypoints
+        grid = ops.CellGrid(pts, lens, max(self.radius, self.iss_salient_radius, self.iss_non_max_radius))
+        F = compute_fpfh(pts, nrm, self.radius, self.max_nn, lens, grid=grid)
+        idx, counts = keypoints.iss_keypoints(pts, self.iss_salient_radius, self.iss_non_max_radius, self.iss_gamma[0], self.iss_gamma[1],
+                                              self.iss_min_neighbors, lengths=lens, grid=grid)
+        self.keypoint_counts = counts
+        self.keypoint_counts_log.append(counts)
+        return pts[idx].contiguous(), counts.astype(np.int32), F[idx].contiguous()
 
     @staticmethod
     def _batch_matches(pts, lens, off, F):

@@ -680,7 +680,30 @@ def fpfh(points, normals, nbr, max_nn=100, return_spfh=False):
     return (out, spfh) if return_spfh else out
 
 
-FGR_STATUS = ('NOTHING', 'OK', 'FAILED')                                                        # BUF_FGR_* of buffer_hip.h
+def iss_keypoints(points, nbr_sal, nbr_nms, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, max_nn=0, return_eig=True):
+    """buf_iss_keypoints: ISS keypoints of the points f32[n,3] from their sorted radius rows at the salient radius nbr_sal int32[n,k]
+    and at the non-max radius nbr_nms int32[n,k'] (CellGrid.query: padded with values >= n; the same tensor may serve both) ->
+    (mask u8[n], saliency f64[n], eig f64[n,3] descending or None).  max_nn: 0 = whole rows, else the first max_nn columns.  The rows may
+    belong to several stacked clouds: a row stays inside its cloud."""
+    L = _lib.lib()
+    points = _dev(points, torch.float32, "iss_keypoints.points")
+    nbr_sal, nbr_nms = _dev(nbr_sal, torch.int32, "iss_keypoints.nbr_sal"), _dev(nbr_nms, torch.int32, "iss_keypoints.nbr_nms")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"iss_keypoints: points {tuple(points.shape)} is not [N,3]")
+    n = int(points.shape[0])
+    for what, nbr in (("nbr_sal", nbr_sal), ("nbr_nms", nbr_nms)):
+        if nbr.dim() != 2 or nbr.shape[0] != n:
+            raise ValueError(f"iss_keypoints: {what} {tuple(nbr.shape)} is not [{n},k]")
+    mask = torch.empty((n,), dtype=torch.uint8, device=points.device)
+    sal = torch.empty((n,), dtype=torch.float64, device=points.device)
+    eig = torch.empty((n, 3), dtype=torch.float64, device=points.device) if return_eig else None
+    check(L.buf_iss_keypoints(_ptr(points), n, _ptr(nbr_sal), int(nbr_sal.shape[1]), _ptr(nbr_nms), int(nbr_nms.shape[1]), int(max_nn),
+                              float(gamma_21), float(gamma_32), int(min_neighbors), _ptr(sal), _ptr(eig), _ptr(mask), _stream()),
+          "buf_iss_keypoints")
+    return mask, sal, eig
+
+
+FGR_STATUS = ('NOTHING', 'OK', 'FAILED')                                                       # BUF_FGR_* of buffer_hip.h
 FGR_MAX_TUPLES = 4096
 
 

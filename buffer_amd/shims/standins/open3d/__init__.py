@@ -4,6 +4,7 @@ libbuffer_hip.so (open3d==0.13.0 is a pip dependency of the reference, README.md
     geometry.PointCloud                 points / normals / colors, voxel_down_sample, estimate_normals,
                                         orient_normals_towards_camera_location, transform, paint_uniform_color
                                         (ThreeDMatch/dataset.py:91-153, KITTI/dataset.py:102-176, utils/common.py:569-578)
+    geometry.keypoint                   compute_iss_keypoints -> buffer_amd/keypoints.py iss_keypoints (buf_iss_keypoints)
     utility.Vector3dVector, Vector2iVector
     io.read_point_cloud                 PLY vertices (utils/tools.py:6-7)
     pipelines.registration              registration_ransac_based_on_correspondence (models/BUFFER.py:314-326) -> buf_ransac_kabsch,

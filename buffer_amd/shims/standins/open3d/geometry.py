@@ -97,3 +97,34 @@ class PointCloud:
         n[flip] *= -1.0
         self._normals = Vector3dVector(n)
         return self
+
+
+def _compute_iss_keypoints(input, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+    """open3d geometry.keypoint.compute_iss_keypoints -> PointCloud of the keypoints, in row order, with their normals if the input
+    has them (buffer_amd/keypoints.py iss_keypoints, csrc/iss.hip; restated from the published algorithm, unpinned: include/buffer_hip.h
+    N11 lists the deviations).  A radius of 0 is open3d's heuristic: 6 x (salient) / 4 x (non-max) the cloud's resolution = the mean
+    distance of a point to its nearest other point (ops.knn at k = 2, fp32)."""
+    import torch
+    from buffer_amd import keypoints, ops
+    out = PointCloud()
+    if not input.has_points():
+        return out
+    pts_h = np.asarray(input.points).reshape(-1, 3)
+    pts = torch.from_numpy(pts_h.astype(np.float32)).to(_device())
+    if salient_radius == 0.0 or non_max_radius == 0.0:
+        res = 0.0
+        if len(pts_h) >= 2:
+            res = float(ops.knn(pts[None], pts[None], 2)[0][0, :, 1].double().mean())
+        salient_radius, non_max_radius = 6.0 * res, 4.0 * res
+    if not (salient_radius > 0.0 and non_max_radius > 0.0):     # a single point, or all points coincident: nothing is salient
+        return out
+    idx = keypoints.iss_keypoints(pts, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)[0].cpu().numpy()
+    out._points = Vector3dVector(pts_h[idx])
+    if input.has_normals():
+        out._normals = Vector3dVector(np.asarray(input.normals)[idx])
+    return out
+
+
+class keypoint:
+    """open3d.geometry.keypoint"""
+    compute_iss_keypoints = staticmethod(_compute_iss_keypoints)

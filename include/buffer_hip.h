@@ -73,7 +73,9 @@ int         buf_device_count(void);
 #define BUF_TIMED_CLIQUE_WALK    22  /* N10 k_clique_walk: work = seed ranks launched */
 #define BUF_TIMED_CLIQUE_POSE    23  /* N10 k_clique_pose (GNC-TLS + voting): work = pairs */
 #define BUF_TIMED_CLIQUE_POLISH  24  /* N10 k_clique_polish: work = pairs */
-#define BUF_TIMED_NKERNELS       25
+#define BUF_TIMED_ISS_SALIENCY   25  /* N11 k_iss_saliency: work = n * (4*k_sal + 24*K + 32) bytes, K = the columns read (an upper bound: rows are shorter) */
+#define BUF_TIMED_ISS_NMS        26  /* N11 k_iss_nms: work = n * (4*k_nms + 8*K + 9) bytes (an upper bound as well) */
+#define BUF_TIMED_NKERNELS       27
 void        buf_timing_enable(int on);
 long long   buf_timing_collect(double* total_ms, double* total_bytes);
 long long   buf_timing_collect_kernel(int kernel_id, double* total_ms, double* total_work);
@@ -630,6 +632,34 @@ size_t  buf_fpfh_ws_bytes(int n);
 int     buf_fpfh(const float* pts, const float* normals, int n, const int* nbr, int k_nbr, int max_nn,
                  double* fpfh_out /* f64[n,33] */, double* spfh_out /* f64[n,33], nullable = use ws */,
                  void* ws, size_t ws_bytes, void* stream);
+
+/* N11  ISS keypoints (Intrinsic Shape Signatures, Zhong 2009, in the simplified form of open3d's compute_iss_keypoints, restated
+ * from its published form, parity unpinned: this text is the specification).  One call for any number of stacked clouds, two
+ * launches (saliency, then non-maximum suppression, which reads saliency_out), no workspace, nothing read back.
+ * pts f32[n,3]; nbr_sal int32[n,k_sal] / nbr_nms int32[n,k_nms] = a buf_grid_query row per point at the salient / the non-max radius
+ * (ascending by (d2, index), padded with values >= n: the rows stay inside a point's cloud, so no lengths are needed; the two may be
+ * one array).  saliency_out f64[n]; eig_out f64[n,3] (nullable); mask_out u8[n]: 1 = keypoint.
+ * Rows: the valid entries of a row are those with 0 <= idx < n among its first min(max_nn, k) columns (max_nn == 0: all k columns);
+ *   the point itself is one of them (column 0 is not skipped: the covariance is taken over the whole support, as open3d does).
+ * Saliency of point i, m_i = the valid entries of its salient row.  m_i < min_neighbors: eigenvalues and saliency are 0.  Otherwise,
+ *   all fp64 on the fp32 coordinates promoted, no FMA: mu = (sum p_j) / m_i and C_ab = (sum (p_j,a - mu_a)(p_j,b - mu_b)) / m_i, six
+ *   entries, every sum over the valid entries in column order.  lambda1 >= lambda2 >= lambda3 = the eigenvalues of C: cyclic Jacobi,
+ *   pivots (0,1), (0,2), (1,2), until the off-diagonal absolute sum is <= 1e-20 of the diagonal's or 12 sweeps are done: a
+ *   deterministic function of the six entries (backward stable: each lambda is within a few ulp of lambda1 of the exact one).
+ *   s_i = lambda3 if lambda1 > 0 and lambda2 < gamma_21 * lambda1 and lambda3 < gamma_32 * lambda2, else 0 (products: open3d divides;
+ *   lambda1 > 0 restates its cov.isZero() exit).  eig_out[i] = (lambda1, lambda2, lambda3).
+ * Non-maximum suppression: mask_i = 1 iff s_i > 0, the non-max row of i has at least min_neighbors valid entries, and no valid entry j
+ *   of it has s_j > s_i.  Ties keep both points (open3d's IsLocalMaxima).
+ * Further deviations from open3d: its radius search is in fp64 on a KD-tree, the rows here come from the caller (buf_grid_query: fp32
+ *   d2 < r*r); it takes the resolution heuristic and the cloud, here both radii arrive as rows.
+ * A NaN or infinite point has an empty row in the grid, so it falls under the first rule, and it is in no other row: every output is
+ * finite.  No float atomics, every sum has a fixed order: a point's outputs are the same bits alone, in any batch and on reruns.
+ * BUF_EINVAL before any device work, buf_last_error naming the argument, for n < 0, k_sal or k_nms < 1, max_nn < 0,
+ * min_neighbors < 1, a gamma that is not finite or not positive, and with n > 0 a null pts, nbr_sal, nbr_nms, saliency_out or
+ * mask_out.  n == 0 succeeds and touches nothing. */
+int     buf_iss_keypoints(const float* pts, int n, const int* nbr_sal, int k_sal, const int* nbr_nms, int k_nms, int max_nn,
+                          double gamma_21, double gamma_32, int min_neighbors, double* saliency_out /* f64[n] */,
+                          double* eig_out /* f64[n,3], nullable */, unsigned char* mask_out /* u8[n] */, void* stream);
 
 /* N7  Fast Global Registration (Zhou, Park, Koltun, ECCV 2016; open3d registration_fast_based_on_feature_matching restated from
  * its published form, parity unpinned: this text is the specification).  B pairs per call, two launches, nothing read back.
