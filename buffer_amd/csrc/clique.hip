@@ -1,7 +1,7 @@
 // N10  Max-clique + truncated-least-squares pose estimation on given correspondences, the method made known by TEASER++ (Yang, Shi,
 // Carlone, T-RO 2021), restated from its published form with the deviations of include/buffer_hip.h (scale 1, a greedy clique with
 // the k-core bound beside it, no certification, N8's refit appended).  B pairs per call, 9 kernels, nothing read back.  The rows,
-// the bit matrix, the Kabsch solver, the fixed-shape sums and the residual are N8's (sc2.hip), called as they are.
+// the bit matrix, the refit loop and the residual are N8's (sc2.hip), the Kabsch solver and the fixed-shape sums pose_math.h's.
 //
 //   k_sc2_gather, k_sc2_compat   N8's: rows and the bit matrix C of e_ij <= d_thr (its diagonal bit is masked where the graph is read)
 //   k_clique_deg      one wavefront per row: population count of its words, minus the diagonal
@@ -18,19 +18,15 @@
 //   k_clique_pose     one workgroup per pair: the winner, its members' points in LDS, GNC-TLS over the TIMs (recomputed, never
 //                     stored: a weight is a function of the previous rotation and mu), then the three votes (bitonic sort of the 2K
 //                     endpoints, a lane per candidate)
-//   k_clique_polish   N8's refinement started from that pose (k_sc2_refine's loop; its arguments do not fit: other info, other NOTHING)
+//   k_clique_polish   N8's refinement started from that pose (sc2_refit), with its own info words and its own NOTHING rule
 // All fp64 without FMA; integer LDS atomics only; every float sum in a fixed shape: a pair's outputs are the same bits alone, in any
 // batch and across runs.
+#include "pose_math.h"
+
 #define CLQ_PEEL_W 1024
 #define CLQ_MAX_SEEDS 1024
 #define CLQ_MAX_MEMBERS 512
 #define CLQ_PINFO 4                                              // per pair in the workspace: live rows, bound
-
-__device__ __forceinline__ int clq_wave_sum_i(int v)
-{
-    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
 
 // grid (rows / 4, pairs): deg = popcount(row) - the diagonal bit; -1 on a dead row
 __global__ void __launch_bounds__(SC2_W) k_clique_deg(const Sc2Pair* __restrict__ mp, const int* __restrict__ live,
@@ -42,7 +38,7 @@ __global__ void __launch_bounds__(SC2_W) k_clique_deg(const Sc2Pair* __restrict_
     const unsigned long long* row = bits + P.bits_off + (long long)i * W;
     int c = 0;
     for (int w = lane; w < W; w += WAVE) c += __popcll(row[w]);
-    c = clq_wave_sum_i(c);
+    c = wave_sum(c);
     if (lane == 0) deg[(size_t)P.corr_off + i] = live[(size_t)P.corr_off + i] ? c - 1 : -1;
 }
 
@@ -299,9 +295,9 @@ __global__ void __launch_bounds__(SC2_W) k_clique_pose(const Sc2Pair* __restrict
                     for (int r = 0; r < 3; r++)
                         for (int c = 0; c < 3; c++) H[3 * r + c] += (w * al[r]) * be[c];
                 }
-            sc2_block_sum<9>(H, red);
+            tile_sum<9, SC2_WAVES>(H, red);
             for (int k = 0; k < 9; k++) R[k] = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
-            sc2_kabsch_rotation(H, R);
+            if (finite9(H)) kabsch_rotation(H, R);
             if (it == 0) {
                 double mx = 0.0;
                 for (int a = 0; a < K - 1; a++)
@@ -319,7 +315,7 @@ __global__ void __launch_bounds__(SC2_W) k_clique_pose(const Sc2Pair* __restrict
                     zo[0] += w == 0.0 ? 1.0 : 0.0;
                     zo[1] += w == 1.0 ? 1.0 : 0.0;
                 }
-            sc2_block_sum<2>(zo, red);
+            tile_sum<2, SC2_WAVES>(zo, red);
             for (int k = 0; k < 9; k++) Rp[k] = R[k];
             mu_prev = mu;
             if ((it >= 1 && zo[0] + zo[1] == (double)M && zo[0] == pz && zo[1] == po) || it + 1 == gnc_iterations) break;
@@ -401,7 +397,7 @@ __global__ void __launch_bounds__(SC2_W) k_clique_pose(const Sc2Pair* __restrict
     g[1] = n_live; g[2] = bound; g[3] = size; g[4] = win; g[5] = K; g[6] = steps; g[7] = 0;
 }
 
-// one workgroup per pair: N8's refinement from pose0 (k_sc2_refine's loop), NOTHING below 3 final inliers, every remaining output
+// one workgroup per pair: N8's refinement from pose0 (sc2_refit), NOTHING below 3 final inliers, every remaining output
 __global__ void __launch_bounds__(SC2_W) k_clique_polish(const Sc2Pair* __restrict__ mp, const double* __restrict__ rows,
                                                        const int* __restrict__ live, const double* __restrict__ pose0,
                                                        const int* __restrict__ ginfo, double inlier_thr, int refine_iterations,
@@ -417,30 +413,10 @@ __global__ void __launch_bounds__(SC2_W) k_clique_polish(const Sc2Pair* __restri
     const bool ok = ginfo[8 * (size_t)b] == BUF_CLIQUE_OK;
     double T[12];
     for (int k = 0; k < 12; k++) T[k] = pose0[12 * (size_t)b + k];
-    int last = 0;
-    for (int it = 0; ok && it < refine_iterations; it++) {       // (block-uniform: every thread holds the same T and counts)
-        double s[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-        for (int i = tid; i < n; i += SC2_W)
-            if (L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr) {
-                for (int c = 0; c < 6; c++) s[c] += R[6 * (size_t)i + c];
-                s[6] += 1.0;
-            }
-        sc2_block_sum<7>(s, red);
-        const int count = (int)s[6];
-        if ((it > 0 && count <= last) || count < 3) break;
-        last = count;
-        double cen[6], H[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-        for (int c = 0; c < 6; c++) cen[c] = s[c] / s[6];
-        for (int i = tid; i < n; i += SC2_W)
-            if (L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr)
-                for (int r = 0; r < 3; r++)
-                    for (int c = 0; c < 3; c++) H[3 * r + c] += (R[6 * (size_t)i + r] - cen[r]) * (R[6 * (size_t)i + 3 + c] - cen[3 + c]);
-        sc2_block_sum<9>(H, red);
-        sc2_pose(cen, cen + 3, H, T);
-    }
+    if (ok) sc2_refit(R, L, n, inlier_thr, refine_iterations, red, T);
     double fin[1] = { 0.0 };
     for (int i = tid; i < n; i += SC2_W) fin[0] += (ok && L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr) ? 1.0 : 0.0;
-    sc2_block_sum<1>(fin, red);
+    tile_sum<1, SC2_WAVES>(fin, red);
     const bool good = ok && fin[0] >= 3.0;
     if (inliers_out)
         for (int i = tid; i < n; i += SC2_W)
@@ -519,20 +495,14 @@ extern "C" int buf_clique_batched(const float* src, const int* src_lengths_host,
     BUF_REQUIRE(gnc_iterations >= 1 && gnc_iterations <= 1000 && refine_iterations >= 0, BUF_EINVAL,
                 "buf_clique_batched: gnc_iterations=%d (1..1000) refine_iterations=%d", gnc_iterations, refine_iterations);
     if (npairs == 0) return BUF_OK;
-    BUF_REQUIRE(src_lengths_host && tgt_lengths_host && corr_lengths_host, BUF_EINVAL, "buf_clique_batched: null host array");
-    BUF_REQUIRE(T_out && info_out, BUF_EINVAL, "buf_clique_batched: null output");
-    long long nst = 0, ntt = 0, nct = 0, maxn = 0;
-    for (int b = 0; b < npairs; b++) {
-        BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0 && corr_lengths_host[b] >= 0, BUF_EINVAL,
-                    "buf_clique_batched: negative length in pair %d", b);
+    long long nct, maxn;
+    const int brc = corr_batch_check("buf_clique_batched", src, src_lengths_host, tgt, tgt_lengths_host, corr, corr_lengths_host, npairs, true,
+                                     T_out, info_out, nct, maxn, [&](int b) {
         BUF_REQUIRE(corr_lengths_host[b] <= BUF_SC2_MAX_ROWS, BUF_EINVAL, "buf_clique_batched: %d correspondences in pair %d (at most %d)",
                     corr_lengths_host[b], b, BUF_SC2_MAX_ROWS);
-        nst += src_lengths_host[b]; ntt += tgt_lengths_host[b]; nct += corr_lengths_host[b];
-        maxn = corr_lengths_host[b] > maxn ? corr_lengths_host[b] : maxn;
-    }
-    BUF_REQUIRE(nst < 0x7fffffffLL && ntt < 0x7fffffffLL && nct < 0x7fffffffLL, BUF_EINVAL,
-                "buf_clique_batched: %lld / %lld points, %lld correspondences (int32 indices)", nst, ntt, nct);
-    BUF_REQUIRE((nst == 0 || src) && (ntt == 0 || tgt) && (nct == 0 || corr), BUF_EINVAL, "buf_clique_batched: null input");
+        return (int)BUF_OK;
+    });
+    if (brc) return brc;
     long long rows, words, counts;
     sc2_sizes(corr_lengths_host, npairs, max_seeds, rows, words, counts);
     const size_t need = buf_clique_ws_bytes(corr_lengths_host, npairs, max_seeds, max_members);

@@ -10,10 +10,9 @@
 //                   ascending order; the 27 sums of a step go through a xor-shuffle tree inside each wavefront and a fixed tree over
 //                   the four wavefronts in LDS; lane 0 solves and updates the pose, which the others read back from LDS.  The
 //                   normalised kept points live in the workspace (48 bytes per row), formed once.
-// icp_solve6 and the dT form of k_icp_update are restated here (fgr_solve6, fgr_apply): a second caller would be free to change how
-// the compiler inlines them into the ICP kernels.
 // No float atomics and a fixed order in every sum: a pair's outputs are the same bits alone, in any batch and across runs.
 #include "common.h"
+#include "pose_math.h"
 
 #define FGR_W 256
 #define FGR_WAVES (FGR_W / WAVE)
@@ -103,24 +102,6 @@ __global__ void __launch_bounds__(FGR_W) k_fgr_tuples(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------
-// sum of NV values per lane over the workgroup, in a fixed tree; the result is valid in thread 0 (red: FGR_WAVES * NV doubles)
-template <int NV>
-__device__ __forceinline__ void fgr_block_sum(double (&v)[NV], double* red)
-{
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-#pragma unroll
-    for (int k = 0; k < NV; k++)
-        for (int d = WAVE / 2; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
-    __syncthreads();                                             // red may still be read from the last use
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; k++) red[wave * NV + k] = v[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < NV; k++) v[k] = (red[k] + red[NV + k]) + (red[2 * NV + k] + red[3 * NV + k]);
-}
-
 // mean of the finite rows of a cloud -> c[3] in thread 0 (count in cnt); lane k adds rows k, k + FGR_W, ...
 __device__ __forceinline__ void fgr_mean(const float* __restrict__ p, int n, double* red, double c[3], double& cnt)
 {
@@ -129,7 +110,7 @@ __device__ __forceinline__ void fgr_mean(const float* __restrict__ p, int n, dou
         const double x = p[3 * (size_t)i], y = p[3 * (size_t)i + 1], z = p[3 * (size_t)i + 2];
         if (isfinite(x) && isfinite(y) && isfinite(z)) { v[0] += x; v[1] += y; v[2] += z; v[3] += 1.0; }
     }
-    fgr_block_sum<4>(v, red);
+    tile_sum<4, FGR_WAVES, false>(v, red);
     cnt = v[3];
     for (int k = 0; k < 3; k++) c[k] = v[k] / v[3];
 }
@@ -148,52 +129,14 @@ __device__ __forceinline__ double fgr_max_norm2(const float* __restrict__ p, int
     return m;
 }
 
-// H x = -g by LDL^T without pivoting (icp_solve6 restated); false when the system is not positive definite
-__device__ static bool fgr_solve6(const double* up, const double* g, double (&x)[6])
-{
-    double A[6][6], L[6][6], D[6], y[6];
-    int k = 0;
-    for (int r = 0; r < 6; r++)
-        for (int c = r; c < 6; c++) { A[r][c] = up[k]; A[c][r] = up[k]; k++; }
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-        for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
-        if (!(d > 0.0) || !isfinite(d)) return false;
-        D[j] = d;
-        L[j][j] = 1.0;
-        for (int i = j + 1; i < 6; i++) {
-            double e = A[i][j];
-            for (int m = 0; m < j; m++) e -= L[i][m] * L[j][m] * D[m];
-            L[i][j] = e / d;
-        }
-    }
-    for (int i = 0; i < 6; i++) {
-        double e = -g[i];
-        for (int m = 0; m < i; m++) e -= L[i][m] * y[m];
-        y[i] = e;
-    }
-    for (int i = 5; i >= 0; i--) {
-        double e = y[i] / D[i];
-        for (int m = i + 1; m < 6; m++) e -= L[m][i] * x[m];
-        x[i] = e;
-    }
-    for (int i = 0; i < 6; i++)
-        if (!isfinite(x[i])) return false;
-    return true;
-}
-
 // T <- dT(x) T on T = [R (9, row-major) | t (3)], dT = [Rz(x2) Ry(x1) Rx(x0) | x3..5]
 __device__ static void fgr_apply(const double (&x)[6], double* T)
 {
-    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-    double d[3][3];
-    d[0][0] = cg * cb; d[0][1] = cg * sb * sa - sg * ca; d[0][2] = cg * sb * ca + sg * sa;
-    d[1][0] = sg * cb; d[1][1] = sg * sb * sa + cg * ca; d[1][2] = sg * sb * ca - cg * sa;
-    d[2][0] = -sb;     d[2][1] = cb * sa;                d[2][2] = cb * ca;
-    double n[12];
+    double d[9], n[12];
+    rot_zyx(x, d);
     for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) n[3 * r + c] = (d[r][0] * T[c] + d[r][1] * T[3 + c]) + d[r][2] * T[6 + c];
-        n[9 + r] = ((d[r][0] * T[9] + d[r][1] * T[10]) + d[r][2] * T[11]) + x[3 + r];
+        for (int c = 0; c < 3; c++) n[3 * r + c] = (d[3 * r] * T[c] + d[3 * r + 1] * T[3 + c]) + d[3 * r + 2] * T[6 + c];
+        n[9 + r] = ((d[3 * r] * T[9] + d[3 * r + 1] * T[10]) + d[3 * r + 2] * T[11]) + x[3 + r];
     }
     for (int k = 0; k < 12; k++) T[k] = n[k];
 }
@@ -287,10 +230,10 @@ __global__ void __launch_bounds__(FGR_W) k_fgr_optimize(const float* __restrict_
 #pragma unroll
                 for (int a = 0; a < 6; a++) v[21 + a] += w * ((J[0][a] * r[0] + J[1][a] * r[1]) + J[2][a] * r[2]);
             }
-            fgr_block_sum<FGR_NV>(v, red);
+            tile_sum<FGR_NV, FGR_WAVES, false>(v, red);
             if (tid == 0) {
                 double x[6];
-                if (fgr_solve6(v, v + 21, x)) fgr_apply(x, sh + 8);
+                if (solve6(v, v + 21, x)) fgr_apply(x, sh + 8);
                 else sh[20] = 1.0;
             }
             __syncthreads();
@@ -334,6 +277,32 @@ extern "C" size_t buf_fgr_ws_bytes(int n_corr_total, int npairs, int max_tuples)
     return w.used();
 }
 
+// The (src, tgt, corr) batch of buf_fgr_batched, buf_sc2_batched and buf_clique_batched (fn = the entry point's name), in the order
+// all three test it: null host arrays (more_host: the entry point's further ones), null outputs, per pair a negative length and
+// then the entry point's own limit (pair_limit(b) sets the error and returns its code), the int32 totals, null inputs.
+// nct = correspondences of the batch, maxn = the most in one pair.
+template <class PairLimit>
+static int corr_batch_check(const char* fn, const float* src, const int* src_lengths_host, const float* tgt, const int* tgt_lengths_host,
+                            const int* corr, const int* corr_lengths_host, int npairs, bool more_host, const void* T_out,
+                            const void* info_out, long long& nct, long long& maxn, PairLimit pair_limit)
+{
+    BUF_REQUIRE(src_lengths_host && tgt_lengths_host && corr_lengths_host && more_host, BUF_EINVAL, "%s: null host array", fn);
+    BUF_REQUIRE(T_out && info_out, BUF_EINVAL, "%s: null output", fn);
+    long long nst = 0, ntt = 0;
+    nct = maxn = 0;
+    for (int b = 0; b < npairs; b++) {
+        BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0 && corr_lengths_host[b] >= 0, BUF_EINVAL,
+                    "%s: negative length in pair %d", fn, b);
+        if (const int rc = pair_limit(b)) return rc;
+        nst += src_lengths_host[b]; ntt += tgt_lengths_host[b]; nct += corr_lengths_host[b];
+        maxn = corr_lengths_host[b] > maxn ? corr_lengths_host[b] : maxn;
+    }
+    BUF_REQUIRE(nst < 0x7fffffffLL && ntt < 0x7fffffffLL && nct < 0x7fffffffLL, BUF_EINVAL,
+                "%s: %lld / %lld points, %lld correspondences (int32 indices)", fn, nst, ntt, nct);
+    BUF_REQUIRE((nst == 0 || src) && (ntt == 0 || tgt) && (nct == 0 || corr), BUF_EINVAL, "%s: null input", fn);
+    return BUF_OK;
+}
+
 extern "C" int buf_fgr_batched(const float* src, const int* src_lengths_host, const float* tgt, const int* tgt_lengths_host,
                                const int* corr, const int* corr_lengths_host, int npairs, const unsigned long long* seeds_host,
                                double tuple_scale, int max_tuples, int trial_factor, double mu_start, double delta, int delta_absolute,
@@ -354,19 +323,14 @@ extern "C" int buf_fgr_batched(const float* src, const int* src_lengths_host, co
     BUF_REQUIRE(decrease_every >= 1 && iterations >= 0, BUF_EINVAL, "buf_fgr_batched: decrease_every=%d iterations=%d", decrease_every,
                 iterations);
     if (npairs == 0) return BUF_OK;
-    BUF_REQUIRE(src_lengths_host && tgt_lengths_host && corr_lengths_host && seeds_host, BUF_EINVAL, "buf_fgr_batched: null host array");
-    BUF_REQUIRE(T_out && info_out, BUF_EINVAL, "buf_fgr_batched: null output");
-    long long nst = 0, ntt = 0, nct = 0;
-    for (int b = 0; b < npairs; b++) {
-        BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0 && corr_lengths_host[b] >= 0, BUF_EINVAL,
-                    "buf_fgr_batched: negative length in pair %d", b);
+    long long nct, maxn;
+    const int brc = corr_batch_check("buf_fgr_batched", src, src_lengths_host, tgt, tgt_lengths_host, corr, corr_lengths_host, npairs,
+                                     seeds_host != nullptr, T_out, info_out, nct, maxn, [&](int b) {
         BUF_REQUIRE((long long)trial_factor * corr_lengths_host[b] <= 0x7fffffffLL, BUF_EINVAL,
                     "buf_fgr_batched: trial_factor * %d correspondences of pair %d overflows int", corr_lengths_host[b], b);
-        nst += src_lengths_host[b]; ntt += tgt_lengths_host[b]; nct += corr_lengths_host[b];
-    }
-    BUF_REQUIRE(nst < 0x7fffffffLL && ntt < 0x7fffffffLL && nct < 0x7fffffffLL, BUF_EINVAL,
-                "buf_fgr_batched: %lld / %lld points, %lld correspondences (int32 indices)", nst, ntt, nct);
-    BUF_REQUIRE((nst == 0 || src) && (ntt == 0 || tgt) && (nct == 0 || corr), BUF_EINVAL, "buf_fgr_batched: null input");
+        return (int)BUF_OK;
+    });
+    if (brc) return brc;
     const size_t need = buf_fgr_ws_bytes((int)nct, npairs, max_tuples);
     BUF_REQUIRE(ws && ws_bytes >= need, BUF_EINVAL, "buf_fgr_batched: workspace %zu < %zu bytes", ws ? ws_bytes : (size_t)0, need);
 

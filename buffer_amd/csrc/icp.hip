@@ -21,6 +21,7 @@
 // Host round trips: one int (the number of active pairs) is read back after every 8th round, so a call makes at most
 // ceil((max_iteration + 1) / 8) small readbacks and no per-pair synchronisation.
 #include "common.h"
+#include "pose_math.h"
 
 #define ICP_TILE 256
 #define ICP_WAVES (ICP_TILE / WAVE)
@@ -33,7 +34,11 @@
 //   point-to-plane: upper triangle of J^T J (21, row by row), J^T r (6); J = [p x n, n], r = (p - q) . n
 //   generalized:    upper triangle of J^T M J (21, row by row), J^T M d (6); J = [-[p]x, I], d = p - q,
 //                   M = (C(n_q) + R C(n_s) R^T)^-1 with C(n) = I - (1 - eps) n n^T
-template <int M> struct IcpRec { static constexpr int NV = M == ICP_P2P ? 17 : 29; static constexpr int STRIDE = M == ICP_P2P ? 18 : 30; };
+template <int M> struct IcpRec {
+    static constexpr int NV = M == ICP_P2P ? 17 : 29, STRIDE = M == ICP_P2P ? 18 : 30;
+    static constexpr int CNT = 0, FIT = 0, D2 = 1, H = 2, G = 23, MIN_CNT = M == ICP_P2P ? 3 : 6;     // (what pose_update reads)
+    static constexpr bool KABSCH = M == ICP_P2P;
+};
 
 struct IcpState {
     double anchor[3];
@@ -41,26 +46,6 @@ struct IcpState {
     int done;
     int pad;
 };
-
-// sum of v over the ICP_TILE threads of the workgroup; the result lands in out[0..NV) (threads 0..NV-1 store it)
-template <int NV>
-__device__ __forceinline__ void icp_block_sum(double (&v)[NV], double (*part)[NV], double* __restrict__ out)
-{
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-#pragma unroll
-    for (int k = 0; k < NV; k++)
-        for (int d = WAVE / 2; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) part[w][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double s = part[0][threadIdx.x];
-        for (int j = 1; j < ICP_WAVES; j++) s += part[j][threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-}
 
 __global__ void __launch_bounds__(ICP_TILE) k_icp_setup(const float* __restrict__ src, const int* __restrict__ src_off,
                                                       const double* __restrict__ T_init, double* __restrict__ T,
@@ -75,7 +60,7 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_setup(const float* __restrict_
 #pragma unroll
         for (int c = 0; c < 3; c++) v[c] += (double)src[3 * (size_t)(lo + i) + c];
     }
-    icp_block_sum<3>(v, part, cen);
+    tile_sum<3, ICP_WAVES>(v, part, cen);
     __syncthreads();
     const double* Ti = T_init + 16 * (size_t)b;
     if (threadIdx.x < 16) T[16 * (size_t)b + threadIdx.x] = Ti[threadIdx.x];
@@ -95,21 +80,6 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_setup(const float* __restrict_
 // what only the Generalized ICP instantiation of k_icp_correspond takes (the other two have no such argument)
 struct IcpGicpArgs { const float* src_normals; double w; };              // w = 1 - epsilon
 __device__ __forceinline__ const IcpGicpArgs& icp_gicp_args(const IcpGicpArgs& a) { return a; }
-
-__device__ static void icp_cross(const double* a, const double* b, double* c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// row j of a normal array in fp64; a row that is not a unit vector (| |n|^2 - 1 | >= 1e-3, or any component not finite) is zero
-__device__ __forceinline__ void icp_gicp_normal(const float* __restrict__ normals, size_t j, double (&n)[3])
-{
-    n[0] = normals[3 * j]; n[1] = normals[3 * j + 1]; n[2] = normals[3 * j + 2];
-    const double l2 = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
-    if (!(fabs(l2 - 1.0) < 1e-3)) { n[0] = 0.0; n[1] = 0.0; n[2] = 0.0; }   // (NaN and inf fail the comparison)
-}
 
 template <int M, typename... G>
 __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __restrict__ grids, const int* __restrict__ table,
@@ -178,8 +148,8 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __r
                 const IcpGicpArgs& ga = icp_gicp_args(gicp...);
                 const double p[3] = { px, py, pz };
                 double nq[3], ns[3];
-                icp_gicp_normal(tgt_normals, (size_t)best, nq);
-                icp_gicp_normal(ga.src_normals, i, ns);
+                unit_normal_or_zero(tgt_normals, (size_t)best, nq);
+                unit_normal_or_zero(ga.src_normals, i, ns);
                 // S = C(n_q) + R C(n_s) R^T = (I - w n_q n_q^T) + (R R^T - w m m^T), m = R n_s; upper triangle 00 01 02 11 12 22
                 double m[3], S[6];
 #pragma unroll
@@ -194,41 +164,22 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __r
                             S[k++] = (((r == c ? 1.0 : 0.0) - ga.w * nq[r] * nq[c]) + rr) - ga.w * m[r] * m[c];
                         }
                 }
-                // Mm = S^-1 by cofactors (S is symmetric positive definite: both terms are, for eps > 0)
-                const double c00 = S[3] * S[5] - S[4] * S[4], c01 = S[2] * S[4] - S[1] * S[5], c02 = S[1] * S[4] - S[2] * S[3];
-                const double c11 = S[0] * S[5] - S[2] * S[2], c12 = S[1] * S[2] - S[0] * S[4], c22 = S[0] * S[3] - S[1] * S[1];
-                const double idet = 1.0 / ((S[0] * c00 + S[1] * c01) + S[2] * c02);
-                const double Mm[3][3] = { { c00 * idet, c01 * idet, c02 * idet }, { c01 * idet, c11 * idet, c12 * idet },
-                                          { c02 * idet, c12 * idet, c22 * idet } };
-                // with A = -[p]x: row r of M A is p x (row r of M), A^T x is p x x.  MA is formed once and serves all three blocks.
-                double MA[3][3], col[3], AtMA[3][3], Md[3], AtMd[3];
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-                    icp_cross(p, Mm[r], MA[r]);
-                    Md[r] = (Mm[r][0] * dx + Mm[r][1] * dy) + Mm[r][2] * dz;
-                }
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const double mc[3] = { MA[0][c], MA[1][c], MA[2][c] };
-                    icp_cross(p, mc, col);
-#pragma unroll
-                    for (int r = 0; r < 3; r++) AtMA[r][c] = col[r];
-                }
-                icp_cross(p, Md, AtMd);
+                GicpTerm gt;
+                gicp_term(S, p, dx, dy, dz, gt);
                 int k = 2;
 #pragma unroll
                 for (int r = 0; r < 3; r++) {                              // rows 0..2 of H: [A^T M A | A^T M], A^T M = (M A)^T
 #pragma unroll
-                    for (int c = r; c < 3; c++) v[k++] = AtMA[r][c];
+                    for (int c = r; c < 3; c++) v[k++] = gt.AtMA[r][c];
 #pragma unroll
-                    for (int c = 0; c < 3; c++) v[k++] = MA[c][r];
+                    for (int c = 0; c < 3; c++) v[k++] = gt.MA[c][r];
                 }
 #pragma unroll
                 for (int r = 0; r < 3; r++)                                // rows 3..5: M
 #pragma unroll
-                    for (int c = r; c < 3; c++) v[k++] = Mm[r][c];
+                    for (int c = r; c < 3; c++) v[k++] = gt.Mm[r][c];
 #pragma unroll
-                for (int r = 0; r < 3; r++) { v[23 + r] = AtMd[r]; v[26 + r] = Md[r]; }
+                for (int r = 0; r < 3; r++) { v[23 + r] = gt.AtMd[r]; v[26 + r] = gt.Md[r]; }
             } else {
                 const size_t j = 3 * (size_t)best;
                 const double nx = tgt_normals[j], ny = tgt_normals[j + 1], nz = tgt_normals[j + 2];
@@ -244,116 +195,19 @@ __global__ void __launch_bounds__(ICP_TILE) k_icp_correspond(const CellGrid* __r
             }
         }
     }
-    icp_block_sum<NV>(v, part, slab + (size_t)tile * IcpRec<M>::STRIDE);
+    tile_sum<NV, ICP_WAVES>(v, part, slab + (size_t)tile * IcpRec<M>::STRIDE);
 }
 
-// ---- fp64 solvers (one lane) ----------------------------------------------------------------
-// Kabsch: R maximising tr(R H) over proper rotations, H = sum (p - pc)(q - qc)^T.  One-sided Jacobi on the columns of H
-// (H V = U S), singular values sorted descending; with U3 = U1 x U2 and V3 = V1 x V2 the rotation V diag(1, 1, d) U^T of
-// the det-corrected SVD (d = sign det(V U^T)) is [V1 V2 V1xV2][U1 U2 U1xU2]^T whatever the sign of the third pair.
-__device__ static bool icp_unit(double* a)
+// One wave per pair, the update kernel of icp.hip and vgicp.hip.  Rec names the record: NV values at STRIDE, the slots CNT (terms),
+// FIT (numerator of fitness) and D2 (sum of d2), the step's sums from H on (and its gradient at G), the fewest terms MIN_CNT a
+// step takes, and KABSCH: the step is the Kabsch rotation about State's anchor, else the 6x6 solve.
+template <class Rec, class State>
+__device__ __forceinline__ void pose_update(const int* __restrict__ src_off, const int* __restrict__ tile_off,
+                                            const double* __restrict__ slab, int max_iteration, double rel_fitness, double rel_rmse,
+                                            double* __restrict__ T, double* __restrict__ fitness, double* __restrict__ rmse_out,
+                                            int* __restrict__ iters, State* __restrict__ st, int* __restrict__ active)
 {
-    const double l = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-    if (!(l > 0.0) || !isfinite(l)) return false;
-    a[0] /= l; a[1] /= l; a[2] /= l;
-    return true;
-}
-
-// a unit vector orthogonal to the unit vector u
-__device__ static void icp_any_orthogonal(const double* u, double* o)
-{
-    const double e[3] = { fabs(u[0]) < 0.6 ? 1.0 : 0.0, fabs(u[0]) < 0.6 ? 0.0 : 1.0, 0.0 };
-    icp_cross(u, e, o);
-    icp_unit(o);
-}
-
-__device__ static bool icp_kabsch_rotation(const double (&H)[3][3], double (&R)[3][3])
-{
-    double A[3][3], V[3][3];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) { A[r][c] = H[r][c]; V[r][c] = r == c ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 40; sweep++) {
-        bool rotated = false;
-        for (int pr = 0; pr < 3; pr++) {
-            const int i = pr == 2 ? 1 : 0, j = pr == 0 ? 1 : 2;
-            const double al = (A[0][i] * A[0][i] + A[1][i] * A[1][i]) + A[2][i] * A[2][i];
-            const double be = (A[0][j] * A[0][j] + A[1][j] * A[1][j]) + A[2][j] * A[2][j];
-            const double ga = (A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j];
-            if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
-            const double ze = (be - al) / (2.0 * ga);
-            const double t = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
-            const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-            for (int k = 0; k < 3; k++) {
-                const double ai = A[k][i], aj = A[k][j];
-                A[k][i] = cs * ai - sn * aj; A[k][j] = sn * ai + cs * aj;
-                const double vi = V[k][i], vj = V[k][j];
-                V[k][i] = cs * vi - sn * vj; V[k][j] = sn * vi + cs * vj;
-            }
-            rotated = true;
-        }
-        if (!rotated) break;
-    }
-    double s[3];
-    int o[3] = { 0, 1, 2 };
-    for (int c = 0; c < 3; c++) s[c] = (A[0][c] * A[0][c] + A[1][c] * A[1][c]) + A[2][c] * A[2][c];
-    for (int a = 0; a < 2; a++)                                               // descending, stable
-        for (int c = 0; c < 2 - a; c++)
-            if (s[o[c]] < s[o[c + 1]]) { const int t = o[c]; o[c] = o[c + 1]; o[c + 1] = t; }
-    double U1[3], U2[3], U3[3], V1[3], V2[3], V3[3];
-    for (int k = 0; k < 3; k++) { U1[k] = A[k][o[0]]; U2[k] = A[k][o[1]]; V1[k] = V[k][o[0]]; V2[k] = V[k][o[1]]; }
-    if (!icp_unit(U1)) return false;                                         // H = 0: no rotation to find
-    const double pj = (U1[0] * U2[0] + U1[1] * U2[1]) + U1[2] * U2[2];
-    for (int k = 0; k < 3; k++) U2[k] -= pj * U1[k];
-    if (!(s[o[1]] > 1e-28 * s[o[0]]) || !icp_unit(U2)) icp_any_orthogonal(U1, U2);   // rank 1: any completion
-    icp_cross(U1, U2, U3);
-    icp_cross(V1, V2, V3);
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) R[r][c] = (V1[r] * U1[c] + V2[r] * U2[c]) + V3[r] * U3[c];
-    return true;
-}
-
-// J^T J x = -J^T r by Cholesky (LDL^T without pivoting); false when the system is not positive definite
-__device__ static bool icp_solve6(const double* up, const double* g, double (&x)[6])
-{
-    double A[6][6], L[6][6], D[6], y[6];
-    int k = 0;
-    for (int r = 0; r < 6; r++)
-        for (int c = r; c < 6; c++) { A[r][c] = up[k]; A[c][r] = up[k]; k++; }
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-        for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
-        if (!(d > 0.0) || !isfinite(d)) return false;
-        D[j] = d;
-        L[j][j] = 1.0;
-        for (int i = j + 1; i < 6; i++) {
-            double e = A[i][j];
-            for (int m = 0; m < j; m++) e -= L[i][m] * L[j][m] * D[m];
-            L[i][j] = e / d;
-        }
-    }
-    for (int i = 0; i < 6; i++) {
-        double e = -g[i];
-        for (int m = 0; m < i; m++) e -= L[i][m] * y[m];
-        y[i] = e;
-    }
-    for (int i = 5; i >= 0; i--) {
-        double e = y[i] / D[i];
-        for (int m = i + 1; m < 6; m++) e -= L[m][i] * x[m];
-        x[i] = e;
-    }
-    for (int i = 0; i < 6; i++)
-        if (!isfinite(x[i])) return false;
-    return true;
-}
-
-template <int M>
-__global__ void __launch_bounds__(WAVE) k_icp_update(const int* __restrict__ src_off, const int* __restrict__ tile_off,
-                                                   const double* __restrict__ slab, int max_iteration, double rel_fitness,
-                                                   double rel_rmse, double* __restrict__ T, double* __restrict__ fitness,
-                                                   double* __restrict__ rmse_out, int* __restrict__ iters, IcpState* __restrict__ st,
-                                                   int* __restrict__ active)
-{
-    constexpr int NV = IcpRec<M>::NV;
+    constexpr int NV = Rec::NV;
     const int b = blockIdx.x, lane = threadIdx.x;
     if (st[b].done) return;
     const int t0 = tile_off[b], t1 = tile_off[b + 1];
@@ -361,54 +215,53 @@ __global__ void __launch_bounds__(WAVE) k_icp_update(const int* __restrict__ src
 #pragma unroll
     for (int k = 0; k < NV; k++) v[k] = 0.0;
     for (int t = t0 + lane; t < t1; t += WAVE) {
-        const double* rec = slab + (size_t)t * IcpRec<M>::STRIDE;
+        const double* rec = slab + (size_t)t * Rec::STRIDE;
 #pragma unroll
         for (int k = 0; k < NV; k++) v[k] += rec[k];
     }
 #pragma unroll
-    for (int k = 0; k < NV; k++)
-        for (int d = WAVE / 2; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
+    for (int k = 0; k < NV; k++) v[k] = wave_sum(v[k]);
     if (lane != 0) return;
     const int n = src_off[b + 1] - src_off[b];
-    const double cnt = v[0];
-    const double fit = n > 0 ? cnt / (double)n : 0.0;
-    const double rmse = cnt > 0.0 ? sqrt(v[1] / cnt) : 0.0;
+    const double cnt = v[Rec::CNT];
+    const double fit = n > 0 ? v[Rec::FIT] / (double)n : 0.0;
+    const double rmse = cnt > 0.0 ? sqrt(v[Rec::D2] / cnt) : 0.0;
     fitness[b] = fit;
     rmse_out[b] = rmse;
-    IcpState s = st[b];
+    State s = st[b];
     const int it = iters[b];
     bool stop;
     double dT[4][4];
     if (it > 0 && fabs(s.prev_fit - fit) < rel_fitness && fabs(s.prev_rmse - rmse) < rel_rmse) stop = true;   // converged
     else if (it >= max_iteration) stop = true;
-    else if (cnt < (M == ICP_P2P ? 3.0 : 6.0)) stop = true;                                               // too few matches
+    else if (cnt < (double)Rec::MIN_CNT) stop = true;                                                       // too few matches
     else {
         for (int r = 0; r < 4; r++)
             for (int c = 0; c < 4; c++) dT[r][c] = r == c ? 1.0 : 0.0;
-        if (M == ICP_P2P) {
-            const double* a = s.anchor;
-            double pc[3], qc[3], H[3][3], R[3][3];
-            for (int r = 0; r < 3; r++) { pc[r] = v[2 + r] / cnt; qc[r] = v[5 + r] / cnt; }
+        double R[9];
+        if constexpr (Rec::KABSCH) {
+            const double* a = s.anchor, *sp = v + Rec::H;        // sum P (3), sum Q (3), sum P Q^T (9)
+            double pc[3], qc[3], H[9];
+            for (int r = 0; r < 3; r++) { pc[r] = sp[r] / cnt; qc[r] = sp[3 + r] / cnt; }
             for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 3; c++) H[r][c] = v[8 + 3 * r + c] - cnt * pc[r] * qc[c];
-            stop = !icp_kabsch_rotation(H, R);
+                for (int c = 0; c < 3; c++) H[3 * r + c] = sp[6 + 3 * r + c] - cnt * pc[r] * qc[c];
+            stop = !kabsch_rotation(H, R);
             if (!stop) {
                 const double Pa[3] = { a[0] + pc[0], a[1] + pc[1], a[2] + pc[2] }, Qa[3] = { a[0] + qc[0], a[1] + qc[1], a[2] + qc[2] };
                 for (int r = 0; r < 3; r++) {
-                    for (int c = 0; c < 3; c++) dT[r][c] = R[r][c];
-                    dT[r][3] = Qa[r] - ((R[r][0] * Pa[0] + R[r][1] * Pa[1]) + R[r][2] * Pa[2]);
+                    for (int c = 0; c < 3; c++) dT[r][c] = R[3 * r + c];
+                    dT[r][3] = Qa[r] - ((R[3 * r] * Pa[0] + R[3 * r + 1] * Pa[1]) + R[3 * r + 2] * Pa[2]);
                 }
             }
         } else {
             double x[6];
-            stop = !icp_solve6(v + 2, v + 23, x);
+            stop = !solve6(v + Rec::H, v + Rec::G, x);
             if (!stop) {
-                // R = Rz(x2) Ry(x1) Rx(x0), t = x3..5 (open3d TransformVector6dToMatrix4d, restated)
-                const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-                dT[0][0] = cg * cb; dT[0][1] = cg * sb * sa - sg * ca; dT[0][2] = cg * sb * ca + sg * sa;
-                dT[1][0] = sg * cb; dT[1][1] = sg * sb * sa + cg * ca; dT[1][2] = sg * sb * ca - cg * sa;
-                dT[2][0] = -sb;     dT[2][1] = cb * sa;                dT[2][2] = cb * ca;
-                dT[0][3] = x[3]; dT[1][3] = x[4]; dT[2][3] = x[5];
+                rot_zyx(x, R);
+                for (int r = 0; r < 3; r++) {
+                    for (int c = 0; c < 3; c++) dT[r][c] = R[3 * r + c];
+                    dT[r][3] = x[3 + r];
+                }
             }
         }
     }
@@ -427,6 +280,55 @@ __global__ void __launch_bounds__(WAVE) k_icp_update(const int* __restrict__ src
         s.done = 1;
     }
     st[b] = s;
+}
+
+template <int M>
+__global__ void __launch_bounds__(WAVE) k_icp_update(const int* __restrict__ src_off, const int* __restrict__ tile_off,
+                                                   const double* __restrict__ slab, int max_iteration, double rel_fitness,
+                                                   double rel_rmse, double* __restrict__ T, double* __restrict__ fitness,
+                                                   double* __restrict__ rmse_out, int* __restrict__ iters, IcpState* __restrict__ st,
+                                                   int* __restrict__ active)
+{
+    pose_update<IcpRec<M>>(src_off, tile_off, slab, max_iteration, rel_fitness, rel_rmse, T, fitness, rmse_out, iters, st, active);
+}
+
+// Per-pair tile counts of tile-wide tiles as prefix offsets on the device (dst: npairs + 1 ints); the total comes back in *ntiles
+static int upload_tile_offsets(int* dst, const int* lengths_host, int npairs, int tile, const char* fn, int* ntiles, hipStream_t s)
+{
+    int* tiles = (int*)malloc(sizeof(int) * (size_t)npairs);
+    BUF_REQUIRE(tiles, BUF_EINVAL, "%s: out of host memory", fn);
+    long long nts = 0;
+    for (int b = 0; b < npairs; b++) nts += tiles[b] = cdiv(lengths_host[b], tile);
+    const int rc = upload_offsets(dst, tiles, npairs, (int)nts, fn, s);
+    free(tiles);
+    *ntiles = (int)nts;
+    return rc;
+}
+
+// The rounds of icp.hip and vgicp.hip on the workspace e (src_off, tile_off, slab, st, active): launch_terms() puts the kernel that writes the records on the stream, update is the
+// k_*_update entry point.  One int (the pairs still active) is read back after every 8th round.
+template <class Ws, class State, class Terms>
+static int pose_rounds(const Ws& e, Terms launch_terms, void (*update)(const int*, const int*, const double*, int, double, double, double*,
+                                                                       double*, double*, int*, State*, int*),
+                       int npairs, int max_iteration, double rel_fitness, double rel_rmse, double* T_out, double* fitness_out,
+                       double* rmse_out, int* iters_out, hipStream_t s)
+{
+    for (int r = 0; r <= max_iteration; r++) {
+        const bool probe = (r & 7) == 7 && r < max_iteration;
+        if (probe) BUF_CHECK_HIP(hipMemsetAsync(e.active, 0, sizeof(int), s));
+        launch_terms();
+        update<<<npairs, WAVE, 0, s>>>(e.src_off, e.tile_off, e.slab, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
+                                       iters_out, e.st, probe ? e.active : nullptr);
+        if (probe) {
+            BUF_LAUNCH_CHECK();
+            int left = 0;
+            BUF_CHECK_HIP(hipMemcpyAsync(&left, e.active, sizeof(int), hipMemcpyDeviceToHost, s));
+            BUF_CHECK_HIP(hipStreamSynchronize(s));
+            if (left == 0) break;
+        }
+    }
+    BUF_LAUNCH_CHECK();
+    return BUF_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -461,25 +363,13 @@ static int icp_rounds(const IcpWs& e, const buf_grid_t& g, const float* src, con
                       int npairs, int ntiles, float r2, int max_iteration, double rel_fitness, double rel_rmse, double* T_out,
                       double* fitness_out, double* rmse_out, int* iters_out, int* nn_out, hipStream_t s, G... gicp)
 {
-    for (int r = 0; r <= max_iteration; r++) {
-        const bool probe = (r & 7) == 7 && r < max_iteration;
-        if (probe) BUF_CHECK_HIP(hipMemsetAsync(e.active, 0, sizeof(int), s));
+    const auto terms = [&] {
         if (ntiles > 0)
             k_icp_correspond<M><<<ntiles, ICP_TILE, 0, s>>>((const CellGrid*)g.desc, g.table, (const float4*)g.sorted, src, e.src_off,
                                                            e.tile_off, npairs, tgt, tgt_normals, nt, r2, T_out, e.st, nn_out, e.slab,
                                                            gicp...);
-        k_icp_update<M><<<npairs, WAVE, 0, s>>>(e.src_off, e.tile_off, e.slab, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out,
-                                                rmse_out, iters_out, e.st, probe ? e.active : nullptr);
-        if (probe) {
-            BUF_LAUNCH_CHECK();
-            int left = 0;
-            BUF_CHECK_HIP(hipMemcpyAsync(&left, e.active, sizeof(int), hipMemcpyDeviceToHost, s));
-            BUF_CHECK_HIP(hipStreamSynchronize(s));
-            if (left == 0) break;
-        }
-    }
-    BUF_LAUNCH_CHECK();
-    return BUF_OK;
+    };
+    return pose_rounds(e, terms, k_icp_update<M>, npairs, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out, iters_out, s);
 }
 
 // buf_icp_batched (fn = its name, method 0 / 1) and buf_gicp_batched (method 2, with src_normals and epsilon): one body
@@ -496,12 +386,11 @@ static int icp_run(const char* fn, const float* src, const float* src_normals, c
     BUF_REQUIRE(max_iteration >= 0, BUF_EINVAL, "%s: max_iteration=%d", fn, max_iteration);
     if (npairs == 0) return BUF_OK;
     BUF_REQUIRE(src_lengths_host && tgt_lengths_host, BUF_EINVAL, "%s: null lengths", fn);
-    long long ns = 0, nt = 0, nts = 0;
+    long long ns = 0, nt = 0;
     for (int b = 0; b < npairs; b++) {
         BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0, BUF_EINVAL, "%s: negative length in pair %d", fn, b);
         ns += src_lengths_host[b];
         nt += tgt_lengths_host[b];
-        nts += cdiv(src_lengths_host[b], ICP_TILE);
     }
     BUF_REQUIRE(ns < 0x7fffffffLL && nt < 0x7fffffffLL, BUF_EINVAL, "%s: %lld / %lld points (int32 indices)", fn, ns, nt);
     BUF_REQUIRE(ns == 0 || src, BUF_EINVAL, "%s: null src", fn);
@@ -520,22 +409,19 @@ static int icp_run(const char* fn, const float* src, const float* src_normals, c
     if (rc) return rc;
     rc = upload_offsets(e.src_off, src_lengths_host, npairs, (int)ns, fn, s);
     if (rc) return rc;
-    int* tiles = (int*)malloc(sizeof(int) * (size_t)npairs);
-    BUF_REQUIRE(tiles, BUF_EINVAL, "%s: out of host memory", fn);
-    for (int b = 0; b < npairs; b++) tiles[b] = cdiv(src_lengths_host[b], ICP_TILE);
-    rc = upload_offsets(e.tile_off, tiles, npairs, (int)nts, fn, s);
-    free(tiles);
+    int nts = 0;
+    rc = upload_tile_offsets(e.tile_off, src_lengths_host, npairs, ICP_TILE, fn, &nts, s);
     if (rc) return rc;
     k_icp_setup<<<npairs, ICP_TILE, 0, s>>>(src, e.src_off, T_init, T_out, fitness_out, rmse_out, iters_out, e.st);
     BUF_LAUNCH_CHECK();
     const float r2 = max_dist * max_dist;                 // buf_grid_query's threshold
     if (method == ICP_P2P)
-        return icp_rounds<ICP_P2P>(e, g, src, tgt, nullptr, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
+        return icp_rounds<ICP_P2P>(e, g, src, tgt, nullptr, (int)nt, npairs, nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
                                    fitness_out, rmse_out, iters_out, nn_out, s);
     if (method == ICP_P2L)
-        return icp_rounds<ICP_P2L>(e, g, src, tgt, tgt_normals, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
+        return icp_rounds<ICP_P2L>(e, g, src, tgt, tgt_normals, (int)nt, npairs, nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
                                    fitness_out, rmse_out, iters_out, nn_out, s);
-    return icp_rounds<ICP_GICP>(e, g, src, tgt, tgt_normals, (int)nt, npairs, (int)nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
+    return icp_rounds<ICP_GICP>(e, g, src, tgt, tgt_normals, (int)nt, npairs, nts, r2, max_iteration, rel_fitness, rel_rmse, T_out,
                                 fitness_out, rmse_out, iters_out, nn_out, s, IcpGicpArgs{ src_normals, 1.0 - epsilon });
 }
 

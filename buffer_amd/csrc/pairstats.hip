@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(PS_TILE) k_pair_correspond(const CellGrid* __r
             v[8] = uy * uy; v[9] = uy * uz; v[10] = uz * uz;
         }
     }
-    icp_block_sum<PS_NV>(v, part, slab + (size_t)tile * PS_STRIDE);
+    tile_sum<PS_NV, ICP_WAVES>(v, part, slab + (size_t)tile * PS_STRIDE);
 }
 
 __global__ void __launch_bounds__(WAVE) k_pair_reduce(const int* __restrict__ tile_off, const double* __restrict__ slab,

@@ -20,9 +20,9 @@
 //                  ascending columns), the weighted Kabsch pose and its inlier count over all live rows
 //   k_sc2_refine   one workgroup per pair: the winner, the refits over its inliers, every output
 // All fp64 without FMA (the library is built with -ffp-contract=off); no atomics and a fixed order in every sum: a pair's outputs
-// are the same bits alone, in any batch and across runs.  sc2_kabsch_rotation restates icp_kabsch_rotation (icp.hip) for the
-// reason fgr.hip gives for its solver.
+// are the same bits alone, in any batch and across runs.
 #include "common.h"
+#include "pose_math.h"
 
 #define SC2_W 256
 #define SC2_WAVES (SC2_W / WAVE)
@@ -60,12 +60,6 @@ __device__ __forceinline__ double sc2_wave_max(double v)
     return v;
 }
 
-__device__ __forceinline__ double sc2_wave_sum(double v)
-{
-    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-
 __device__ __forceinline__ unsigned long long sc2_wave_max_u64(unsigned long long v)
 {
     for (int d = WAVE / 2; d > 0; d >>= 1) {
@@ -84,81 +78,11 @@ __device__ __forceinline__ double sc2_residual(const double* T, const double* r)
     return sqrt((x * x + y * y) + z * z);
 }
 
-// ---- fp64 Kabsch (icp_kabsch_rotation restated) ------------------------------------------------
-__device__ static void sc2_cross(const double* a, const double* b, double* c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ static bool sc2_unit(double* a)
-{
-    const double l = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-    if (!(l > 0.0) || !isfinite(l)) return false;
-    a[0] /= l; a[1] /= l; a[2] /= l;
-    return true;
-}
-
-// R maximising tr(R H) over proper rotations, H = sum w (p - pc)(q - qc)^T: one-sided Jacobi on the columns of H, singular values
-// descending, R = [V1 V2 V1xV2][U1 U2 U1xU2]^T (the det-corrected SVD solution).  false (R untouched) for H = 0 or a non-finite H.
-__device__ static bool sc2_kabsch_rotation(const double* H, double* R)
-{
-    double A[3][3], V[3][3];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            if (!isfinite(H[3 * r + c])) return false;
-            A[r][c] = H[3 * r + c]; V[r][c] = r == c ? 1.0 : 0.0;
-        }
-    for (int sweep = 0; sweep < 40; sweep++) {
-        bool rotated = false;
-        for (int pr = 0; pr < 3; pr++) {
-            const int i = pr == 2 ? 1 : 0, j = pr == 0 ? 1 : 2;
-            const double al = (A[0][i] * A[0][i] + A[1][i] * A[1][i]) + A[2][i] * A[2][i];
-            const double be = (A[0][j] * A[0][j] + A[1][j] * A[1][j]) + A[2][j] * A[2][j];
-            const double ga = (A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j];
-            if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
-            const double ze = (be - al) / (2.0 * ga);
-            const double t = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
-            const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-            for (int k = 0; k < 3; k++) {
-                const double ai = A[k][i], aj = A[k][j];
-                A[k][i] = cs * ai - sn * aj; A[k][j] = sn * ai + cs * aj;
-                const double vi = V[k][i], vj = V[k][j];
-                V[k][i] = cs * vi - sn * vj; V[k][j] = sn * vi + cs * vj;
-            }
-            rotated = true;
-        }
-        if (!rotated) break;
-    }
-    double s[3];
-    int o[3] = { 0, 1, 2 };
-    for (int c = 0; c < 3; c++) s[c] = (A[0][c] * A[0][c] + A[1][c] * A[1][c]) + A[2][c] * A[2][c];
-    for (int a = 0; a < 2; a++)                                  // descending, stable
-        for (int c = 0; c < 2 - a; c++)
-            if (s[o[c]] < s[o[c + 1]]) { const int t = o[c]; o[c] = o[c + 1]; o[c + 1] = t; }
-    double U1[3], U2[3], U3[3], V1[3], V2[3], V3[3];
-    for (int k = 0; k < 3; k++) { U1[k] = A[k][o[0]]; U2[k] = A[k][o[1]]; V1[k] = V[k][o[0]]; V2[k] = V[k][o[1]]; }
-    if (!sc2_unit(U1)) return false;
-    const double pj = (U1[0] * U2[0] + U1[1] * U2[1]) + U1[2] * U2[2];
-    for (int k = 0; k < 3; k++) U2[k] -= pj * U1[k];
-    if (!(s[o[1]] > 1e-28 * s[o[0]]) || !sc2_unit(U2)) {        // rank 1: any completion
-        const double e[3] = { fabs(U1[0]) < 0.6 ? 1.0 : 0.0, fabs(U1[0]) < 0.6 ? 0.0 : 1.0, 0.0 };
-        sc2_cross(U1, e, U2);
-        sc2_unit(U2);
-    }
-    sc2_cross(U1, U2, U3);
-    sc2_cross(V1, V2, V3);
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) R[3 * r + c] = (V1[r] * U1[c] + V2[r] * U2[c]) + V3[r] * U3[c];
-    return true;
-}
-
-// T = [R | cq - R cp] from the centroids and H (the identity rotation where sc2_kabsch_rotation finds none)
+// T = [R | cq - R cp] from the centroids and H (the identity rotation where H is zero or not finite)
 __device__ static void sc2_pose(const double* cp, const double* cq, const double* H, double* T)
 {
     double R[9] = { 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0 };
-    sc2_kabsch_rotation(H, R);
+    if (finite9(H)) kabsch_rotation(H, R);
     for (int k = 0; k < 9; k++) T[k] = R[k];
     for (int r = 0; r < 3; r++) T[9 + r] = cq[r] - ((R[3 * r] * cp[0] + R[3 * r + 1] * cp[1]) + R[3 * r + 2] * cp[2]);
 }
@@ -440,18 +364,18 @@ __global__ void __launch_bounds__(WAVE) k_sc2_hyp(const Sc2Pair* __restrict__ mp
     // weighted Kabsch on the normalised weights
     double part = 0.0;
     for (int a = lane; a < m; a += WAVE) part += sw[cur][a];
-    const double wsum = sc2_wave_sum(part);
+    const double wsum = wave_sum(part);
     double cen[6], H[9];
     for (int c = 0; c < 6; c++) {
         part = 0.0;
         for (int a = lane; a < m; a += WAVE) part += (sw[cur][a] / wsum) * sr[a][c];
-        cen[c] = sc2_wave_sum(part);
+        cen[c] = wave_sum(part);
     }
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) {
             part = 0.0;
             for (int a = lane; a < m; a += WAVE) part += (sw[cur][a] / wsum) * ((sr[a][r] - cen[r]) * (sr[a][3 + c] - cen[3 + c]));
-            H[3 * r + c] = sc2_wave_sum(part);
+            H[3 * r + c] = wave_sum(part);
         }
     double T[12];
     sc2_pose(cen, cen + 3, H, T);                                // (every lane holds the same sums: the same pose in every lane)
@@ -468,20 +392,33 @@ __global__ void __launch_bounds__(WAVE) k_sc2_hyp(const Sc2Pair* __restrict__ mp
     }
 }
 
-// sum of NV values per lane over the workgroup in a fixed tree, the result in every thread (red: SC2_WAVES * NV doubles)
-template <int NV>
-__device__ __forceinline__ void sc2_block_sum(double (&v)[NV], double* red)
+// The refits of T over its inliers (live rows with a residual below inlier_thr) by one workgroup of SC2_W: sums, centroids, H,
+// pose, until the count stops growing or falls below 3.  Block-uniform: every thread holds the same T and counts.
+__device__ static void sc2_refit(const double* __restrict__ R, const int* __restrict__ L, int n, double inlier_thr, int refine_iterations,
+                                 double* red, double* T)
 {
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = sc2_wave_sum(v[k]);
-    __syncthreads();                                             // red may still be read from the last use
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; k++) red[wave * NV + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = (red[k] + red[NV + k]) + (red[2 * NV + k] + red[3 * NV + k]);
+    const int tid = threadIdx.x;
+    int last = 0;
+    for (int it = 0; it < refine_iterations; it++) {
+        double s[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+        for (int i = tid; i < n; i += SC2_W)
+            if (L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr) {
+                for (int c = 0; c < 6; c++) s[c] += R[6 * (size_t)i + c];
+                s[6] += 1.0;
+            }
+        tile_sum<7, SC2_WAVES>(s, red);
+        const int count = (int)s[6];
+        if ((it > 0 && count <= last) || count < 3) break;
+        last = count;
+        double cen[6], H[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+        for (int c = 0; c < 6; c++) cen[c] = s[c] / s[6];
+        for (int i = tid; i < n; i += SC2_W)
+            if (L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr)
+                for (int r = 0; r < 3; r++)
+                    for (int c = 0; c < 3; c++) H[3 * r + c] += (R[6 * (size_t)i + r] - cen[r]) * (R[6 * (size_t)i + 3 + c] - cen[3 + c]);
+        tile_sum<9, SC2_WAVES>(H, red);
+        sc2_pose(cen, cen + 3, H, T);
+    }
 }
 
 // one workgroup per pair
@@ -512,7 +449,7 @@ __global__ void __launch_bounds__(SC2_W) k_sc2_refine(const Sc2Pair* __restrict_
             best = key > best ? key : best;
         }
     }
-    sc2_block_sum<2>(cnt2, red);
+    tile_sum<2, SC2_WAVES>(cnt2, red);
     best = sc2_wave_max_u64(best);
     if (tid % WAVE == 0) wbest[tid / WAVE] = best;
     __syncthreads();
@@ -525,34 +462,14 @@ __global__ void __launch_bounds__(SC2_W) k_sc2_refine(const Sc2Pair* __restrict_
 
     double T[12];
     for (int k = 0; k < 12; k++) T[k] = ok ? hypT[12 * ((size_t)b * max_seeds + win) + k] : ((k == 0 || k == 4 || k == 8) ? 1.0 : 0.0);
-    int last = 0;
-    for (int it = 0; ok && it < refine_iterations; it++) {       // (block-uniform: every thread holds the same T and counts)
-        double s[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-        for (int i = tid; i < n; i += SC2_W)
-            if (L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr) {
-                for (int c = 0; c < 6; c++) s[c] += R[6 * (size_t)i + c];
-                s[6] += 1.0;
-            }
-        sc2_block_sum<7>(s, red);
-        const int count = (int)s[6];
-        if ((it > 0 && count <= last) || count < 3) break;
-        last = count;
-        double cen[6], H[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-        for (int c = 0; c < 6; c++) cen[c] = s[c] / s[6];
-        for (int i = tid; i < n; i += SC2_W)
-            if (L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr)
-                for (int r = 0; r < 3; r++)
-                    for (int c = 0; c < 3; c++) H[3 * r + c] += (R[6 * (size_t)i + r] - cen[r]) * (R[6 * (size_t)i + 3 + c] - cen[3 + c]);
-        sc2_block_sum<9>(H, red);
-        sc2_pose(cen, cen + 3, H, T);
-    }
+    if (ok) sc2_refit(R, L, n, inlier_thr, refine_iterations, red, T);
     double fin[1] = { 0.0 };
     for (int i = tid; i < n; i += SC2_W) {
         const bool in = ok && L[i] && sc2_residual(T, R + 6 * (size_t)i) < inlier_thr;
         fin[0] += in ? 1.0 : 0.0;
         if (inliers_out) inliers_out[(size_t)P.corr_off + i] = in ? 1 : 0;
     }
-    sc2_block_sum<1>(fin, red);
+    tile_sum<1, SC2_WAVES>(fin, red);
     for (int k = tid; k < max_seeds; k += SC2_W) {
         if (seeds_out) seeds_out[(size_t)b * max_seeds + k] = sd[k];
         if (hyp_counts_out) hyp_counts_out[(size_t)b * max_seeds + k] = hc[k];
@@ -637,20 +554,14 @@ extern "C" int buf_sc2_batched(const float* src, const int* src_lengths_host, co
     BUF_REQUIRE(power_iterations >= 0 && power_iterations <= 1000 && refine_iterations >= 0, BUF_EINVAL,
                 "buf_sc2_batched: power_iterations=%d (0..1000) refine_iterations=%d", power_iterations, refine_iterations);
     if (npairs == 0) return BUF_OK;
-    BUF_REQUIRE(src_lengths_host && tgt_lengths_host && corr_lengths_host, BUF_EINVAL, "buf_sc2_batched: null host array");
-    BUF_REQUIRE(T_out && info_out, BUF_EINVAL, "buf_sc2_batched: null output");
-    long long nst = 0, ntt = 0, nct = 0, maxn = 0, maxS = 1;
-    for (int b = 0; b < npairs; b++) {
-        BUF_REQUIRE(src_lengths_host[b] >= 0 && tgt_lengths_host[b] >= 0 && corr_lengths_host[b] >= 0, BUF_EINVAL,
-                    "buf_sc2_batched: negative length in pair %d", b);
+    long long nct, maxn, maxS = 1;
+    const int brc = corr_batch_check("buf_sc2_batched", src, src_lengths_host, tgt, tgt_lengths_host, corr, corr_lengths_host, npairs, true,
+                                     T_out, info_out, nct, maxn, [&](int b) {
         BUF_REQUIRE(corr_lengths_host[b] <= BUF_SC2_MAX_ROWS, BUF_EINVAL, "buf_sc2_batched: %d correspondences in pair %d (at most %d)",
                     corr_lengths_host[b], b, BUF_SC2_MAX_ROWS);
-        nst += src_lengths_host[b]; ntt += tgt_lengths_host[b]; nct += corr_lengths_host[b];
-        maxn = corr_lengths_host[b] > maxn ? corr_lengths_host[b] : maxn;
-    }
-    BUF_REQUIRE(nst < 0x7fffffffLL && ntt < 0x7fffffffLL && nct < 0x7fffffffLL, BUF_EINVAL,
-                "buf_sc2_batched: %lld / %lld points, %lld correspondences (int32 indices)", nst, ntt, nct);
-    BUF_REQUIRE((nst == 0 || src) && (ntt == 0 || tgt) && (nct == 0 || corr), BUF_EINVAL, "buf_sc2_batched: null input");
+        return (int)BUF_OK;
+    });
+    if (brc) return brc;
     long long rows, words, counts;
     sc2_sizes(corr_lengths_host, npairs, max_seeds, rows, words, counts);
     const size_t need = buf_sc2_ws_bytes(corr_lengths_host, npairs, max_seeds);

@@ -19,8 +19,9 @@
 //                  one term per occupied voxel; xor butterfly inside the wave, fixed sum over the 4 waves: ONE record per tile
 //   k_vg_update    one wave per pair: records summed in a fixed order, fitness / rmse, N2's stopping rules, the 6x6 solve, T <- dT T
 // All fp64 without FMA, every sum in a fixed order, no float atomics: a pair's result has the same bits alone, in any batch and on
-// reruns.  The small solvers of icp.hip are restated here (vg_*) so that icp.hip's kernels keep their instructions.
+// reruns.  The fp64 routines are those of pose_math.h; the update kernel body, the round loop and the tile offsets are icp.hip's.
 #include "common.h"
+#include "pose_math.h"
 #include <limits.h>
 #include <math.h>
 
@@ -33,6 +34,10 @@
 struct VgCloud { int mn[3]; int dim[3]; long long table_off; };     // dim = 0: no voxel
 struct VgStatus { int error; int nrows; };
 struct VgState { double prev_fit, prev_rmse; int done; int pad; };
+struct VgRec {                                                       // (the record as pose_update of icp.hip reads it)
+    static constexpr int NV = VG_NV, STRIDE = VG_NV, CNT = 0, FIT = 1, D2 = 2, H = 3, G = 24, MIN_CNT = 6;
+    static constexpr bool KABSCH = false;
+};
 
 // voxel coordinates of a point; false for a point the map leaves out
 __device__ __forceinline__ bool vg_voxel_of(double x, double y, double z, double voxel, int (&k)[3])
@@ -41,16 +46,6 @@ __device__ __forceinline__ bool vg_voxel_of(double x, double y, double z, double
     if (!(fabs(kx) < VG_KLIM) || !(fabs(ky) < VG_KLIM) || !(fabs(kz) < VG_KLIM)) return false;     // (NaN and inf fail the comparison)
     k[0] = (int)kx; k[1] = (int)ky; k[2] = (int)kz;
     return true;
-}
-
-// row j of a normal array in fp64 under N2's rule; zero (C = I) for a null array or an unusable row
-__device__ __forceinline__ void vg_normal(const float* __restrict__ normals, size_t j, double (&n)[3])
-{
-    n[0] = 0.0; n[1] = 0.0; n[2] = 0.0;
-    if (!normals) return;
-    const double a = normals[3 * j], b = normals[3 * j + 1], c = normals[3 * j + 2];
-    const double l2 = (a * a + b * b) + c * c;
-    if (fabs(l2 - 1.0) < 1e-3) { n[0] = a; n[1] = b; n[2] = c; }
 }
 
 // ------------------------------------------------------------------------------------------ map build
@@ -153,7 +148,7 @@ __global__ void __launch_bounds__(256) k_vg_emit(const float* __restrict__ pts, 
     for (int t = p; t < e; t++) {                                    // input order
         const size_t i = (size_t)sorted[t];
         double nn[3];
-        vg_normal(normals, i, nn);
+        unit_normal_or_zero(normals, i, nn);
         int k = 0;
 #pragma unroll
         for (int r = 0; r < 3; r++) {
@@ -344,32 +339,6 @@ __global__ void __launch_bounds__(WAVE) k_vg_setup(int npairs, const double* __r
     fitness[b] = 0.0; rmse[b] = 0.0; iters[b] = 0;
 }
 
-__device__ static void vg_cross(const double* a, const double* b, double* c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// sum of v over the VG_TILE threads of the workgroup; the result lands in out[0..VG_NV)
-__device__ __forceinline__ void vg_block_sum(double (&v)[VG_NV], double (*part)[VG_NV], double* __restrict__ out)
-{
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-#pragma unroll
-    for (int k = 0; k < VG_NV; k++)
-        for (int d = WAVE / 2; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < VG_NV; k++) part[w][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < VG_NV) {
-        double s = part[0][threadIdx.x];
-        for (int j = 1; j < VG_WAVES; j++) s += part[j][threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-}
-
 // offset j of a neighbourhood of K voxels.  1: the voxel; 7: the voxel, +x, -x, +y, -y, +z, -z; 27: dz outermost, dx innermost, -1 0 +1
 template <int K> __device__ __forceinline__ constexpr int vg_off(int j, int axis)
 {
@@ -425,7 +394,7 @@ __global__ void __launch_bounds__(VG_TILE) k_vg_terms(const VgCloud* __restrict_
         if (row_out) row_out[i] = own >= 0 ? own - row_off[pc] : -1;
         if (nhit > 0) {
             double ns[3], m[3], RR[6];
-            vg_normal(src_normals, i, ns);
+            unit_normal_or_zero(src_normals, i, ns);
 #pragma unroll
             for (int r = 0; r < 3; r++) m[r] = (Tb[4 * r] * ns[0] + Tb[4 * r + 1] * ns[1]) + Tb[4 * r + 2] * ns[2];
             {
@@ -450,81 +419,28 @@ __global__ void __launch_bounds__(VG_TILE) k_vg_terms(const VgCloud* __restrict_
 #pragma unroll
                         for (int c = r; c < 3; c++) { S[k] = (row[3 + k] + RR[k]) - (w * m[r]) * m[c]; k++; }
                 }
-                // Mm = S^-1 by cofactors (S is symmetric positive definite: both terms are, for eps > 0)
-                const double c00 = S[3] * S[5] - S[4] * S[4], c01 = S[2] * S[4] - S[1] * S[5], c02 = S[1] * S[4] - S[2] * S[3];
-                const double c11 = S[0] * S[5] - S[2] * S[2], c12 = S[1] * S[2] - S[0] * S[4], c22 = S[0] * S[3] - S[1] * S[1];
-                const double idet = 1.0 / ((S[0] * c00 + S[1] * c01) + S[2] * c02);
-                const double Mm[3][3] = { { c00 * idet, c01 * idet, c02 * idet }, { c01 * idet, c11 * idet, c12 * idet },
-                                          { c02 * idet, c12 * idet, c22 * idet } };
-                // with A = -[p]x: row r of M A is p x (row r of M), A^T x is p x x
-                double MA[3][3], col[3], AtMA[3][3], Md[3], AtMd[3];
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-                    vg_cross(p, Mm[r], MA[r]);
-                    Md[r] = (Mm[r][0] * dx + Mm[r][1] * dy) + Mm[r][2] * dz;
-                }
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const double mc[3] = { MA[0][c], MA[1][c], MA[2][c] };
-                    vg_cross(p, mc, col);
-#pragma unroll
-                    for (int r = 0; r < 3; r++) AtMA[r][c] = col[r];
-                }
-                vg_cross(p, Md, AtMd);
+                GicpTerm gt;
+                gicp_term(S, p, dx, dy, dz, gt);
                 v[0] += 1.0;
                 v[2] += (dx * dx + dy * dy) + dz * dz;
                 int k = 3;
 #pragma unroll
                 for (int r = 0; r < 3; r++) {                          // rows 0..2 of H: [A^T M A | A^T M], A^T M = (M A)^T
 #pragma unroll
-                    for (int c = r; c < 3; c++) v[k++] += Nv * AtMA[r][c];
+                    for (int c = r; c < 3; c++) v[k++] += Nv * gt.AtMA[r][c];
 #pragma unroll
-                    for (int c = 0; c < 3; c++) v[k++] += Nv * MA[c][r];
+                    for (int c = 0; c < 3; c++) v[k++] += Nv * gt.MA[c][r];
                 }
 #pragma unroll
                 for (int r = 0; r < 3; r++)                            // rows 3..5: M
 #pragma unroll
-                    for (int c = r; c < 3; c++) v[k++] += Nv * Mm[r][c];
+                    for (int c = r; c < 3; c++) v[k++] += Nv * gt.Mm[r][c];
 #pragma unroll
-                for (int r = 0; r < 3; r++) { v[24 + r] += Nv * AtMd[r]; v[27 + r] += Nv * Md[r]; }
+                for (int r = 0; r < 3; r++) { v[24 + r] += Nv * gt.AtMd[r]; v[27 + r] += Nv * gt.Md[r]; }
             }
         }
     }
-    vg_block_sum(v, part, slab + (size_t)tile * VG_NV);
-}
-
-// H x = -g by Cholesky (LDL^T without pivoting); false when the system is not positive definite
-__device__ static bool vg_solve6(const double* up, const double* g, double (&x)[6])
-{
-    double A[6][6], L[6][6], D[6], y[6];
-    int k = 0;
-    for (int r = 0; r < 6; r++)
-        for (int c = r; c < 6; c++) { A[r][c] = up[k]; A[c][r] = up[k]; k++; }
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-        for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
-        if (!(d > 0.0) || !isfinite(d)) return false;
-        D[j] = d;
-        L[j][j] = 1.0;
-        for (int i = j + 1; i < 6; i++) {
-            double e = A[i][j];
-            for (int m = 0; m < j; m++) e -= L[i][m] * L[j][m] * D[m];
-            L[i][j] = e / d;
-        }
-    }
-    for (int i = 0; i < 6; i++) {
-        double e = -g[i];
-        for (int m = 0; m < i; m++) e -= L[i][m] * y[m];
-        y[i] = e;
-    }
-    for (int i = 5; i >= 0; i--) {
-        double e = y[i] / D[i];
-        for (int m = i + 1; m < 6; m++) e -= L[m][i] * x[m];
-        x[i] = e;
-    }
-    for (int i = 0; i < 6; i++)
-        if (!isfinite(x[i])) return false;
-    return true;
+    tile_sum<VG_NV, VG_WAVES>(v, part, slab + (size_t)tile * VG_NV);
 }
 
 __global__ void __launch_bounds__(WAVE) k_vg_update(const int* __restrict__ src_off, const int* __restrict__ tile_off,
@@ -533,63 +449,7 @@ __global__ void __launch_bounds__(WAVE) k_vg_update(const int* __restrict__ src_
                                                   double* __restrict__ rmse_out, int* __restrict__ iters, VgState* __restrict__ st,
                                                   int* __restrict__ active)
 {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    if (st[b].done) return;
-    const int t0 = tile_off[b], t1 = tile_off[b + 1];
-    double v[VG_NV];
-#pragma unroll
-    for (int k = 0; k < VG_NV; k++) v[k] = 0.0;
-    for (int t = t0 + lane; t < t1; t += WAVE) {
-        const double* rec = slab + (size_t)t * VG_NV;
-#pragma unroll
-        for (int k = 0; k < VG_NV; k++) v[k] += rec[k];
-    }
-#pragma unroll
-    for (int k = 0; k < VG_NV; k++)
-        for (int d = WAVE / 2; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
-    if (lane != 0) return;
-    const int n = src_off[b + 1] - src_off[b];
-    const double cnt = v[0];
-    const double fit = n > 0 ? v[1] / (double)n : 0.0;
-    const double rmse = cnt > 0.0 ? sqrt(v[2] / cnt) : 0.0;
-    fitness[b] = fit;
-    rmse_out[b] = rmse;
-    VgState s = st[b];
-    const int it = iters[b];
-    bool stop;
-    double dT[4][4];
-    if (it > 0 && fabs(s.prev_fit - fit) < rel_fitness && fabs(s.prev_rmse - rmse) < rel_rmse) stop = true;   // converged
-    else if (it >= max_iteration) stop = true;
-    else if (cnt < 6.0) stop = true;                                                                         // too few terms
-    else {
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) dT[r][c] = r == c ? 1.0 : 0.0;
-        double x[6];
-        stop = !vg_solve6(v + 3, v + 24, x);
-        if (!stop) {
-            // R = Rz(x2) Ry(x1) Rx(x0), t = x3..5 (N2's dT)
-            const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-            dT[0][0] = cg * cb; dT[0][1] = cg * sb * sa - sg * ca; dT[0][2] = cg * sb * ca + sg * sa;
-            dT[1][0] = sg * cb; dT[1][1] = sg * sb * sa + cg * ca; dT[1][2] = sg * sb * ca - cg * sa;
-            dT[2][0] = -sb;     dT[2][1] = cb * sa;                dT[2][2] = cb * ca;
-            dT[0][3] = x[3]; dT[1][3] = x[4]; dT[2][3] = x[5];
-        }
-    }
-    if (!stop) {
-        double* Tb = T + 16 * (size_t)b;
-        double Tn[16];
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++)
-                Tn[4 * r + c] = ((dT[r][0] * Tb[c] + dT[r][1] * Tb[4 + c]) + dT[r][2] * Tb[8 + c]) + dT[r][3] * Tb[12 + c];
-        for (int k = 0; k < 16; k++) Tb[k] = Tn[k];
-        iters[b] = it + 1;
-        s.prev_fit = fit;
-        s.prev_rmse = rmse;
-        if (active) atomicAdd(active, 1);
-    } else {
-        s.done = 1;
-    }
-    st[b] = s;
+    pose_update<VgRec>(src_off, tile_off, slab, max_iteration, rel_fitness, rel_rmse, T, fitness, rmse_out, iters, st, active);
 }
 
 struct VgWs { int* src_off; int* tile_off; int* pair_cloud; VgState* st; double* slab; int* active; };
@@ -619,25 +479,13 @@ static int vg_rounds(const VgWs& e, const buf_voxel_map_t* map, const float* src
                      int max_iteration, double rel_fitness, double rel_rmse, double* T_out, double* fitness_out, double* rmse_out,
                      int* iters_out, int* row_out, hipStream_t s)
 {
-    for (int r = 0; r <= max_iteration; r++) {
-        const bool probe = (r & 7) == 7 && r < max_iteration;
-        if (probe) BUF_CHECK_HIP(hipMemsetAsync(e.active, 0, sizeof(int), s));
+    const auto terms = [&] {
         if (ntiles > 0)
             k_vg_terms<K><<<ntiles, VG_TILE, 0, s>>>((const VgCloud*)map->clouds, map->table, map->rows, map->row_off, e.pair_cloud, src,
                                                      src_normals, e.src_off, e.tile_off, npairs, map->voxel, 1.0 - map->epsilon, T_out,
                                                      e.st, row_out, e.slab);
-        k_vg_update<<<npairs, WAVE, 0, s>>>(e.src_off, e.tile_off, e.slab, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
-                                            iters_out, e.st, probe ? e.active : nullptr);
-        if (probe) {
-            BUF_LAUNCH_CHECK();
-            int left = 0;
-            BUF_CHECK_HIP(hipMemcpyAsync(&left, e.active, sizeof(int), hipMemcpyDeviceToHost, s));
-            BUF_CHECK_HIP(hipStreamSynchronize(s));
-            if (left == 0) break;
-        }
-    }
-    BUF_LAUNCH_CHECK();
-    return BUF_OK;
+    };
+    return pose_rounds(e, terms, k_vg_update, npairs, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out, iters_out, s);
 }
 
 extern "C" int buf_vgicp_batched(const buf_voxel_map_t* map, const float* src, const float* src_normals, const int* src_lengths_host,
@@ -654,13 +502,12 @@ extern "C" int buf_vgicp_batched(const buf_voxel_map_t* map, const float* src, c
     BUF_REQUIRE(src_lengths_host, BUF_EINVAL, "buf_vgicp_batched: null lengths");
     BUF_REQUIRE(pair_cloud_host || npairs <= map->nclouds, BUF_EINVAL, "buf_vgicp_batched: %d pairs but %d map clouds and no pair_cloud",
                 npairs, map->nclouds);
-    long long ns = 0, nts = 0;
+    long long ns = 0;
     for (int b = 0; b < npairs; b++) {
         BUF_REQUIRE(src_lengths_host[b] >= 0, BUF_EINVAL, "buf_vgicp_batched: negative length in pair %d", b);
         BUF_REQUIRE(!pair_cloud_host || (pair_cloud_host[b] >= 0 && pair_cloud_host[b] < map->nclouds), BUF_EINVAL,
                     "buf_vgicp_batched: pair_cloud[%d]=%d outside the map's %d clouds", b, pair_cloud_host ? pair_cloud_host[b] : 0, map->nclouds);
         ns += src_lengths_host[b];
-        nts += cdiv(src_lengths_host[b], VG_TILE);
     }
     BUF_REQUIRE(ns < 0x7fffffffLL, BUF_EINVAL, "buf_vgicp_batched: %lld points (int32 indices)", ns);
     BUF_REQUIRE(ns == 0 || src, BUF_EINVAL, "buf_vgicp_batched: null src");
@@ -672,11 +519,8 @@ extern "C" int buf_vgicp_batched(const buf_voxel_map_t* map, const float* src, c
     const VgWs e = carve_vgicp(w, (int)ns, npairs);
     int rc = upload_offsets(e.src_off, src_lengths_host, npairs, (int)ns, "buf_vgicp_batched", s);
     if (rc) return rc;
-    int* tiles = (int*)malloc(sizeof(int) * (size_t)npairs);
-    BUF_REQUIRE(tiles, BUF_EINVAL, "buf_vgicp_batched: out of host memory");
-    for (int b = 0; b < npairs; b++) tiles[b] = cdiv(src_lengths_host[b], VG_TILE);
-    rc = upload_offsets(e.tile_off, tiles, npairs, (int)nts, "buf_vgicp_batched", s);
-    free(tiles);
+    int nts = 0;
+    rc = upload_tile_offsets(e.tile_off, src_lengths_host, npairs, VG_TILE, "buf_vgicp_batched", &nts, s);
     if (rc) return rc;
     for (int b0 = 0; b0 < npairs; b0 += OFFS_PER_LAUNCH) {               // the pairs' clouds, by value in the argument block
         OffsetChunk c;
@@ -688,11 +532,11 @@ extern "C" int buf_vgicp_batched(const buf_voxel_map_t* map, const float* src, c
     k_vg_setup<<<cdiv(npairs, WAVE), WAVE, 0, s>>>(npairs, T_init, T_out, fitness_out, rmse_out, iters_out, e.st);
     BUF_LAUNCH_CHECK();
     if (neighbors == 1)
-        return vg_rounds<1>(e, map, src, src_normals, npairs, (int)nts, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
+        return vg_rounds<1>(e, map, src, src_normals, npairs, nts, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
                             iters_out, row_out, s);
     if (neighbors == 7)
-        return vg_rounds<7>(e, map, src, src_normals, npairs, (int)nts, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
+        return vg_rounds<7>(e, map, src, src_normals, npairs, nts, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
                             iters_out, row_out, s);
-    return vg_rounds<27>(e, map, src, src_normals, npairs, (int)nts, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
+    return vg_rounds<27>(e, map, src, src_normals, npairs, nts, max_iteration, rel_fitness, rel_rmse, T_out, fitness_out, rmse_out,
                          iters_out, row_out, s);
 }

@@ -534,6 +534,12 @@ def post_refine(T_init, src, tgt, thr=0.10, iters=20):
     return T, info
 
 
+def _icp_outputs(B, dev):
+    """The (T f64[B,4,4], fitness f64[B], rmse f64[B], iterations int32[B]) outputs of icp_batched / vgicp_batched."""
+    return (torch.empty((B, 4, 4), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
+            torch.empty((B,), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev))
+
+
 ICP_METHODS = {'point_to_point': 0, 'point_to_plane': 1, 'generalized': 2}     # BUF_ICP_POINT_TO_POINT / _POINT_TO_PLANE / _GENERALIZED
 
 
@@ -550,10 +556,7 @@ def icp_batched(src, src_lengths, tgt, tgt_lengths, max_dist, T_init, method='po
     m = ICP_METHODS[method]
     nrm = _dev(tgt_normals, torch.float32, "icp_batched.tgt_normals") if tgt_normals is not None else None
     T_init = _dev(T_init, torch.float64, "icp_batched.T_init").reshape(B, 4, 4)
-    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
-    fit = torch.empty((B,), dtype=torch.float64, device=dev)
-    rmse = torch.empty((B,), dtype=torch.float64, device=dev)
-    iters = torch.empty((B,), dtype=torch.int32, device=dev)
+    T, fit, rmse, iters = _icp_outputs(B, dev)
     nn = torch.empty((max(int(src.shape[0]), 1),), dtype=torch.int32, device=dev) if correspondences else None
     nbytes = max(L.buf_icp_ws_bytes(int(src.shape[0]), int(tgt.shape[0]), max(B, 1), m), 1)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -648,10 +651,7 @@ def vgicp_batched(src, src_lengths, vmap, T_init, neighbors=7, src_normals=None,
         if pc.shape[0] != B:
             raise ValueError(f"vgicp_batched: {B} pairs but {pc.shape[0]} pair_cloud entries")
     T_init = _dev(T_init, torch.float64, "vgicp_batched.T_init").reshape(B, 4, 4)
-    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
-    fit = torch.empty((B,), dtype=torch.float64, device=dev)
-    rmse = torch.empty((B,), dtype=torch.float64, device=dev)
-    iters = torch.empty((B,), dtype=torch.int32, device=dev)
+    T, fit, rmse, iters = _icp_outputs(B, dev)
     row = torch.empty((max(ns, 1),), dtype=torch.int32, device=dev) if rows else None
     nbytes = max(L.buf_vgicp_ws_bytes(ns, max(B, 1)), 1)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -703,6 +703,23 @@ def iss_keypoints(points, nbr_sal, nbr_nms, gamma_21=0.975, gamma_32=0.975, min_
     return mask, sal, eig
 
 
+def _corr_batch(fn, src, src_lengths, tgt, tgt_lengths, corr, corr_lengths):
+    """The (src, tgt, corr) batch of fgr_batched / sc2_batched / clique_batched (fn) on the device and its host lengths, checked against
+    each other -> (src, tgt, corr, sl, tl, cl, B, dev)."""
+    src, tgt = _dev(src, torch.float32, f"{fn}.src"), _dev(tgt, torch.float32, f"{fn}.tgt")
+    corr = _dev(corr, torch.int32, f"{fn}.corr")
+    sl, tl, cl = _host_i32(src_lengths), _host_i32(tgt_lengths), _host_i32(corr_lengths)
+    B = int(sl.shape[0])
+    if tl.shape[0] != B or cl.shape[0] != B:
+        raise ValueError(f"{fn}: {B} source lengths but {tl.shape[0]} target and {cl.shape[0]} correspondence lengths")
+    for name, t, ln, w in (("src", src, sl, 3), ("tgt", tgt, tl, 3), ("corr", corr, cl, 2)):
+        if t.dim() != 2 or t.shape[1] != w:
+            raise ValueError(f"{fn}: {name} {tuple(t.shape)} is not [N,{w}]")
+        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
+            raise ValueError(f"{fn}: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    return src, tgt, corr, sl, tl, cl, B, src.device
+
+
 FGR_STATUS = ('NOTHING', 'OK', 'FAILED')                                                       # BUF_FGR_* of buffer_hip.h
 FGR_MAX_TUPLES = 4096
 
@@ -716,17 +733,7 @@ def fgr_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, seeds=No
     updates applied), rows int32[B,3*max_tuples,2] or None: the kept correspondences, tail -1, weights f64[B,3*max_tuples] or None:
     their line-process weights at the last linearisation, tail NaN), all on the device; two launches, nothing read back."""
     L = _lib.lib()
-    src, tgt = _dev(src, torch.float32, "fgr_batched.src"), _dev(tgt, torch.float32, "fgr_batched.tgt")
-    corr = _dev(corr, torch.int32, "fgr_batched.corr")
-    sl, tl, cl = _host_i32(src_lengths), _host_i32(tgt_lengths), _host_i32(corr_lengths)
-    B, dev = int(sl.shape[0]), src.device
-    if tl.shape[0] != B or cl.shape[0] != B:
-        raise ValueError(f"fgr_batched: {B} source lengths but {tl.shape[0]} target and {cl.shape[0]} correspondence lengths")
-    for name, t, ln, w in (("src", src, sl, 3), ("tgt", tgt, tl, 3), ("corr", corr, cl, 2)):
-        if t.dim() != 2 or t.shape[1] != w:
-            raise ValueError(f"fgr_batched: {name} {tuple(t.shape)} is not [N,{w}]")
-        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
-            raise ValueError(f"fgr_batched: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    src, tgt, corr, sl, tl, cl, B, dev = _corr_batch("fgr_batched", src, src_lengths, tgt, tgt_lengths, corr, corr_lengths)
     if not (1 <= int(max_tuples) <= FGR_MAX_TUPLES):
         raise ValueError(f"fgr_batched: max_tuples={max_tuples} (1..{FGR_MAX_TUPLES})")
     sd = np.arange(B, dtype=np.uint64) if seeds is None else np.array([int(s) & _MASK64 for s in seeds], dtype=np.uint64).reshape(-1)
@@ -760,17 +767,7 @@ def sc2_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, d_thr, i
     int32[B,max_seeds] (by rank, tail -1), counts int32[max_seeds * sum n] (pair b's block at max_seeds * its first row, rank r at
     + r n_b), inlier_mask uint8[sum n])."""
     L = _lib.lib()
-    src, tgt = _dev(src, torch.float32, "sc2_batched.src"), _dev(tgt, torch.float32, "sc2_batched.tgt")
-    corr = _dev(corr, torch.int32, "sc2_batched.corr")
-    sl, tl, cl = _host_i32(src_lengths), _host_i32(tgt_lengths), _host_i32(corr_lengths)
-    B, dev = int(sl.shape[0]), src.device
-    if tl.shape[0] != B or cl.shape[0] != B:
-        raise ValueError(f"sc2_batched: {B} source lengths but {tl.shape[0]} target and {cl.shape[0]} correspondence lengths")
-    for name, t, ln, w in (("src", src, sl, 3), ("tgt", tgt, tl, 3), ("corr", corr, cl, 2)):
-        if t.dim() != 2 or t.shape[1] != w:
-            raise ValueError(f"sc2_batched: {name} {tuple(t.shape)} is not [N,{w}]")
-        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
-            raise ValueError(f"sc2_batched: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    src, tgt, corr, sl, tl, cl, B, dev = _corr_batch("sc2_batched", src, src_lengths, tgt, tgt_lengths, corr, corr_lengths)
     if B and int(cl.max()) > SC2_MAX_ROWS:
         raise ValueError(f"sc2_batched: {int(cl.max())} correspondences in one pair (at most {SC2_MAX_ROWS})")
     if not (1 <= int(max_seeds) <= SC2_MAX_SEEDS) or not (3 <= int(k1) <= SC2_MAX_K1):
@@ -808,17 +805,7 @@ def clique_batched(src, src_lengths, tgt, tgt_lengths, corr, corr_lengths, d_thr
     (-1 on dead rows), sizes int32[B,max_seeds] (by rank, tail -1), members int32[B,max_members] (rows, tail -1), weights
     f64[B, max_members (max_members - 1) / 2] (NaN tail), pose0 f64[B,12] (R and t before the refit), inlier_mask uint8[sum n])."""
     L = _lib.lib()
-    src, tgt = _dev(src, torch.float32, "clique_batched.src"), _dev(tgt, torch.float32, "clique_batched.tgt")
-    corr = _dev(corr, torch.int32, "clique_batched.corr")
-    sl, tl, cl = _host_i32(src_lengths), _host_i32(tgt_lengths), _host_i32(corr_lengths)
-    B, dev = int(sl.shape[0]), src.device
-    if tl.shape[0] != B or cl.shape[0] != B:
-        raise ValueError(f"clique_batched: {B} source lengths but {tl.shape[0]} target and {cl.shape[0]} correspondence lengths")
-    for name, t, ln, w in (("src", src, sl, 3), ("tgt", tgt, tl, 3), ("corr", corr, cl, 2)):
-        if t.dim() != 2 or t.shape[1] != w:
-            raise ValueError(f"clique_batched: {name} {tuple(t.shape)} is not [N,{w}]")
-        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
-            raise ValueError(f"clique_batched: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    src, tgt, corr, sl, tl, cl, B, dev = _corr_batch("clique_batched", src, src_lengths, tgt, tgt_lengths, corr, corr_lengths)
     if B and int(cl.max()) > SC2_MAX_ROWS:
         raise ValueError(f"clique_batched: {int(cl.max())} correspondences in one pair (at most {SC2_MAX_ROWS})")
     if not (1 <= int(max_seeds) <= CLIQUE_MAX_SEEDS) or not (3 <= int(max_members) <= CLIQUE_MAX_MEMBERS):
