@@ -35,6 +35,7 @@
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "iss.hip"
+#include "match.hip"
 #include "fgr.hip"
 #include "sc2.hip"
 #include "clique.hip"

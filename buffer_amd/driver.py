@@ -183,6 +183,10 @@ def add_descriptor_args(ap):
                     help='the points --descriptor fpfh matches.  all: every point of the second-level clouds (default).  iss: their ISS '
                          'keypoints (buffer_amd/keypoints.py: salient radius 6 voxels, non-max radius 4 voxels); the summary carries '
                          '"keypoints" = the detector, the two radii and the mean keypoints per cloud')
+    ap.add_argument('--match-ratio', type=float, default=None, metavar='R',
+                    help="--descriptor fpfh: Lowe's ratio test on top of the mutual filter, 0 < R < 1 -- a match stays only if its nearest "
+                         'descriptor distance is at most R times the second nearest (ops.feature_match; default: no ratio test); the '
+                         'summary carries "match_ratio"')
 
 
 def parse_with_preset(ap, argv, driver_name):
@@ -197,6 +201,10 @@ def parse_with_preset(ap, argv, driver_name):
         ap.error(f'--estimator {a.estimator} chooses the estimator of the classical baseline: it needs --descriptor fpfh')
     if a.keypoints != 'all' and a.descriptor != 'fpfh':
         ap.error(f'--keypoints {a.keypoints} chooses the detector of the classical baseline: it needs --descriptor fpfh')
+    if a.match_ratio is not None and a.descriptor != 'fpfh':
+        ap.error(f'--match-ratio {a.match_ratio} thins the matches of the classical baseline: it needs --descriptor fpfh')
+    if a.match_ratio is not None and not (0.0 < a.match_ratio < 1.0):
+        ap.error(f'--match-ratio {a.match_ratio}: must be in (0, 1)')
     if a.refine == 'voxelized' and a.descriptor == 'fpfh':
         ap.error('--refine voxelized refines the learned path: not available with --descriptor fpfh')
     if a.refine_voxel is not None and not (0.0 < a.refine_voxel < float('inf')):
@@ -220,7 +228,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     --stage-metrics (per scene with scene_of = one scene name per pair; stage_metrics.json under log_root, pair ids = labels).
     --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor" and
     "estimator", --estimator choosing its RANSAC, its Fast Global Registration, its SC2-PCR or its max-clique + TLS estimator, which adds
-    "certified_pairs"; --keypoints iss makes it match ISS keypoints instead of every point and adds "keypoints").
+    "certified_pairs"; --keypoints iss makes it match ISS keypoints instead of every point and adds "keypoints"; --match-ratio R
+    adds Lowe's ratio test to its matching and "match_ratio").
     --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
     unrefined poses.
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
@@ -232,7 +241,7 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
         from .fpfh import FpfhRegistration
         iss = getattr(a, 'keypoints', 'all') == 'iss'
         pipe = FpfhRegistration(cfg, dev, estimator=getattr(a, 'estimator', 'ransac'),     # no neighbourhood limits: nothing to calibrate
-                                keypoints='iss' if iss else None)
+                                keypoints='iss' if iss else None, match_ratio=getattr(a, 'match_ratio', None))
     else:
         pipe = BufferPipeline(cfg, dev)
     if a.limits and not fpfh:
@@ -286,6 +295,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
             out['estimator'] = getattr(a, 'estimator', 'ransac')
             if certified is not None:
                 out['certified_pairs'] = int((certified == 1).sum())
+            if pipe.match_ratio is not None:
+                out['match_ratio'] = pipe.match_ratio
             if pipe.keypoints == 'iss':                      # (the mean is this rank's: the counts stay on the rank that found them)
                 kc = np.concatenate(pipe.keypoint_counts_log or [np.zeros(0, np.int64)])
                 out['keypoints'] = dict(detector='iss', salient_radius=pipe.iss_salient_radius, non_max_radius=pipe.iss_non_max_radius,

@@ -5,6 +5,8 @@ from its published form (include/buffer_hip.h, N6; parity unpinned).
 
     compute_fpfh        descriptors of one or several stacked clouds: one cell grid, one radius query, one launch pair
     match               (mutual) 1-NN matches of two descriptor sets through ops.knn (d = 33: the exact fp32 scan)
+    match_batch         the same matches for all pairs of a batch in ONE ops.feature_match call (csrc/match.hip), optionally thinned
+                        by Lowe's ratio test
     FpfhRegistration    estimator='ransac' (default), 'fgr' (buffer_amd/fgr.py: one batched Fast Global Registration call per
                         batch on the concatenated match lists), 'sc2' (buffer_amd/sc2.py: one batched SC2-PCR call per batch on the
                         same lists) or 'clique' (buffer_amd/clique.py: one batched max-clique + TLS call per batch on the same
@@ -59,6 +61,24 @@ def match(fa, fb, mutual=True):
     return torch.stack([i, ab[i]], 1).to(torch.int32).contiguous()
 
 
+def match_batch(F, lens, mutual=True, ratio=None):
+    """F f64|f32[sum lens,d] (device): the descriptors of the clouds src, tgt, src, tgt, ... stacked as register_batch stacks them,
+    lens int[2B] -> (corr int32[m,2] (device), corr_lengths int32[B] (host)): per pair the rows of match(F_src, F_tgt, mutual), the
+    pairs concatenated -- one ops.feature_match call, one read-back (the counts).  ratio (None or in (0, 1)): Lowe's ratio test on the
+    forward matches as well (nearest squared distance <= ratio^2 x the second nearest)."""
+    lens = np.asarray(lens, np.int32).reshape(-1)
+    if lens.shape[0] % 2:
+        raise ValueError(f'match_batch: {lens.shape[0]} clouds do not pair up')
+    F = F.float()
+    if int(lens.sum()) != int(F.shape[0]):
+        raise ValueError(f'match_batch: lengths sum to {int(lens.sum())}, F holds {int(F.shape[0])} rows')
+    parts = torch.split(F, [int(n) for n in lens]) if len(lens) else ()
+    empty = F[:0]
+    fa, fb = torch.cat(parts[0::2] or (empty,)), torch.cat(parts[1::2] or (empty,))
+    corr, cl, _, _ = ops.feature_match(fa, lens[0::2], fb, lens[1::2], mutual=mutual, ratio=ratio)
+    return corr, cl
+
+
 def ransac_on_matches(src, tgt, corr, nhyp, seed, max_dist, edge_similarity):
     """src f32[ns,3], tgt f32[nt,3], corr int32[m,2] (device) -> pose f32[4,4] src -> tgt: ops.ransac_kabsch over the matched rows
     (the kernel indexes both clouds with one list, so the rows are gathered first); fewer than 3 matches give the identity."""
@@ -85,11 +105,17 @@ class FpfhRegistration:
     salient / non-max radii iss_salient_factor / iss_non_max_factor * cfg.voxel_size_0 (open3d's 6 x / 4 x resolution heuristic, the
     voxel size standing in for the resolution), iss_gamma = (gamma_21, gamma_32) and iss_min_neighbors; FPFH is still computed for
     every point, matching and the estimator then run on the keypoints' rows alone (fewer than 3 matches: the identity, as ever).
-    `keypoint_counts` keeps the last call's keypoints per cloud (int64[2B], host); refine_batch goes on refining on the dense clouds."""
+    `keypoint_counts` keeps the last call's keypoints per cloud (int64[2B], host); refine_batch goes on refining on the dense clouds.
+    match_ratio=None (default): the mutual matches as they are.  match_ratio=R in (0, 1): Lowe's ratio test on top (match_batch).  Either
+    way all pairs of a batch are matched in one match_batch call, with the rows match() gives pair by pair."""
 
     def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac',
-                 keypoints=None, iss_salient_factor=6.0, iss_non_max_factor=4.0, iss_gamma=(0.975, 0.975), iss_min_neighbors=5):
+                 keypoints=None, iss_salient_factor=6.0, iss_non_max_factor=4.0, iss_gamma=(0.975, 0.975), iss_min_neighbors=5,
+                 match_ratio=None):
         self.cfg, self.device = cfg, torch.device(device)
+        if match_ratio is not None and not (0.0 < float(match_ratio) < 1.0):
+            raise ValueError(f'FpfhRegistration: match_ratio={match_ratio} (None, or in (0, 1))')
+        self.match_ratio = None if match_ratio is None else float(match_ratio)
         if keypoints not in KEYPOINTS:
             raise ValueError(f'FpfhRegistration: unknown keypoints {keypoints!r} (one of {KEYPOINTS})')
         self.keypoints = keypoints
@@ -140,12 +166,13 @@ class FpfhRegistration:
             return self._sc2_batch(pts, lens, off, F)
         if self.estimator == 'clique':
             return self._clique_batch(pts, lens, off, F)
+        corr, cl = match_batch(F, lens, True, self.match_ratio)
+        co = np.concatenate([[0], np.cumsum(cl)])
         out = []
         for b in range(B):
             s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
-            corr = match(F[s0:t0], F[t0:t1], True)
-            out.append(ransac_on_matches(pts[s0:t0], pts[t0:t1], corr, self.cfg.ransac_hypotheses, seeds[b], self.max_dist,
-                                         self.edge_similarity))
+            out.append(ransac_on_matches(pts[s0:t0], pts[t0:t1], corr[int(co[b]):int(co[b + 1])], self.cfg.ransac_hypotheses, seeds[b],
+                                         self.max_dist, self.edge_similarity))
         return out
 
     def _iss_sets(self, pts, nrm, lens):
@@ -161,42 +188,38 @@ class FpfhRegistration:
         self.keypoint_counts_log.append(counts)
         return pts[idx].contiguous(), counts.astype(np.int32), F[idx].contiguous()
 
-    @staticmethod
-    def _batch_matches(pts, lens, off, F):
-        """the matches of every pair (pair by pair, as the RANSAC path matches) and the two sides stacked apart (the pairs' clouds
-        alternate in pts: src, tgt, src, ...) -> (src, tgt, list of corr)"""
+    def _batch_matches(self, pts, lens, off, F):
+        """the matches of every pair (one match_batch call: the rows the RANSAC path gets) and the two sides stacked apart (the pairs'
+        clouds alternate in pts: src, tgt, src, ...) -> (src, tgt, corr int32[m,2], corr_lengths int32[B] on the host)"""
         B = len(lens) // 2
-        corrs = []
-        for b in range(B):
-            s0, t0, t1 = int(off[2 * b]), int(off[2 * b + 1]), int(off[2 * b + 2])
-            corrs.append(match(F[s0:t0], F[t0:t1], True))
+        corr, cl = match_batch(F, lens, True, self.match_ratio)
         src = torch.cat([pts[int(off[2 * b]):int(off[2 * b + 1])] for b in range(B)])
         tgt = torch.cat([pts[int(off[2 * b + 1]):int(off[2 * b + 2])] for b in range(B)])
-        return src, tgt, corrs
+        return src, tgt, corr, cl
 
     def _sc2_batch(self, pts, lens, off, F):
         """the matches of every pair, then ONE sc2_batched call for the batch"""
         from . import sc2
-        src, tgt, corrs = self._batch_matches(pts, lens, off, F)
-        res = sc2.sc2_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
+        src, tgt, corr, cl = self._batch_matches(pts, lens, off, F)
+        res = sc2.sc2_registration(src, lens[0::2], tgt, lens[1::2], corr, cl,
                                    d_thr=self.max_dist, inlier_thr=self.max_dist, nms_radius=0.0)
         return list(res['poses'].float().unbind(0))
 
     def _clique_batch(self, pts, lens, off, F):
         """the matches of every pair, then ONE clique_batched call for the batch; keeps its `certified` and `bound`"""
         from . import clique
-        src, tgt, corrs = self._batch_matches(pts, lens, off, F)
-        res = clique.clique_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
+        src, tgt, corr, cl = self._batch_matches(pts, lens, off, F)
+        res = clique.clique_registration(src, lens[0::2], tgt, lens[1::2], corr, cl,
                                          d_thr=self.max_dist, tim_thr=self.max_dist, t_thr=self.max_dist / 2, inlier_thr=self.max_dist)
         self.certified, self.bound = res['certified'], res['bound']
         self.certified_log.append(self.certified)
         return list(res['poses'].float().unbind(0))
 
     def _fgr_batch(self, pts, lens, off, F, seeds):
-        """the matches of every pair (pair by pair, as the RANSAC path matches), then ONE fgr_batched call for the batch"""
+        """the matches of every pair, then ONE fgr_batched call for the batch"""
         from . import fgr
-        src, tgt, corrs = self._batch_matches(pts, lens, off, F)
-        res = fgr.fast_global_registration(src, lens[0::2], tgt, lens[1::2], torch.cat(corrs), [int(c.shape[0]) for c in corrs],
+        src, tgt, corr, cl = self._batch_matches(pts, lens, off, F)
+        res = fgr.fast_global_registration(src, lens[0::2], tgt, lens[1::2], corr, cl,
                                            seeds=[int(s) & ops._MASK64 for s in seeds], maximum_correspondence_distance=self.max_dist,
                                            delta_absolute=True)
         return list(res['poses'].float().unbind(0))

@@ -720,7 +720,41 @@ def _corr_batch(fn, src, src_lengths, tgt, tgt_lengths, corr, corr_lengths):
     return src, tgt, corr, sl, tl, cl, B, src.device
 
 
-FGR_STATUS = ('NOTHING', 'OK', 'FAILED')                                                       # BUF_FGR_* of buffer_hip.h
+def feature_match(fa, a_lengths, fb, b_lengths, mutual=True, ratio=None, return_nn=False):
+    """buf_feature_match (N12 of buffer_hip.h): the descriptor matches of the pairs stacked in fa f32|f64[sum a_lengths,d] /
+    fb [sum b_lengths,d] (device, 1 <= d <= 64; float64 is cast to fp32, as fpfh.match casts), pair p owning a_lengths[p] / b_lengths[p]
+    consecutive rows -> (corr int32[m,2] (device: (row of A_p, its nearest row of B_p), pair-local, ascending inside a pair, the pairs
+    stacked: what _corr_batch takes), corr_lengths int32[P] (host), nn, ssd).  mutual: only the rows that are each other's nearest.
+    ratio (None = off, else in (0, 1)): only the rows whose nearest squared distance is at most ratio^2 times the second nearest (Lowe's
+    test, forward direction).  return_nn: nn int32[sum a_lengths,2] / ssd f32[sum a_lengths,2] = every row's nearest and second-nearest
+    row (-1) and squared distance (+inf), else None.  Exact and deterministic; one read-back, the counts."""
+    L = _lib.lib()
+    fa, fb = _dev(fa, torch.float32, "feature_match.fa"), _dev(fb, torch.float32, "feature_match.fb")
+    al, bl = _host_i32(a_lengths), _host_i32(b_lengths)
+    P = int(al.shape[0])
+    if bl.shape[0] != P:
+        raise ValueError(f"feature_match: {P} lengths of A but {bl.shape[0]} of B")
+    if fa.dim() != 2 or fb.dim() != 2 or fa.shape[1] != fb.shape[1]:
+        raise ValueError(f"feature_match: fa {tuple(fa.shape)} and fb {tuple(fb.shape)} are not [N,d] with one d")
+    for name, t, ln in (("fa", fa, al), ("fb", fb, bl)):
+        if (ln < 0).any() or int(ln.astype(np.int64).sum()) != int(t.shape[0]):
+            raise ValueError(f"feature_match: {name} lengths sum to {int(ln.astype(np.int64).sum())}, {name} holds {int(t.shape[0])} rows")
+    if ratio is not None and not (0.0 < float(ratio) < 1.0):
+        raise ValueError(f"feature_match: ratio={ratio} (None, or in (0, 1))")
+    na, nb, d, dev = int(fa.shape[0]), int(fb.shape[0]), int(fa.shape[1]), fa.device
+    corr = torch.empty((na, 2), dtype=torch.int32, device=dev)
+    counts = torch.zeros((P,), dtype=torch.int32, device=dev)
+    nn = torch.empty((na, 2), dtype=torch.int32, device=dev) if return_nn else None
+    ssd = torch.empty((na, 2), dtype=torch.float32, device=dev) if return_nn else None
+    nbytes = max(L.buf_feature_match_ws_bytes(na, nb, P), 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.buf_feature_match(_ptr(fa), _hptr(al), _ptr(fb), _hptr(bl), P, d, int(bool(mutual)), 0.0 if ratio is None else float(ratio),
+                              _ptr(corr), _ptr(counts), _ptr(nn), _ptr(ssd), _ptr(ws), nbytes, _stream()), "buf_feature_match")
+    cl = counts.cpu().numpy()
+    return corr[:int(cl.sum())], cl, nn, ssd
+
+
+FGR_STATUS = ('NOTHING', 'OK', 'FAILED')                                                      # BUF_FGR_* of buffer_hip.h
 FGR_MAX_TUPLES = 4096
 
 

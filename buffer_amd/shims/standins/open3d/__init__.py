@@ -11,7 +11,8 @@ libbuffer_hip.so (open3d==0.13.0 is a pip dependency of the reference, README.md
                                         registration_icp (KITTI/dataset.py:104-107) -> device nearest-neighbour ICP,
                                         point-to-point and (TransformationEstimationPointToPlane) point-to-plane,
                                         Feature, compute_fpfh_feature (KDTreeSearchParamHybrid) -> buf_fpfh,
-                                        registration_ransac_based_on_feature_matching -> fpfh.match + buf_ransac_kabsch
+                                        registration_ransac_based_on_feature_matching -> fpfh.match + buf_ransac_kabsch,
+                                        correspondences_from_features -> ops.feature_match (buf_feature_match)
 
 It is installed behind any real open3d (buffer_amd.shims.install appends this directory to sys.path), so an
 environment that has the real package keeps using it.  Point data crosses as numpy arrays exactly as with open3d;

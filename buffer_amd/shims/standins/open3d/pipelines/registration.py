@@ -144,6 +144,32 @@ def compute_fpfh_feature(input, search_param):
     return Feature(fpfh.compute_fpfh(pts, nrm, search_param.radius, search_param.max_nn).cpu().numpy().T)
 
 
+def correspondences_from_features(source_features, target_features, mutual_filter=False, mutual_consistency_ratio=0.1):
+    """open3d correspondences_from_features -> int32[m,2] rows (source column, its nearest target column), ascending by source column:
+    the 1-NN matches of the source features among the target features (ops.feature_match, csrc/match.hip: exact fp32 squared
+    distances, ties to the lower column; restated, unpinned: include/buffer_hip.h N12 is the specification).  mutual_filter keeps the
+    matches that are nearest in both directions -- unless they are fewer than mutual_consistency_ratio x the forward matches: then, as
+    in open3d, the forward matches are returned."""
+    import torch
+    from buffer_amd import ops
+    if source_features.dimension() != target_features.dimension():
+        raise ValueError("open3d stand-in: the two feature sets differ in dimension")
+    na, nb = source_features.num(), target_features.num()
+    if na == 0 or nb == 0:
+        return np.zeros((0, 2), np.int32)
+    dev = _device()
+    fa = torch.from_numpy(np.ascontiguousarray(source_features.data.T)).to(dev)
+    fb = torch.from_numpy(np.ascontiguousarray(target_features.data.T)).to(dev)
+    mutual, _, nn, _ = ops.feature_match(fa, [na], fb, [nb], mutual=True, return_nn=True)      # nn: the forward matches, filter or not
+    nn = nn[:, 0].cpu().numpy()
+    rows = np.flatnonzero(nn >= 0)
+    forward = np.stack([rows, nn[rows]], 1).astype(np.int32)
+    if not mutual_filter:
+        return forward
+    mutual = mutual.cpu().numpy()
+    return mutual if len(mutual) >= float(mutual_consistency_ratio) * len(forward) else forward
+
+
 def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
                                                   max_correspondence_distance, estimation_method=None, ransac_n=3, checkers=(),
                                                   criteria=None, seed=0):

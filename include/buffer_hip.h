@@ -661,6 +661,40 @@ int     buf_iss_keypoints(const float* pts, int n, const int* nbr_sal, int k_sal
                           double gamma_21, double gamma_32, int min_neighbors, double* saliency_out /* f64[n] */,
                           double* eig_out /* f64[n,3], nullable */, unsigned char* mask_out /* u8[n] */, void* stream);
 
+/* N12  Batched descriptor matching with a mutual and a ratio filter: exact, ragged, `pairs` pairs per call.  One scan launch for both
+ * directions of all pairs, two small launches for the filters and the ordered output; no atomics; the host reads nothing back.
+ * Pair p owns a_lengths_host[p] / b_lengths_host[p] consecutive rows of fa / fb (f32[., d], device, 1 <= d <= 64): A_p and B_p.
+ * Distance of rows (i, j): ssd = the fp32 sum over the dimensions IN ORDER of (a_c - b_c)^2, formed with __fsub_rn, __fmul_rn and
+ *   __fadd_rn, never contracted (the operations of buf_knn): ssd(i, j) is the same bits as ssd(j, i), and a zero dimension appended to
+ *   both rows changes nothing.
+ * Ranking: by the 64-bit key (float bits of ssd) << 32 | row index, as buf_knn ranks.  The nearest row has the smallest key, the
+ *   second nearest the second smallest; ties go to the lower row.
+ * Forward match of row i of A_p: its nearest row j of B_p.
+ * mutual != 0: the row stays only if i is the nearest row of A_p to j.
+ * 0 < ratio < 1: the row stays only if ssd1 <= r2 * ssd2, with ssd1 / ssd2 the FORWARD nearest and second-nearest sums (the ratio test
+ *   looks at the forward direction only: at the neighbours in B_p of the row of A_p, never at those of j in A_p),
+ *   r2 = (float)((double)ratio * ratio) and the product one __fmul_rn: the squared form of Lowe's test, no square root.  Without a
+ *   second neighbour (one row in B_p, or one ranked row) the test passes.  ratio <= 0 switches the test off.
+ * Non-finite rows: a row with a NaN or infinite component is matched by nobody and matches nobody, on either side (it is not ranked).
+ *   Finite rows whose sum overflows to +inf are ranked like any other.
+ * Output: the surviving (i, j), pair-local indices, ascending i inside a pair, the pairs stacked in pair order, in corr_out
+ *   (int32[na_total, 2] capacity; the rows past the total are not written); counts_out[p] (device int32[pairs]) = the rows of pair p.
+ *   nn_out (nullable) int32[na_total, 2] = per row of A its nearest and second-nearest row of B_p, -1 where there is none; ssd_out
+ *   (nullable) f32[na_total, 2] = their sums, +inf where there is none.  Both cover the forward direction, filters or not.
+ * A pair's rows are the same bits alone, in any batch and at every launch.  With mutual != 0, the ratio off and finite inputs they are
+ * the rows of two buf_knn calls at k = 1 and the comparison idx_ba[idx_ab[i]] == i.
+ * BUF_EINVAL before any device work for pairs < 0, d outside 1..64, ratio >= 1 or NaN, a null host array or counts_out, a negative
+ * length, 2^31 - 1 rows or more on a side, a null input that has rows, a null corr_out when A has rows, and a workspace that is null
+ * or smaller than buf_feature_match_ws_bytes(na_total, nb_total, pairs).  pairs == 0 succeeds and touches nothing; without a row in
+ * A the counts are zeroed and nothing else is touched; a pair with an empty side yields no rows. */
+size_t  buf_feature_match_ws_bytes(long long na_total, long long nb_total, int pairs);
+int     buf_feature_match(const float* fa, const int* a_lengths_host, const float* fb, const int* b_lengths_host,
+                          int pairs, int d, int mutual, float ratio,
+                          int* corr_out /* int32[na_total,2] capacity */, int* counts_out /* device int32[pairs] */,
+                          int* nn_out /* optional int32[na_total,2]: nearest, second (-1 if none) */,
+                          float* ssd_out /* optional f32[na_total,2], +inf if none */,
+                          void* ws, size_t ws_bytes, void* stream);
+
 /* N7  Fast Global Registration (Zhou, Park, Koltun, ECCV 2016; open3d registration_fast_based_on_feature_matching restated from
  * its published form, parity unpinned: this text is the specification).  B pairs per call, two launches, nothing read back.
  * Pair b owns src_lengths_host[b] / tgt_lengths_host[b] consecutive rows of src / tgt (f32[.,3], device) and corr_lengths_host[b]
