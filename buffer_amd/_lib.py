@@ -96,6 +96,9 @@ _SIGNATURES = {
     "buf_cylindrical_net_w25_flags": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "buf_cylindrical_net_split_safe_w25": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "buf_winograd_f25_tile_weights": (_i, [_vp, _i, _i, _vp]),
+    "buf_cylindrical_net_w25t": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "buf_cylindrical_net_split_safe_w25t": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "buf_cyl_row6_tile_taps": (_i, [_vp, _i, _i, _vp]),
     "buf_cylindrical_net_wg_supports": (_i, [_vp, _vp]),
     "buf_cylindrical_net_wg_flags": (_i, [_vp, _vp, _vp]),
     "buf_cylindrical_net_split_safe": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -28,10 +28,11 @@
 #include "convnet_w24p.hip"
 #include "convnet_w24a.hip"
 #include "convnet_w25.hip"
+#include "convnet_w25t.hip"
 #include "costnet.hip"
 #include "costnet_w24.hip"
 #include "costnet_w24b.hip"
-#include "cnn_launch.hip"             // the host side of the nine kernels above: behind all of them
+#include "cnn_launch.hip"             // the host side of the ten kernels above: behind all of them
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "iss.hip"

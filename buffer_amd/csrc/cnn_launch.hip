@@ -1,6 +1,6 @@
 // The host side of the fused fp32 CNN kernels, behind all of them in the translation unit: one launch path per family.
 //
-//   descriptor net   k_cyl_net_wg | _w24 | _w24k | _w24p | _w24a | _w25 (csrc/convnet_w*.hip) and their _rerun twins take the same
+//   descriptor net   k_cyl_net_wg | _w24 | _w24k | _w24p | _w24a | _w25 | _w25t (csrc/convnet_w*.hip) and their _rerun twins take the same
 //                    arguments (CylWgParams): cyl_check states the rules of a stack once, cyl_prepare fills the parameters and picks
 //                    the kernel (cyl_kernel_for), cyl_launch launches it -- the plain kernel, or with P.only_if its masked twin.
 //   cost net         k_cost_net | _w24 | _w24b (csrc/costnet*.hip) differ in their parameter struct: cost_net_prepare / cost_net_launch
@@ -23,12 +23,14 @@ typedef void (*CylKernelFn)(const float*, CylWgParams, float*);
 struct CylKernel { CylKernelFn plain, rerun; LdsGrant grant, grant_rerun; };
 static CylKernel cyl_wg = { k_cyl_net_wg, k_cyl_net_wg_rerun }, cyl_w24 = { k_cyl_net_w24, k_cyl_net_w24_rerun },
                  cyl_w24k = { k_cyl_net_w24k, k_cyl_net_w24k_rerun }, cyl_w24p = { k_cyl_net_w24p, k_cyl_net_w24p_rerun },
-                 cyl_w24a = { k_cyl_net_w24a, k_cyl_net_w24a_rerun }, cyl_w25 = { k_cyl_net_w25, k_cyl_net_w25_rerun };
+                 cyl_w24a = { k_cyl_net_w24a, k_cyl_net_w24a_rerun }, cyl_w25 = { k_cyl_net_w25, k_cyl_net_w25_rerun },
+                 cyl_w25t = { k_cyl_net_w25t, k_cyl_net_w25t_rerun };
 
-// The kernel of a stack (rules checked): with sets of the layers' own k_cyl_net_w25 / k_cyl_net_w24a, whatever the sets hold; else by
-// the relu words -- none above 1: k_cyl_net_wg; bit 1 only: k_cyl_net_w24; bit 2 somewhere: the form's kernel.
-static CylKernel& cyl_kernel_for(const int* relu, int form, bool sets24, bool sets25)
+// The kernel of a stack (rules checked): with sets of the layers' own k_cyl_net_w25t / k_cyl_net_w25 / k_cyl_net_w24a, whatever the sets
+// hold; else by the relu words -- none above 1: k_cyl_net_wg; bit 1 only: k_cyl_net_w24; bit 2 somewhere: the form's kernel.
+static CylKernel& cyl_kernel_for(const int* relu, int form, bool sets24, bool sets25, bool taps)
 {
+    if (taps) return cyl_w25t;
     if (sets25) return cyl_w25;
     if (sets24) return cyl_w24a;
     bool flagged = false, ksplit = false;
@@ -88,8 +90,13 @@ static int w24_check_flags(const int* cin, const int* cout, const int* relu)
 //                  and has 64 or 32 output channels; wt25_host[l] (buf_winograd_f25_tile_weights) on a layer with 64 or 32 output
 //                  channels and Cin % 16 == 0, whatever F(2x4) flag or set it carries (the F(2x5) set wins; the layer's other buffers
 //                  are not read).  A 32-output layer with either set leaves the zero words alone: wider layers may follow it.
-static int cyl_check(const int* cin, const int* cout, const int* relu, const float* const* wt24_host, const float* const* wt25_host, const char* who)
+//                  taps_host[l] (buf_cyl_row6_tile_taps; entry points that take the array only) goes on a layer with 128 output channels.
+static int cyl_check(const int* cin, const int* cout, const int* relu, const float* const* wt24_host, const float* const* wt25_host, const char* who,
+                     const float* const* taps_host = nullptr)
 {
+    for (int l = 0; taps_host && l < WG_LAYERS; l++)
+        BUF_REQUIRE(!taps_host[l] || cout[l] == 128, BUF_EINVAL, "%s: layer %d (%d -> %d) takes no row-6 tap set (128 output channels)", who, l,
+                    cin[l], cout[l]);
     if (!wt24_host && !wt25_host) {
         if (int rc = wg_check_widths(cin, cout)) return rc;
         for (int l = 0; l < WG_LAYERS; l++)
@@ -147,19 +154,21 @@ extern "C" int buf_cylindrical_net_w25_flags(const int* cin_host, const int* cou
 }
 
 // Everything an entry point checks about its stack, the kernel's parameters and the kernel, without a device call.  The set arrays as
-// for cyl_check: an entry point that takes one has checked that it is there.
+// for cyl_check: an entry point that takes one has checked that it is there.  taps_host, order: of the entry points of k_cyl_net_w25t.
 static int cyl_prepare(const float* const* wt_host, const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
-                       const float* const* wt24_host, const float* const* wt25_host, int form, const char* who, CylWgParams& P, CylKernel*& K)
+                       const float* const* wt24_host, const float* const* wt25_host, int form, const char* who, CylWgParams& P, CylKernel*& K,
+                       const float* const* taps_host = nullptr, int order = 0)
 {
     BUF_REQUIRE(wt_host && bias_host && cin_host && cout_host && relu_host, BUF_EINVAL, "%s: null argument", who);
     for (int l = 0; l < WG_LAYERS; l++) {
         P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
         P.cin[l] = cin_host[l]; P.cout[l] = cout_host[l]; P.relu[l] = relu_host[l];
+        P.taps[l] = nullptr;
         BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "%s: null weights for layer %d", who, l);
     }
-    if (int rc = cyl_check(P.cin, P.cout, P.relu, wt24_host, wt25_host, who)) return rc;
+    if (int rc = cyl_check(P.cin, P.cout, P.relu, wt24_host, wt25_host, who, taps_host)) return rc;
     P.only_if = nullptr;
-    K = &cyl_kernel_for(P.relu, form, wt24_host != nullptr, wt25_host != nullptr);
+    K = &cyl_kernel_for(P.relu, form, wt24_host != nullptr, wt25_host != nullptr, taps_host != nullptr);
     if (K == &cyl_wg) return BUF_OK;                      // takes the buffers and the words as they are
     for (int l = 0; l < WG_LAYERS; l++) {
         if (wt25_host && wt25_host[l]) { P.wt[l] = wt25_host[l]; P.relu[l] = (P.relu[l] & 1) | W25_FLAG; }
@@ -167,6 +176,10 @@ static int cyl_prepare(const float* const* wt_host, const float* const* bias_hos
         else if (P.relu[l] & W24K_FLAG) P.wt[l] += WG_BLOCKS * P.cout[l] * P.cin[l];       // behind the layer's F(2x2) set
         else if (wt24_host && wt24_host[l]) { P.wt[l] = wt24_host[l]; P.relu[l] |= W24K_FLAG; }
         P.relu[l] &= ~WG_F24_FLAG;
+        if (taps_host && P.cout[l] == 128) {              // (the words of k_cyl_net_w25t: csrc/convnet_w25t.hip)
+            if (taps_host[l]) { P.taps[l] = taps_host[l]; P.relu[l] |= W25T_TAPS; }
+            if (order & BUF_CYL_ROW6_FIRST) P.relu[l] |= W25T_FIRST;
+        }
     }
     return BUF_OK;
 }
@@ -247,17 +260,19 @@ extern "C" int buf_cylindrical_net_wg(const float* x, int npatch, const float* c
     return buf_cylindrical_net_wg_form(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, BUF_CYL_FORM_DEFAULT, y, stream);
 }
 
-// The same through k_cyl_net_w25 (wt25_host: per layer an optional F(2x5) set) or, without wt25_host, k_cyl_net_w24a
+// The same through k_cyl_net_w25 (wt25_host: per layer an optional F(2x5) set) or, without wt25_host, k_cyl_net_w24a; w25t: through
+// k_cyl_net_w25t with taps_host (per layer an optional row-6 tap set) and order
 static int cyl_net_own_sets(const char* who, const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
                             const int* cout_host, const int* relu_host, const float* const* wt24_host, const float* const* wt25_host, bool w25, float* y,
-                            void* stream)
+                            void* stream, bool w25t = false, const float* const* taps_host = nullptr, int order = 0)
 {
     BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "%s: npatch=%d", who, npatch);
+    BUF_REQUIRE(!w25t || (order & ~BUF_CYL_ROW6_FIRST) == 0, BUF_EINVAL, "%s: order=%d (0, or BUF_CYL_ROW6_FIRST = 1)", who, order);
     if (npatch == 0) return BUF_OK;
-    BUF_REQUIRE(x && y && wt24_host && (wt25_host || !w25), BUF_EINVAL, "%s: null argument", who);
+    BUF_REQUIRE(x && y && wt24_host && (wt25_host || !w25) && (taps_host || !w25t), BUF_EINVAL, "%s: null argument", who);
     CylWgParams P;
     CylKernel* K;
-    if (int rc = cyl_prepare(wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, BUF_CYL_FORM_DEFAULT, who, P, K)) return rc;
+    if (int rc = cyl_prepare(wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, BUF_CYL_FORM_DEFAULT, who, P, K, taps_host, order)) return rc;
     return cyl_launch(*K, x, npatch, P, y, stream);
 }
 
@@ -274,6 +289,16 @@ extern "C" int buf_cylindrical_net_w25(const float* x, int npatch, const float* 
                                        void* stream)
 {
     return cyl_net_own_sets("buf_cylindrical_net_w25", x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, true, y, stream);
+}
+
+// x f32[np,Cin0,140] -> y f32[np,32,140] through k_cyl_net_w25t: buf_cylindrical_net_w25 with, per 128-output layer, an optional row-6 tap
+// set, and the order of the two rounds there
+extern "C" int buf_cylindrical_net_w25t(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
+                                        const int* cout_host, const int* relu_host, const float* const* wt24_host, const float* const* wt25_host,
+                                        const float* const* taps_host, int order, float* y, void* stream)
+{
+    return cyl_net_own_sets("buf_cylindrical_net_w25t", x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, true, y, stream,
+                            true, taps_host, order);
 }
 
 // ---- cost net ---------------------------------------------------------------------------------------------------------------------

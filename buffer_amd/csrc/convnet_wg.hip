@@ -61,6 +61,7 @@ struct CylWgParams {
     const float* bias[WG_LAYERS];   // [Cout]
     int cin[WG_LAYERS], cout[WG_LAYERS], relu[WG_LAYERS];
     const int* only_if;             // nullable: workgroup p runs only if only_if[p] != 0 (the fp32 re-run of buf_cylindrical_net_split_safe)
+    const float* taps[WG_LAYERS];   // k_cyl_net_w25t only (csrc/convnet_w25t.hip): the row-6 tap sets of the layers whose relu word says so
 #ifdef WG_STAMP
     long long* stamps;              // development build (-DWG_STAMP): [workgroup][wave][20] s_memtime at the layer boundaries
 #endif

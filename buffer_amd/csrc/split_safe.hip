@@ -75,16 +75,19 @@ extern "C" int buf_cylindrical_net_split_safe(const float* x, int npatch, const 
 static int cyl_split_safe_own_sets(const char* who, const char* who_f32, const float* x, int npatch, const void* const* wt_split_host,
                                    const float* const* wt_wg_host, const float* const* bias_host, const int* cin_host, const int* cout_host,
                                    const int* relu_host, const float* const* wt24_host, const float* const* wt25_host, bool w25, const float* head_params,
-                                   float* y_or_equi, float* desc, int* status_dev, int* flags_ws, void* stream)
+                                   float* y_or_equi, float* desc, int* status_dev, int* flags_ws, void* stream, bool w25t = false,
+                                   const float* const* taps_host = nullptr, int order = 0)
 {
     BUF_REQUIRE(npatch >= 0, BUF_EINVAL, "%s: npatch=%d", who, npatch);
+    BUF_REQUIRE(!w25t || (order & ~BUF_CYL_ROW6_FIRST) == 0, BUF_EINVAL, "%s: order=%d (0, or BUF_CYL_ROW6_FIRST = 1)", who, order);
     if (npatch == 0) return BUF_OK;
     BUF_REQUIRE(x && y_or_equi && flags_ws && wt_split_host, BUF_EINVAL, "%s: null argument", who);
     BUF_REQUIRE(!head_params || desc, BUF_EINVAL, "%s: head without desc", who);
-    BUF_REQUIRE(wt24_host && (wt25_host || !w25), BUF_EINVAL, "%s: null argument", who_f32);
+    BUF_REQUIRE(wt24_host && (wt25_host || !w25) && (taps_host || !w25t), BUF_EINVAL, "%s: null argument", who_f32);
     CylWgParams P;
     CylKernel* K;
-    if (int rc = cyl_prepare(wt_wg_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, BUF_CYL_FORM_DEFAULT, who_f32, P, K)) return rc;
+    if (int rc = cyl_prepare(wt_wg_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, BUF_CYL_FORM_DEFAULT, who_f32, P, K, taps_host, order))
+        return rc;
     return cyl_split_safe(x, npatch, wt_split_host, bias_host, cin_host, cout_host, relu_host, *K, P, head_params, y_or_equi, desc, status_dev, flags_ws, stream);
 }
 
@@ -106,6 +109,18 @@ extern "C" int buf_cylindrical_net_split_safe_w25(const float* x, int npatch, co
 {
     return cyl_split_safe_own_sets("buf_cylindrical_net_split_safe_w25", "buf_cylindrical_net_w25", x, npatch, wt_split_host, wt_wg_host, bias_host,
                                    cin_host, cout_host, relu_host, wt24_host, wt25_host, true, head_params, y_or_equi, desc, status_dev, flags_ws, stream);
+}
+
+// The same through k_cyl_net_w25t (csrc/convnet_w25t.hip): taps_host and order as for buf_cylindrical_net_w25t, the re-run is k_cyl_net_w25t_rerun
+extern "C" int buf_cylindrical_net_split_safe_w25t(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                                   const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                                   const float* const* wt24_host, const float* const* wt25_host, const float* const* taps_host,
+                                                   int order, const float* head_params, float* y_or_equi, float* desc, int* status_dev,
+                                                   int* flags_ws, void* stream)
+{
+    return cyl_split_safe_own_sets("buf_cylindrical_net_split_safe_w25t", "buf_cylindrical_net_w25t", x, npatch, wt_split_host, wt_wg_host, bias_host,
+                                   cin_host, cout_host, relu_host, wt24_host, wt25_host, true, head_params, y_or_equi, desc, status_dev, flags_ws, stream,
+                                   true, taps_host, order);
 }
 
 // The cost net likewise: dense inputs (s_rows == null: s_eq, t_eq f32[m,32,5,20]) or the gathered form (s_eq = t_eq = equi

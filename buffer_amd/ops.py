@@ -1142,6 +1142,44 @@ def cyl_f25_filters(layers, parts, device):
     return sets, (C.c_void_p * len(sets))(*[None if t is None else t.data_ptr() for t in sets])
 
 
+# Row 6 of the 128-output layers (k_cyl_net_w25t, csrc/convnet_w25t.hip; profiles/cyl_taps_ab.md): 'taps': the direct round of output row 6
+# runs on the filter rows 0 and 1 as the host tiled them (a set of 6 Cout Cin floats per layer) instead of forming its taps per patch from
+# three Winograd block rows; 'order': the direct round runs in front of the Winograd round, whose 64 outputs per lane then need no parking;
+# 'both' (or 'all'); 'off' or None: k_cyl_net_w25 (or whatever the other arguments pick) as it is, bit for bit.  The argument row6= of the two classes
+# picks one per net; a net built with any other form argument keeps that kernel as it was unless row6= asks.  The default is what met both
+# rules of the A/B (profiles/cyl_taps_ab.md): both parts together.
+ROW6_DEFAULT = 'both'
+ROW6_PARTS = {'both': (True, True), 'all': (True, True), 'taps': (True, False), 'order': (False, True), 'off': (False, False), None: (False, False)}
+
+
+def cyl_row6_tile_taps(w):
+    """[Cout, Cin, 3, 3] -> the six taps of output row 6, the filter rows a = 0, 1 as they are, in the tiling of csrc/convnet_w25t.hip:
+    [pair][k-step][q = 0..2][lk][li][4] with float 4 q + e = 6 n2 + 3 a + b of lane (lk, li) = w[16 (2 pair + n2) + li][4 ks + lk][a][b].
+    6 * Cout * Cin floats, bit for bit what buf_cyl_row6_tile_taps writes."""
+    cout, cin = w.shape[0], w.shape[1]
+    assert cin % 4 == 0 and cout % 32 == 0
+    t = np.asarray(w, np.float32)[:, :, :2, :].reshape(cout // 32, 2, 16, cin // 4, 4, 6)      # [pair, n2, li, ks, lk, (a, b)]
+    t = np.transpose(t, (0, 3, 4, 2, 1, 5)).reshape(cout // 32, cin // 4, 4, 16, 3, 4)           # [pair, ks, lk, li, q, e]
+    return np.ascontiguousarray(np.transpose(t, (0, 1, 4, 2, 3, 5))).reshape(-1)                # [pair, ks, q, lk, li, e]
+
+
+def cyl_row6_parts(f24, f24k, f24p, row6, f24a=None, f25=None):
+    """(taps, order first) of the 128-output layers.  Any explicit form argument asks for one of the kernels before this one: neither
+    part then unless row6 says so, and asking for a part with f24, f24k or f24p false is an error."""
+    explicit = not (f24 is None and f24k is None and f24p is None and f24a is None and f25 is None)
+    parts = form_parts('row6', row6, None if explicit else ROW6_DEFAULT, ROW6_PARTS)
+    if any(parts) and not (f24 in (None, True) and f24k in (None, True) and f24p in (None, True)):
+        raise ValueError("row6 goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
+    return parts
+
+
+def cyl_row6_taps(layers, flags, taps, device):
+    """Per layer the row-6 tap set in a buffer of its own (a tensor on `device`) where `taps` and the layer carries the F(2x4) flag of the
+    128-output layers, else None; and the pointer array buf_cylindrical_net_w25t takes."""
+    sets = [torch.from_numpy(cyl_row6_tile_taps(w)).to(device) if (taps and flag == F24_FLAG) else None for (w, _, _), flag in zip(layers, flags)]
+    return sets, (C.c_void_p * len(sets))(*[None if t is None else t.data_ptr() for t in sets])
+
+
 def cyl_layer_filters(w, f24k=True):
     """The fp32 kernel's filter buffer of one layer and its F(2x4) flag: layers with 128 output channels run in the F(2x4) form
     (flag 2) and, with f24k, so do the layers with 64 output channels whose Cin is a multiple of 64 (flag 4: k_cyl_net_w24k or
@@ -1182,15 +1220,18 @@ class CylindricalNet:
     csrc/convnet_w24a.hip: per layer U = G g G^T in the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu
     word; for k_cyl_net_w24a the remaining layers' F(2x4) sets in buffers of their own, `wt24`), biases."""
 
-    def __init__(self, layers, device, f24=None, f24k=None, f24p=None, f24a=None, f25=None):
+    def __init__(self, layers, device, f24=None, f24k=None, f24p=None, f24a=None, f25=None, row6=None):
         """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  No form argument: k_cyl_net_w24a with F(2x4)
         tiles in every layer (F24A_DEFAULT; f24a = 'all' | 'out64' | 'out32' | 'off' picks the parts).  An explicit f24, f24k or f24p gives
         one of the older kernels with the defaults f24 = f24k = True, f24p = F24P_DEFAULT: f24 = False: the F(2x2) form in every
         layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B); f24k = False: F(2x4) in the 128-output layers
         only (k_cyl_net_w24); f24p: the flagged 64-output layers in the pass-split form (k_cyl_net_w24p), else K split (k_cyl_net_w24k).
         f25 = 'all' | 'out64' | 'out32' | 'off' (F25_DEFAULT): F(2x5) tiles in the layers of those output widths (k_cyl_net_w25); the
-        other layers as the remaining arguments say."""
+        other layers as the remaining arguments say.
+        row6 = 'both' | 'taps' | 'order' | 'off' (ROW6_DEFAULT): host-formed row-6 taps and / or the direct round first in the 128-output
+        layers (k_cyl_net_w25t)."""
         parts25 = cyl_f25_parts(f24, f24k, f24p, f25)
+        row6_taps, row6_first = cyl_row6_parts(f24, f24k, f24p, row6, f24a, f25)
         f24, f24k, f24p, parts = cyl_f24a_parts(f24, f24k, f24p, f24a)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_wg"            # the family (CylindricalNetSplit: "buf_cylindrical_net_split"); self.fn is what is called
@@ -1218,7 +1259,13 @@ class CylindricalNet:
         self.f25_layers = [l for l, t in enumerate(self.wt25) if t is not None]
         # The entry point, chosen once: the fp32 call, the split-safe call of CylindricalNetSplit, and what both take between the relu
         # words and the outputs
-        if self.f25_layers:
+        # the 128-output layers k_cyl_net_w25t runs on a row-6 tap set, and the order of their two rounds
+        self.taps, self._tapsp = cyl_row6_taps(layers, flags, row6_taps, device)
+        self.taps_layers = [l for l, t in enumerate(self.taps) if t is not None]
+        self.row6_first = bool(row6_first and F24_FLAG in flags)
+        if self.taps_layers or self.row6_first:
+            fn, safe, self._extra = "w25t", "split_safe_w25t", (self._w24p, self._w25p, self._tapsp, 1 if self.row6_first else 0)
+        elif self.f25_layers:
             fn, safe, self._extra = "w25", "split_safe_w25", (self._w24p, self._w25p)
         elif self.f24_layers:
             fn, safe, self._extra = "wg_all", "split_safe_all", (self._w24p,)
@@ -1256,14 +1303,15 @@ class CylindricalNetSplit:
     kernel.  For widths the fp32 kernel is not built for (the released network's are) the old contract stays: `check_range()` raises if
     the status word was set."""
 
-    def __init__(self, layers, device, f24k=None, f24p=None, f24a=None, f25=None):
-        """f24k, f24p, f24a, f25: the fp32 re-run's kernel, as in CylindricalNet (no form argument: k_cyl_net_w24a_rerun, or
-        k_cyl_net_w25_rerun where F25_DEFAULT names layers)"""
+    def __init__(self, layers, device, f24k=None, f24p=None, f24a=None, f25=None, row6=None):
+        """f24k, f24p, f24a, f25, row6: the fp32 re-run's kernel, as in CylindricalNet (no form argument: k_cyl_net_w24a_rerun, or
+        k_cyl_net_w25_rerun where F25_DEFAULT names layers, or k_cyl_net_w25t_rerun where ROW6_DEFAULT names a part)"""
         cyl_f25_parts(None, f24k, f24p, f25)             # (the arguments are checked whether or not the fp32 side gets built)
+        cyl_row6_parts(None, f24k, f24p, row6, f24a, f25)
         form = cyl_f24a_parts(None, f24k, f24p, f24a)[2]
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_split"
-        self.f24_layers, self.f24_all, self.f25_layers = [], False, []
+        self.f24_layers, self.f24_all, self.f25_layers, self.taps_layers, self.row6_first = [], False, [], [], False
         self.form = 1 if form else 0                     # of the fp32 re-run, as in CylindricalNet
         for w, b, relu in layers:
             cout, cin = w.shape[0], w.shape[1]
@@ -1281,12 +1329,13 @@ class CylindricalNetSplit:
         # the fp32 re-run is a CylindricalNet over the same layers (the split kernel itself takes the relu words 0 / 1); widths it is not
         # built for keep the raising contract
         self.safe = n == 8 and _lib.lib().buf_cylindrical_net_wg_supports(self._ci, self._co) == 0 and not os.environ.get('BUF_SPLIT_UNSAFE')
-        self.f32 = CylindricalNet(layers, device, f24k=f24k, f24p=f24p, f24a=f24a, f25=f25) if self.safe else None
+        self.f32 = CylindricalNet(layers, device, f24k=f24k, f24p=f24p, f24a=f24a, f25=f25, row6=row6) if self.safe else None
         if self.safe:
             f = self.f32
             self.wt_wg, self._wwp, self._re_safe = f.wt, f._wp, f._re
             self.wt24, self._w24p, self.f24_layers, self.f24_all = f.wt24, f._w24p, f.f24_layers, f.f24_all
             self.wt25, self._w25p, self.f25_layers = f.wt25, f._w25p, f.f25_layers
+            self.taps, self._tapsp, self.taps_layers, self.row6_first = f.taps, f._tapsp, f.taps_layers, f.row6_first
             self.fn = f.fn_split_safe
 
     def _safe_call(self, x, head):

@@ -371,6 +371,18 @@ int     buf_cylindrical_net_w25_flags(const int* cin_host, const int* cout_host,
 int     buf_cylindrical_net_w25(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                 const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
                                 const float* const* wt25_host, float* y, void* stream);
+/* Host-formed row-6 taps and the direct round first in the layers with 128 output channels (csrc/convnet_w25t.hip, kernel k_cyl_net_w25t).
+ * buf_cylindrical_net_w25 with one more array and one more word.  taps_host[8]: per layer null, or the 6*Cout*Cin floats of
+ * buf_cyl_row6_tile_taps -- the filter rows 0 and 1 as they are, tiled [pair][k-step][q = 0..2][lk][li][4] with float 4 q + e =
+ * 6 n2 + 3 a + b of a lane -- in a buffer of their own; allowed on a layer with 128 output channels that carries BUF_CYL_F24, else
+ * BUF_EINVAL.  order: 0, or BUF_CYL_ROW6_FIRST: the direct round of row 6 runs in front of the Winograd round in every such layer.
+ * A layer without a tap set forms its taps as in buf_cylindrical_net_w25; with no set and order = 0 the result is that entry point's,
+ * bit for bit. */
+#define BUF_CYL_ROW6_FIRST 1
+int     buf_cyl_row6_tile_taps(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 6*Cout*Cin floats; Cout a multiple of 32 */
+int     buf_cylindrical_net_w25t(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
+                                 const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
+                                 const float* const* wt25_host, const float* const* taps_host, int order, float* y, void* stream);
 
 /* A11 (dense), split-f16 form -- the same stack with fp32-EQUIVALENT arithmetic on the f16 matrix pipe (csrc/convnet_h3.hip; opt-in,
  * the all-fp32 kernel above stays the default): every fp32 operand is split once into hi = f16(x) and lo' = f16((x - hi) 2^11)
@@ -424,6 +436,12 @@ int     buf_cylindrical_net_split_safe_w25(const float* x, int npatch, const voi
                                            const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                            const float* const* wt24_host, const float* const* wt25_host, const float* head_params,
                                            float* y_or_equi, float* desc, int* status_dev, int* flags_ws, void* stream);
+/* The same with the fp32 re-run through k_cyl_net_w25t_rerun: taps_host and order as for buf_cylindrical_net_w25t */
+int     buf_cylindrical_net_split_safe_w25t(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
+                                            const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
+                                            const float* const* wt24_host, const float* const* wt25_host, const float* const* taps_host,
+                                            int order, const float* head_params, float* y_or_equi, float* desc, int* status_dev,
+                                            int* flags_ws, void* stream);
 
 /* A11 (head)  attention pooling + normalisation (models/patch_embedder.py:66-72,81-84): pool_layer
  * (Conv2d 1x1 32->16 + BN + ReLU, Conv2d 1x1 16->1 + BN + ReLU), desc = normalize(mean(y * w)),

@@ -25,7 +25,7 @@ for r in csv.DictReader(open(path)):
     e = rows[k].setdefault(r['Dispatch_Id'], {'grid': int(r['Grid_Size'])})
     e[r['Counter_Name']] = e.get(r['Counter_Name'], 0.0) + float(r['Counter_Value'])
 kernels = {}
-for k in ('k_patch_voxelize', 'k_cyl_net_wg', 'k_cyl_net_w24', 'k_cyl_net_w24k', 'k_cyl_net_w24p', 'k_cyl_net_w24a', 'k_cyl_net_w25', 'k_cyl_net_h3', 'k_desc_head', 'k_select_patches_grid'):
+for k in ('k_patch_voxelize', 'k_cyl_net_wg', 'k_cyl_net_w24', 'k_cyl_net_w24k', 'k_cyl_net_w24p', 'k_cyl_net_w24a', 'k_cyl_net_w25', 'k_cyl_net_w25t', 'k_cyl_net_h3', 'k_desc_head', 'k_select_patches_grid'):
     d = list(rows.get(k, {}).values())
     if not d:
         continue
@@ -50,7 +50,7 @@ for k in ('k_cost_net', 'k_cost_net_w24', 'k_cost_net_w24b'):
             kernels[k][name] = sum(x[c] for x in d) / len(d) / matches
 lib = ctypes.CDLL(os.path.join(ROOT, 'buffer_amd', 'libbuffer_hip.so'))
 src = {f: hashlib.sha256(open(os.path.join(ROOT, 'buffer_amd', 'csrc', f), 'rb').read()).hexdigest()[:16]
-       for f in ('voxelize.hip', 'convnet_wg.hip', 'convnet_w24.hip', 'convnet_w24k.hip', 'convnet_w24p.hip', 'convnet_w24a.hip', 'convnet_w25.hip', 'convnet_h3.hip',
+       for f in ('voxelize.hip', 'convnet_wg.hip', 'convnet_w24.hip', 'convnet_w24k.hip', 'convnet_w24p.hip', 'convnet_w24a.hip', 'convnet_w25.hip', 'convnet_w25t.hip', 'convnet_h3.hip',
                  'costnet.hip', 'costnet_w24.hip', 'costnet_w24b.hip')}
 json.dump(dict(source='rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVES on the bench.py command of the line in `bench` '
                       '(wave-level instruction counts; SQ_INSTS_VALU includes the MFMAs)',
