@@ -16,6 +16,7 @@
 #include "convnet_h3.hip"
 #include "costnet_h3.hip"
 #include "preprocess.hip"
+#include "normals.hip"
 // Packed-fp32 vector instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) are OFF for the whole library (buffer_amd/build.py:
 // -target-feature -packed-fp32-ops).  Round 5 finding (tools/race_probe3.py, profiles/r05_packed_fp32_hazard.txt): a wavefront
 // executing packed-fp32 instructions returns wrong values in its lanes 0..15 now and then while ANOTHER wavefront of the same SIMD

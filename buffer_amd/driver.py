@@ -165,6 +165,12 @@ def add_refine_args(ap):
                     help='--refine voxelized: the voxel edge (default: twice the correspondence distance)')
     ap.add_argument('--refine-neighbors', type=int, default=7, choices=(1, 7, 27),
                     help='--refine voxelized: voxels met by a source point (the voxel it falls into, + its 6 face neighbours, or all 27)')
+    ap.add_argument('--refine-normals', default='knn', choices=('knn', 'hybrid'),
+                    help='the normals of --refine on the learned path.  knn: the 30 nearest neighbours (default).  hybrid: the 30 nearest '
+                         'inside --refine-normal-radius, one launch without a retry loop (preprocess.estimate_normals_radius); '
+                         'the summary carries "refine_normals", and "refined" its "refine_normal_radius"')
+    ap.add_argument('--refine-normal-radius', type=float, default=None, metavar='R',
+                    help='--refine-normals hybrid: the radius (default: twice the correspondence distance)')
 
 
 def add_descriptor_args(ap):
@@ -187,6 +193,10 @@ def add_descriptor_args(ap):
                     help="--descriptor fpfh: Lowe's ratio test on top of the mutual filter, 0 < R < 1 -- a match stays only if its nearest "
                          'descriptor distance is at most R times the second nearest (ops.feature_match; default: no ratio test); the '
                          'summary carries "match_ratio"')
+    ap.add_argument('--fpfh-normals', default='given', choices=('given', 'hybrid'),
+                    help='--descriptor fpfh: the normals under FPFH and its --refine.  given: the data set\'s (default).  hybrid: recomputed '
+                         'from the 30 nearest points inside 2 voxels, oriented to the origin '
+                         '(preprocess.estimate_normals_radius); the summary carries "fpfh_normals"')
 
 
 def parse_with_preset(ap, argv, driver_name):
@@ -205,6 +215,15 @@ def parse_with_preset(ap, argv, driver_name):
         ap.error(f'--match-ratio {a.match_ratio} thins the matches of the classical baseline: it needs --descriptor fpfh')
     if a.match_ratio is not None and not (0.0 < a.match_ratio < 1.0):
         ap.error(f'--match-ratio {a.match_ratio}: must be in (0, 1)')
+    if a.fpfh_normals != 'given' and a.descriptor != 'fpfh':
+        ap.error(f'--fpfh-normals {a.fpfh_normals} chooses the normals of the classical baseline: it needs --descriptor fpfh')
+    if a.refine_normals != 'knn' and (not a.refine or a.descriptor == 'fpfh'):
+        ap.error(f'--refine-normals {a.refine_normals} chooses the normals of --refine on the learned path: it needs --refine, and with '
+                 '--descriptor fpfh the normals are those of --fpfh-normals')
+    if a.refine_normal_radius is not None and a.refine_normals != 'hybrid':
+        ap.error(f'--refine-normal-radius {a.refine_normal_radius} is the radius of --refine-normals hybrid')
+    if a.refine_normal_radius is not None and not (0.0 < a.refine_normal_radius < float('inf')):
+        ap.error(f'--refine-normal-radius {a.refine_normal_radius}: must be finite and > 0')
     if a.refine == 'voxelized' and a.descriptor == 'fpfh':
         ap.error('--refine voxelized refines the learned path: not available with --descriptor fpfh')
     if a.refine_voxel is not None and not (0.0 < a.refine_voxel < float('inf')):
@@ -229,9 +248,9 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     --descriptor fpfh: fpfh.FpfhRegistration stands in for BufferPipeline (nothing to calibrate; the line carries "descriptor" and
     "estimator", --estimator choosing its RANSAC, its Fast Global Registration, its SC2-PCR or its max-clique + TLS estimator, which adds
     "certified_pairs"; --keypoints iss makes it match ISS keypoints instead of every point and adds "keypoints"; --match-ratio R
-    adds Lowe's ratio test to its matching and "match_ratio").
+    adds Lowe's ratio test to its matching and "match_ratio"; --fpfh-normals hybrid recomputes its normals and adds "fpfh_normals").
     --refine: the refined poses travel in a second gather_poses and are summarized under "refined"; everything else reads the
-    unrefined poses.
+    unrefined poses.  --refine-normals hybrid adds "refine_normals" (and "refined" its "refine_normal_radius").
     ranks: init()'s result.  Prints one JSON line and returns the poses f32[n,4,4] (numpy) on rank 0."""
     from . import dist as bdist
     from .pipeline import BufferPipeline
@@ -241,7 +260,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
         from .fpfh import FpfhRegistration
         iss = getattr(a, 'keypoints', 'all') == 'iss'
         pipe = FpfhRegistration(cfg, dev, estimator=getattr(a, 'estimator', 'ransac'),     # no neighbourhood limits: nothing to calibrate
-                                keypoints='iss' if iss else None, match_ratio=getattr(a, 'match_ratio', None))
+                                keypoints='iss' if iss else None, match_ratio=getattr(a, 'match_ratio', None),
+                                normals=getattr(a, 'fpfh_normals', 'given'))
     else:
         pipe = BufferPipeline(cfg, dev)
     if a.limits and not fpfh:
@@ -262,6 +282,9 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
         if a.refine == 'voxelized':
             rv = getattr(a, 'refine_voxel', None)
             refine.update(voxel=2.0 * refine['max_dist'] if rv is None else rv, neighbors=getattr(a, 'refine_neighbors', 7))
+        if getattr(a, 'refine_normals', 'knn') != 'knn':
+            rn = getattr(a, 'refine_normal_radius', None)
+            refine.update(normals=a.refine_normals, normal_radius=2.0 * refine['max_dist'] if rn is None else rn)
     res = register_pairs(pipe, ds, ids, a.batch, stage_metrics=a.stage_metrics, refine=refine)
     refined = None
     if refine is not None:
@@ -288,6 +311,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
                            iterations=float(stats[:, 2].mean()) if len(stats) else 0.0)
             if a.refine == 'voxelized':
                 ref_out.update(voxel=refine['voxel'], neighbors=refine['neighbors'])
+            if 'normals' in refine:
+                ref_out.update(refine_normal_radius=refine['normal_radius'])
         out = summarize(poses)
         out.update(pairs_per_sec=len(ds) / dt, n_gpus=world, limits=pipe.limits, preset=a.preset)
         if fpfh:
@@ -297,12 +322,16 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
                 out['certified_pairs'] = int((certified == 1).sum())
             if pipe.match_ratio is not None:
                 out['match_ratio'] = pipe.match_ratio
+            if pipe.normals != 'given':
+                out['fpfh_normals'] = pipe.normals
             if pipe.keypoints == 'iss':                      # (the mean is this rank's: the counts stay on the rank that found them)
                 kc = np.concatenate(pipe.keypoint_counts_log or [np.zeros(0, np.int64)])
                 out['keypoints'] = dict(detector='iss', salient_radius=pipe.iss_salient_radius, non_max_radius=pipe.iss_non_max_radius,
                                         mean_per_cloud=float(kc.mean()) if len(kc) else 0.0)
         if ref_out is not None:
             out['refined'] = ref_out
+            if 'normals' in refine:
+                out['refine_normals'] = refine['normals']
         overlaps = None
         if a.by_overlap:
             from . import pairs

@@ -23,6 +23,7 @@ ESTIMATORS = ('ransac', 'fgr')
 ALL_ESTIMATORS = ESTIMATORS + ('sc2',)
 KNOWN_ESTIMATORS = ALL_ESTIMATORS + ('clique',)
 KEYPOINTS = (None, 'iss')
+NORMALS = ('given', 'hybrid')
 
 
 def compute_fpfh(points, normals, radius, max_nn=100, lengths=None, grid=None):
@@ -107,12 +108,20 @@ class FpfhRegistration:
     every point, matching and the estimator then run on the keypoints' rows alone (fewer than 3 matches: the identity, as ever).
     `keypoint_counts` keeps the last call's keypoints per cloud (int64[2B], host); refine_batch goes on refining on the dense clouds.
     match_ratio=None (default): the mutual matches as they are.  match_ratio=R in (0, 1): Lowe's ratio test on top (match_batch).  Either
-    way all pairs of a batch are matched in one match_batch call, with the rows match() gives pair by pair."""
+    way all pairs of a batch are matched in one match_batch call, with the rows match() gives pair by pair.
+    normals='given' (default): the normals that arrive with the second-level clouds (the data set's 30-NN ones).  normals='hybrid': they
+    are recomputed from the normal_max_nn (30) nearest points inside normal_radius_factor (2) * cfg.voxel_size_0, oriented to the
+    origin (preprocess.estimate_normals_radius: one grid of its own at that radius, one query, one launch -- FPFH's grid at 5 voxels
+    would serve, but a query at 2 voxels on it measured 4.8 x the whole call on a grid of its own); refine_batch then refines
+    with normals estimated in the same way."""
 
     def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac',
                  keypoints=None, iss_salient_factor=6.0, iss_non_max_factor=4.0, iss_gamma=(0.975, 0.975), iss_min_neighbors=5,
-                 match_ratio=None):
+                 match_ratio=None, normals='given', normal_radius_factor=2.0, normal_max_nn=30):
         self.cfg, self.device = cfg, torch.device(device)
+        if normals not in NORMALS:
+            raise ValueError(f'FpfhRegistration: unknown normals {normals!r} (one of {NORMALS})')
+        self.normals, self.normal_radius, self.normal_max_nn = normals, float(normal_radius_factor) * cfg.voxel_size_0, int(normal_max_nn)
         if match_ratio is not None and not (0.0 < float(match_ratio) < 1.0):
             raise ValueError(f'FpfhRegistration: match_ratio={match_ratio} (None, or in (0, 1))')
         self.match_ratio = None if match_ratio is None else float(match_ratio)
@@ -155,6 +164,8 @@ class FpfhRegistration:
         pts = torch.cat([i['points'] for i in inps]).float().contiguous()
         nrm = torch.cat([i['features'][:, :3] for i in inps]).float().contiguous()
         lens = np.concatenate([np.asarray(i['lengths'], np.int32).reshape(2) for i in inps])
+        if self.normals == 'hybrid':
+            nrm = self._hybrid_normals(pts, lens)
         if self.keypoints == 'iss':
             pts, lens, F = self._iss_sets(pts, nrm, lens)
         else:
@@ -174,6 +185,11 @@ class FpfhRegistration:
             out.append(ransac_on_matches(pts[s0:t0], pts[t0:t1], corr[int(co[b]):int(co[b + 1])], self.cfg.ransac_hypotheses, seeds[b],
                                          self.max_dist, self.edge_similarity))
         return out
+
+    def _hybrid_normals(self, pts, lens):
+        """normals='hybrid': the normals of the stacked clouds, oriented to the origin"""
+        from . import preprocess
+        return preprocess.estimate_normals_radius(pts, self.normal_radius, self.normal_max_nn, lengths=lens)
 
     def _iss_sets(self, pts, nrm, lens):
         """keypoints='iss': FPFH of EVERY point (a descriptor needs the SPFH of all its neighbours) and the ISS keypoints on one shared
@@ -242,6 +258,11 @@ class FpfhRegistration:
         src, tgt = torch.cat([c[0] for c in cl]).float().contiguous(), torch.cat([c[1] for c in cl]).float().contiguous()
         snrm = torch.cat([c[2] for c in cl]).float().contiguous() if method == 'generalized' else None
         tnrm = torch.cat([c[3] for c in cl]).float().contiguous() if method != 'point_to_point' else None
+        if self.normals == 'hybrid' and method == 'generalized':
+            nrm = self._hybrid_normals(torch.cat([src, tgt]), np.concatenate([sl, tl]))
+            snrm, tnrm = nrm[:src.shape[0]].contiguous(), nrm[src.shape[0]:].contiguous()
+        elif self.normals == 'hybrid' and method == 'point_to_plane':
+            tnrm = self._hybrid_normals(tgt, tl)
         T, fit, rmse, iters, _ = ops.icp_batched(src, sl, tgt, tl, float(self.cfg.dist_th if max_dist is None else max_dist), T0, method,
                                                  tnrm, int(max_iteration), src_normals=snrm, epsilon=epsilon)
         return dict(poses=T.float(), fitness=fit, inlier_rmse=rmse, iterations=iters)

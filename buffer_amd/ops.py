@@ -703,6 +703,40 @@ def iss_keypoints(points, nbr_sal, nbr_nms, gamma_21=0.975, gamma_32=0.975, min_
     return mask, sal, eig
 
 
+def row_normals(points, nbr, max_nn=0, camera=None, order=None, return_cov=False, return_counts=False):
+    """buf_row_normals: normals of the points f32[n,3] from their sorted radius rows nbr int32[n,k] (CellGrid.query: padded with values
+    >= n; the point itself is in its row and counts) -> unit normals f32[n,3] (, covariances f64[n,6] = (c00, c01, c02, c11, c12, c22))
+    (, row lengths int32[n]).  max_nn: 0 = whole rows, else the first max_nn columns.  camera (3 numbers): the normals are flipped
+    towards it; None leaves them as computed.  order int32[n] (a permutation, e.g. CellGrid.order): the processing order, speed only.
+    Rows of fewer than 3 points give (0, 0, 1) and the identity.  The rows may belong to several stacked clouds."""
+    L = _lib.lib()
+    points, nbr = _dev(points, torch.float32, "row_normals.points"), _dev(nbr, torch.int32, "row_normals.nbr")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"row_normals: points {tuple(points.shape)} is not [N,3]")
+    n = int(points.shape[0])
+    if nbr.dim() != 2 or nbr.shape[0] != n or nbr.shape[1] < 1:
+        raise ValueError(f"row_normals: nbr {tuple(nbr.shape)} is not [{n},k], k >= 1")
+    if int(max_nn) < 0:
+        raise ValueError(f"row_normals: max_nn={max_nn} (0 = whole rows, or >= 1)")
+    if order is not None:
+        order = _dev(order, torch.int32, "row_normals.order")
+        if tuple(order.shape) != (n,):
+            raise ValueError(f"row_normals: order {tuple(order.shape)} is not [{n}]")
+    cam = None
+    if camera is not None:
+        cam = np.asarray(camera, np.float64).reshape(-1)
+        if cam.shape[0] != 3:
+            raise ValueError(f"row_normals: camera holds {cam.shape[0]} numbers, not 3")
+        cam = (C.c_double * 3)(*cam.tolist())
+    normals = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    cov = torch.empty((n, 6), dtype=torch.float64, device=points.device) if return_cov else None
+    cnt = torch.empty((n,), dtype=torch.int32, device=points.device) if return_counts else None
+    check(L.buf_row_normals(_ptr(points), n, _ptr(nbr), int(nbr.shape[1]), int(max_nn), _ptr(order), cam, 0 if cam is None else 1,
+                            _ptr(normals), _ptr(cov), _ptr(cnt), _stream()), "buf_row_normals")
+    out = (normals,) + ((cov,) if return_cov else ()) + ((cnt,) if return_counts else ())
+    return out if len(out) > 1 else normals
+
+
 def _corr_batch(fn, src, src_lengths, tgt, tgt_lengths, corr, corr_lengths):
     """The (src, tgt, corr) batch of fgr_batched / sc2_batched / clique_batched (fn) on the device and its host lengths, checked against
     each other -> (src, tgt, corr, sl, tl, cl, B, dev)."""

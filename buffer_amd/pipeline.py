@@ -12,6 +12,8 @@ from .patch_embedder import PatchEmbedder
 from .point_learner import PointLearner, orient_axes
 from .weights import load_weights
 
+REFINE_NORMALS = ('knn', 'hybrid')       # refine_batch: how the dense clouds' normals are estimated
+
 
 class BufferPipeline:
     def __init__(self, cfg=THREEDMATCH, device='cuda:0', weights=None, limits=None):
@@ -90,14 +92,17 @@ class BufferPipeline:
         return res
 
     @torch.no_grad()
-    def refine_batch(self, inps, poses, method='generalized', max_dist=None, max_iteration=30, epsilon=1e-3, voxel=None, neighbors=7):
+    def refine_batch(self, inps, poses, method='generalized', max_dist=None, max_iteration=30, epsilon=1e-3, voxel=None, neighbors=7,
+                     normals='knn', normal_radius=None, normal_max_nn=30):
         """Dense refinement of a batch's poses: ONE batched ICP call (icp.py / csrc/icp.hip, all pairs in one set of launches) on the
         dense first-level clouds of inps (src_raw / tgt_raw), started from `poses` (B src -> tgt 4x4: what register_batch returned, a
         list or a [B,4,4] tensor), which are converted to f64 on the device -- no pose passes through the host.
         method: 'generalized' (plane-to-plane, epsilon = the covariance along a normal), 'point_to_plane' or 'point_to_point';
         max_dist: the correspondence distance, cfg.dist_th unless given.  Normals come from ONE stacked
         preprocess.estimate_normals(knn=30, orient=False, lengths=) call: of all 2B clouds (sources, then targets) for 'generalized', of
-        the B targets for 'point_to_plane', none for 'point_to_point'.
+        the B targets for 'point_to_plane', none for 'point_to_point'.  normals='hybrid': the same clouds' normals from ONE
+        preprocess.estimate_normals_radius call instead (the normal_max_nn nearest inside normal_radius, twice the correspondence
+        distance unless given: one grid, one query, one launch, no retry and no host wait); the rest is unchanged.
         method 'voxelized' (icp.vgicp_batched, csrc/vgicp.hip): the normals of 'generalized', ONE voxel map of the B targets (voxel:
         its edge, twice the correspondence distance unless given; epsilon) and one batched call on it with `neighbors` (1, 7 or 27)
         voxels per source point; no nearest-neighbour search.  Its inlier_rmse is the distance to voxel means: of the order of the
@@ -109,6 +114,8 @@ class BufferPipeline:
             raise ValueError(f"refine_batch: unknown method {method!r} (one of {sorted(list(ops.ICP_METHODS) + ['voxelized'])})")
         if method == 'voxelized' and neighbors not in ops.VGICP_NEIGHBORS:
             raise ValueError(f'refine_batch: neighbors={neighbors} (one of {ops.VGICP_NEIGHBORS})')
+        if normals not in REFINE_NORMALS:
+            raise ValueError(f'refine_batch: unknown normals {normals!r} (one of {REFINE_NORMALS})')
         dev, B = self.device, len(inps)
         if isinstance(poses, (list, tuple)):
             poses = torch.stack(list(poses)) if B else torch.zeros((0, 4, 4), device=dev)
@@ -116,15 +123,20 @@ class BufferPipeline:
         if B == 0:
             return dict(poses=torch.zeros((0, 4, 4), dtype=torch.float32, device=dev), fitness=torch.zeros(0, dtype=torch.float64, device=dev),
                         inlier_rmse=torch.zeros(0, dtype=torch.float64, device=dev), iterations=torch.zeros(0, dtype=torch.int32, device=dev))
+        if normals == 'hybrid':
+            nr = 2.0 * float(self.cfg.dist_th if max_dist is None else max_dist) if normal_radius is None else float(normal_radius)
+            estimate = lambda pts, lengths: preprocess.estimate_normals_radius(pts, nr, int(normal_max_nn), orient=False, lengths=lengths)
+        else:
+            estimate = lambda pts, lengths: preprocess.estimate_normals(pts, knn=30, orient=False, lengths=lengths)
         srcs, tgts = [i['src_raw'][:, :3] for i in inps], [i['tgt_raw'][:, :3] for i in inps]
         sl, tl = np.array([s.shape[0] for s in srcs], np.int32), np.array([t.shape[0] for t in tgts], np.int32)
         src, tgt = torch.cat(srcs).float().contiguous(), torch.cat(tgts).float().contiguous()
         snrm = tnrm = None
         if method in ('generalized', 'voxelized'):
-            nrm = preprocess.estimate_normals(torch.cat([src, tgt]), knn=30, orient=False, lengths=np.concatenate([sl, tl]))
+            nrm = estimate(torch.cat([src, tgt]), np.concatenate([sl, tl]))
             snrm, tnrm = nrm[:src.shape[0]].contiguous(), nrm[src.shape[0]:].contiguous()
         elif method == 'point_to_plane':
-            tnrm = preprocess.estimate_normals(tgt, knn=30, orient=False, lengths=tl)
+            tnrm = estimate(tgt, tl)
         if method == 'voxelized':
             edge = float(voxel) if voxel is not None else 2.0 * float(self.cfg.dist_th if max_dist is None else max_dist)
             vmap = ops.voxel_map_build(tgt, tl, edge, tnrm, epsilon)

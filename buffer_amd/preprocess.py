@@ -131,6 +131,63 @@ def estimate_normals(points, knn=30, camera=(0.0, 0.0, 0.0), orient=True, radius
     raise _lib.BufferHipError("estimate_normals: neighbourhood search did not converge")
 
 
+def _radius_rows(fn, points, radius, max_nn, lengths, grid):
+    """the rows of estimate_normals_radius / estimate_covariances -> (points, nbr int32[n,k] or None when n == 0, grid)"""
+    pts = _dev(points, torch.float32, fn)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"{fn}: points {tuple(pts.shape)} is not [N,3]")
+    n = int(pts.shape[0])
+    lens = np.array([n], np.int32) if lengths is None else np.asarray(lengths, np.int32).reshape(-1)
+    if int(lens.sum()) != n:
+        raise ValueError(f"{fn}: lengths sum to {int(lens.sum())}, points holds {n} rows")
+    r = float(radius)
+    if not (0.0 < r < float('inf')):
+        raise ValueError(f"{fn}: radius={radius} (finite, > 0)")
+    if max_nn is not None and int(max_nn) < 1:
+        raise ValueError(f"{fn}: max_nn={max_nn} (None or >= 1)")
+    if n == 0:
+        return pts, None, grid
+    if grid is None:
+        grid = ops.CellGrid(pts, lens, r)
+    elif grid.radius < r or grid.ns != n or not np.array_equal(grid.s_lengths, lens):
+        raise ValueError(f"{fn}: the given grid does not cover these clouds at this radius")
+    if max_nn is None:                                           # whole rows: k = the longest one (the call's one host wait)
+        mc = torch.zeros(1, dtype=torch.int32, device=pts.device)
+        grid.query(pts, lens, 0, radius=r, max_count=mc)
+        k = max(int(mc.item()), 1)
+    else:
+        k = int(max_nn)
+    return pts, grid.query(pts, lens, k, radius=r, q_order=grid.order), grid
+
+
+def estimate_normals_radius(points, radius, max_nn=30, camera=(0.0, 0.0, 0.0), orient=True, lengths=None, grid=None, return_cov=False):
+    """open3d estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) [+ orient_normals_towards_camera_location(camera)], and with
+    max_nn=None KDTreeSearchParamRadius(radius): points f32[n,3] (device; several clouds stacked when `lengths` int[nc] is given)
+    -> unit normals f32[n,3] (, covariances f64[n,6] = (c00, c01, c02, c11, c12, c22)).  The neighbours of a point are the max_nn
+    nearest inside `radius` within its own cloud, itself included; fewer than 3 give (0, 0, 1) and the identity covariance.
+    One CellGrid over the stacked clouds (grid: one built elsewhere over the same points and lengths with a radius no smaller, e.g.
+    the one fpfh.compute_fpfh and keypoints.iss_keypoints use: the rows, and so the result, are the same), one query with k = max_nn
+    in the grid's order, one buf_row_normals launch (include/buffer_hip.h N13): no retry and nothing read back.  max_nn=None adds a
+    count-only query whose maximum, the longest row, is k: the call's single host wait.  The launch itself runs in input order: its
+    `order` argument measured 2 to 8 % slower than none (the row reads, not the gathers, carry the kernel).  A given grid
+    with a larger radius costs query time (2.5 x the radius: 2.2 x / 4.8 x the whole call): share one at a similar radius."""
+    pts, nbr, grid = _radius_rows("estimate_normals_radius", points, radius, max_nn, lengths, grid)
+    if nbr is None:
+        out = torch.zeros((0, 3), dtype=torch.float32, device=pts.device)
+        return (out, torch.zeros((0, 6), dtype=torch.float64, device=pts.device)) if return_cov else out
+    return ops.row_normals(pts, nbr, 0, camera if orient else None, return_cov=return_cov)
+
+
+def estimate_covariances(points, radius, max_nn=30, camera=(0.0, 0.0, 0.0), orient=True, lengths=None, grid=None):
+    """open3d estimate_covariances(KDTreeSearchParamHybrid(radius, max_nn) | KDTreeSearchParamRadius(radius) with max_nn=None):
+    the covariances f64[n,6] = (c00, c01, c02, c11, c12, c22) of estimate_normals_radius' neighbourhoods, by the same launch.  The
+    arguments are estimate_normals_radius' (camera and orient are taken so that one argument list serves both; a covariance has no sign)."""
+    pts, nbr, grid = _radius_rows("estimate_covariances", points, radius, max_nn, lengths, grid)
+    if nbr is None:
+        return torch.zeros((0, 6), dtype=torch.float64, device=pts.device)
+    return ops.row_normals(pts, nbr, 0, None, return_cov=True)[1]
+
+
 def prepare_fragments(raws, downsample, voxel_size_0, max_num_pts=30000, seeds=None, with_normals=True):
     """The test-split branch of ThreeDMatchDataset.__getitem__ (dataset.py:93-95,125-153) for SEVERAL fragments:
     raws: list of f32[n,3] device tensors -> list of dict(fds_pts f32[N,3] shuffled, sds_pts f32[M,6] = shuffled

@@ -1,8 +1,10 @@
 """Stand-in for the slice of open3d 0.13 the reference's inference path touches, backed by the gfx950 kernels of
 libbuffer_hip.so (open3d==0.13.0 is a pip dependency of the reference, README.md:28; absent from this image).
 
-    geometry.PointCloud                 points / normals / colors, voxel_down_sample, estimate_normals,
-                                        orient_normals_towards_camera_location, transform, paint_uniform_color
+    geometry.PointCloud                 points / normals / colors / covariances, voxel_down_sample,
+                                        estimate_normals (KDTreeSearchParamKNN -> buf_knn_normals; KDTreeSearchParamHybrid,
+                                        KDTreeSearchParamRadius -> buf_row_normals), estimate_covariances (Hybrid, Radius ->
+                                        buf_row_normals), orient_normals_towards_camera_location, transform, paint_uniform_color
                                         (ThreeDMatch/dataset.py:91-153, KITTI/dataset.py:102-176, utils/common.py:569-578)
     geometry.keypoint                   compute_iss_keypoints -> buffer_amd/keypoints.py iss_keypoints (buf_iss_keypoints)
     utility.Vector3dVector, Vector2iVector

@@ -30,12 +30,14 @@ class PointCloud:
         self._points = Vector3dVector()
         self._normals = Vector3dVector()
         self._colors = Vector3dVector()
+        self._covariances = np.zeros((0, 3, 3), np.float64)
         if points is not None:
             self.points = points
 
     points = property(lambda s: s._points, lambda s, v: setattr(s, "_points", Vector3dVector(v)))
     normals = property(lambda s: s._normals, lambda s, v: setattr(s, "_normals", Vector3dVector(v)))
     colors = property(lambda s: s._colors, lambda s, v: setattr(s, "_colors", Vector3dVector(v)))
+    covariances = property(lambda s: s._covariances, lambda s, v: setattr(s, "_covariances", np.asarray(v, np.float64).reshape(-1, 3, 3)))
 
     def has_points(self):
         return len(self._points) > 0
@@ -74,16 +76,45 @@ class PointCloud:
             out._colors = Vector3dVector(np.repeat(np.asarray(self._colors)[:1], len(out._points), 0))
         return out
 
+    def _radius_search(self, search_param, what):
+        """(radius, max_nn or None) of a Hybrid / Radius neighbourhood"""
+        if isinstance(search_param, KDTreeSearchParamHybrid):
+            return search_param.radius, search_param.max_nn
+        if isinstance(search_param, KDTreeSearchParamRadius):
+            return search_param.radius, None
+        raise NotImplementedError(f"open3d stand-in: {what} takes a KDTreeSearchParamHybrid or KDTreeSearchParamRadius neighbourhood"
+                                  + (" (or KDTreeSearchParamKNN)" if what == "estimate_normals" else ""))
+
     def estimate_normals(self, search_param=None, fast_normal_computation=True):
-        """30-NN PCA normals by default (csrc/preprocess.hip buf_knn_normals); orientation is left as computed."""
+        """PCA normals; orientation is left as computed.  KDTreeSearchParamKNN (default: 30-NN): csrc/preprocess.hip buf_knn_normals;
+        KDTreeSearchParamHybrid(radius, max_nn) / KDTreeSearchParamRadius(radius): csrc/normals.hip buf_row_normals
+        (preprocess.estimate_normals_radius; include/buffer_hip.h N13 lists the deviations)."""
         import torch
         from buffer_amd import preprocess
-        if isinstance(search_param, KDTreeSearchParamHybrid):
-            raise NotImplementedError("open3d stand-in: only KDTreeSearchParamKNN neighbourhoods are provided")
-        knn = search_param.knn if search_param is not None else 30
-        pts = torch.from_numpy(np.asarray(self._points, np.float32)).to(_device())
-        self._normals = Vector3dVector(preprocess.estimate_normals(pts, knn=knn, orient=False).cpu().numpy())
+        knn = search_param is None or isinstance(search_param, KDTreeSearchParamKNN)
+        if not knn:
+            radius, max_nn = self._radius_search(search_param, "estimate_normals")
+        pts = torch.from_numpy(np.asarray(self._points, np.float32).reshape(-1, 3)).to(_device())
+        if knn:
+            nrm = preprocess.estimate_normals(pts, knn=search_param.knn if search_param is not None else 30, orient=False)
+        else:
+            nrm = preprocess.estimate_normals_radius(pts, radius, max_nn, orient=False)
+        self._normals = Vector3dVector(nrm.cpu().numpy())
         return self
+
+    def estimate_covariances(self, search_param=None):
+        """per-point covariances of the neighbourhoods (KDTreeSearchParamHybrid / KDTreeSearchParamRadius; open3d's default is
+        KDTreeSearchParamKNN(30), which is not provided) -> self.covariances f64[n,3,3] (preprocess.estimate_covariances, N13)."""
+        import torch
+        from buffer_amd import preprocess
+        radius, max_nn = self._radius_search(search_param, "estimate_covariances")
+        pts = torch.from_numpy(np.asarray(self._points, np.float32).reshape(-1, 3)).to(_device())
+        c = preprocess.estimate_covariances(pts, radius, max_nn).cpu().numpy()
+        self._covariances = c[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+        return self
+
+    def has_covariances(self):
+        return len(self._covariances) > 0 and len(self._covariances) == len(self._points)
 
     def orient_normals_towards_camera_location(self, camera_location=(0.0, 0.0, 0.0)):
         if not self.has_normals():

@@ -679,6 +679,36 @@ int     buf_iss_keypoints(const float* pts, int n, const int* nbr_sal, int k_sal
                           double gamma_21, double gamma_32, int min_neighbors, double* saliency_out /* f64[n] */,
                           double* eig_out /* f64[n,3], nullable */, unsigned char* mask_out /* u8[n] */, void* stream);
 
+/* N13  Normals and covariances of radius and hybrid neighbourhoods (open3d estimate_normals / estimate_covariances with
+ * KDTreeSearchParamRadius / KDTreeSearchParamHybrid, restated from the published form, parity unpinned: this text is the
+ * specification).  One call for any number of stacked clouds, one launch, no workspace, nothing read back.
+ * pts f32[n,3]; nbr int32[n,k_nbr] = a buf_grid_query row per point (ascending by (d2, index), padded with values >= n: the rows stay
+ * inside a point's cloud, so no lengths are needed).  normals_out f32[n,3], cov_out f64[n,6] = (c00, c01, c02, c11, c12, c22),
+ * count_out int32[n]: each nullable, not all three.
+ * Rows: the valid entries of row i are those with 0 <= idx < n among its first min(max_nn, k_nbr) columns, wherever they sit
+ *   (max_nn == 0: all k_nbr columns); m_i is their number.  The point itself is one of them, as the grid returns it: nothing is skipped.
+ * Arithmetic, all fp64 on the fp32 coordinates promoted, no FMA: q = p_i.  For each valid entry j in column order d = p_j - q,
+ *   S1_a += d_a and S2 += (dx dx, dx dy, dx dz, dy dy, dy dz, dz dz).  m_i >= 3: mu = S1 / m_i, E = S2 / m_i, cov_ab = E_ab - mu_a * mu_b;
+ *   the normal is the eigenvector of the smallest eigenvalue as open3d's FastEigen3x3 finds it (the solver of buf_knn_normals: the same
+ *   function of the six entries), a zero vector from it becomes (0, 0, 1).  m_i < 3: cov = (1, 0, 0, 1, 0, 1) (open3d's identity) and
+ *   the normal is (0, 0, 1).  orient != 0: the normal is flipped when n . (camera - q) < 0, the products summed left to right as
+ *   buf_knn_normals sums them.  count_out[i] = m_i.
+ * Deviations from open3d: the moments are taken about the query point, not the origin (the same covariance up to rounding, far better
+ *   conditioned for clouds away from the origin: the cancellation in E - mu mu^T is of the order of the neighbourhood's radius squared,
+ *   not of the cloud's distance squared); the rows come from the fp32 grid search (d2 < r*r in fp32), not from an fp64 KD-tree.
+ * Non-finite points: a NaN or infinite point has an empty row in the grid and lies in no other row, so it takes the m_i < 3 rule.  A
+ *   hand-made row of three or more entries that names a non-finite point has a covariance with non-finite entries: cov_out holds them
+ *   as computed and the normal is (NaN, NaN, NaN); nothing else follows from it.  Indices are range-checked: nothing is read out of bounds.
+ * order (nullable) int32[n], a permutation of the points: slot t of the launch handles point order[t] (an entry outside [0, n) is
+ *   skipped).  Speed only: with the grid's cell order (buf_grid_t.order) the gathers of a wavefront stay inside a few cells.  The result
+ *   does not depend on it.
+ * No float atomics, every sum has a fixed order: a point's outputs are the same bits alone, in any batch, with any order and on reruns.
+ * BUF_EINVAL before any device work, buf_last_error naming the argument, for n < 0, k_nbr < 1, max_nn < 0, all three outputs null,
+ * orient != 0 with a null camera_host (f64[3], host), and with n > 0 a null pts or nbr.  n == 0 succeeds and touches nothing. */
+int     buf_row_normals(const float* pts, int n, const int* nbr, int k_nbr, int max_nn, const int* order /* nullable */,
+                        const double* camera_host, int orient, float* normals_out /* f32[n,3], nullable */,
+                        double* cov_out /* f64[n,6], nullable */, int* count_out /* int32[n], nullable */, void* stream);
+
 /* N12  Batched descriptor matching with a mutual and a ratio filter: exact, ragged, `pairs` pairs per call.  One scan launch for both
  * directions of all pairs, two small launches for the filters and the ordered output; no atomics; the host reads nothing back.
  * Pair p owns a_lengths_host[p] / b_lengths_host[p] consecutive rows of fa / fb (f32[., d], device, 1 <= d <= 64): A_p and B_p.
