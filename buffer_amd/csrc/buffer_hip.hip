@@ -33,7 +33,7 @@
 #include "costnet.hip"
 #include "costnet_w24.hip"
 #include "costnet_w24b.hip"
-#include "cnn_launch.hip"             // the host side of the ten kernels above: behind all of them
+#include "cnn_launch.hip"             // the host side of the six fused CNN kernels above: behind all of them
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "iss.hip"

@@ -1,6 +1,6 @@
 // The host side of the fused fp32 CNN kernels, behind all of them in the translation unit: one launch path per family.
 //
-//   descriptor net   k_cyl_net_wg | _w24 | _w24k | _w24p | _w24a | _w25 | _w25t (csrc/convnet_w*.hip) and their _rerun twins take the same
+//   descriptor net   k_cyl_net_wg | _w24k | _w25t (csrc/convnet_wg.hip, _w24k.hip, _w25t.hip) and their _rerun twins take the same
 //                    arguments (CylWgParams): cyl_check states the rules of a stack once, cyl_prepare fills the parameters and picks
 //                    the kernel (cyl_kernel_for), cyl_launch launches it -- the plain kernel, or with P.only_if its masked twin.
 //   cost net         k_cost_net | _w24 | _w24b (csrc/costnet*.hip) differ in their parameter struct: cost_net_prepare / cost_net_launch
@@ -21,27 +21,23 @@ static inline bool wg_f24_flagged(int relu) { return relu >= 2; }
 // A kernel and its masked twin; the LDS grants are per kernel symbol
 typedef void (*CylKernelFn)(const float*, CylWgParams, float*);
 struct CylKernel { CylKernelFn plain, rerun; LdsGrant grant, grant_rerun; };
-static CylKernel cyl_wg = { k_cyl_net_wg, k_cyl_net_wg_rerun }, cyl_w24 = { k_cyl_net_w24, k_cyl_net_w24_rerun },
-                 cyl_w24k = { k_cyl_net_w24k, k_cyl_net_w24k_rerun }, cyl_w24p = { k_cyl_net_w24p, k_cyl_net_w24p_rerun },
-                 cyl_w24a = { k_cyl_net_w24a, k_cyl_net_w24a_rerun }, cyl_w25 = { k_cyl_net_w25, k_cyl_net_w25_rerun },
+static CylKernel cyl_wg = { k_cyl_net_wg, k_cyl_net_wg_rerun }, cyl_w24k = { k_cyl_net_w24k, k_cyl_net_w24k_rerun },
                  cyl_w25t = { k_cyl_net_w25t, k_cyl_net_w25t_rerun };
 
-// The kernel of a stack (rules checked): with sets of the layers' own k_cyl_net_w25t / k_cyl_net_w25 / k_cyl_net_w24a, whatever the sets
-// hold; else by the relu words -- none above 1: k_cyl_net_wg; bit 1 only: k_cyl_net_w24; bit 2 somewhere: the form's kernel.
-static CylKernel& cyl_kernel_for(const int* relu, int form, bool sets24, bool sets25, bool taps)
+// The kernel of a stack (rules checked).  An entry point that takes sets of the layers' own (sets: any of the three arrays) runs
+// k_cyl_net_w25t, whatever the sets hold; else by the relu words -- none above 1: k_cyl_net_wg; bit 2 somewhere in the K-split form:
+// k_cyl_net_w24k; everything else: k_cyl_net_w25t, whose body holds every other layer form.
+static CylKernel& cyl_kernel_for(const int* relu, int form, bool sets)
 {
-    if (taps) return cyl_w25t;
-    if (sets25) return cyl_w25;
-    if (sets24) return cyl_w24a;
+    if (sets) return cyl_w25t;
     bool flagged = false, ksplit = false;
     for (int l = 0; l < WG_LAYERS; l++) {
         flagged |= wg_f24_flagged(relu[l]);
         ksplit |= (relu[l] & BUF_CYL_F24K) != 0;
     }
     if (!flagged) return cyl_wg;
-    if (!ksplit) return cyl_w24;
     if (form == BUF_CYL_FORM_DEFAULT) form = BUF_CYL_FORM_LIBRARY;
-    return form == BUF_CYL_FORM_PASS_SPLIT ? cyl_w24p : cyl_w24k;
+    return ksplit && form == BUF_CYL_FORM_K_SPLIT ? cyl_w24k : cyl_w25t;
 }
 
 // The widths k_cyl_net_wg is built for, stated once: what buf_cylindrical_net_wg accepts and buf_cylindrical_net_wg_supports reports.
@@ -154,7 +150,7 @@ extern "C" int buf_cylindrical_net_w25_flags(const int* cin_host, const int* cou
 }
 
 // Everything an entry point checks about its stack, the kernel's parameters and the kernel, without a device call.  The set arrays as
-// for cyl_check: an entry point that takes one has checked that it is there.  taps_host, order: of the entry points of k_cyl_net_w25t.
+// for cyl_check: an entry point that takes one has checked that it is there.  taps_host, order: of buf_cylindrical_net_w25t and its twin.
 static int cyl_prepare(const float* const* wt_host, const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                        const float* const* wt24_host, const float* const* wt25_host, int form, const char* who, CylWgParams& P, CylKernel*& K,
                        const float* const* taps_host = nullptr, int order = 0)
@@ -168,7 +164,7 @@ static int cyl_prepare(const float* const* wt_host, const float* const* bias_hos
     }
     if (int rc = cyl_check(P.cin, P.cout, P.relu, wt24_host, wt25_host, who, taps_host)) return rc;
     P.only_if = nullptr;
-    K = &cyl_kernel_for(P.relu, form, wt24_host != nullptr, wt25_host != nullptr, taps_host != nullptr);
+    K = &cyl_kernel_for(P.relu, form, wt24_host || wt25_host || taps_host);
     if (K == &cyl_wg) return BUF_OK;                      // takes the buffers and the words as they are
     for (int l = 0; l < WG_LAYERS; l++) {
         if (wt25_host && wt25_host[l]) { P.wt[l] = wt25_host[l]; P.relu[l] = (P.relu[l] & 1) | W25_FLAG; }
@@ -176,7 +172,7 @@ static int cyl_prepare(const float* const* wt_host, const float* const* bias_hos
         else if (P.relu[l] & W24K_FLAG) P.wt[l] += WG_BLOCKS * P.cout[l] * P.cin[l];       // behind the layer's F(2x2) set
         else if (wt24_host && wt24_host[l]) { P.wt[l] = wt24_host[l]; P.relu[l] |= W24K_FLAG; }
         P.relu[l] &= ~WG_F24_FLAG;
-        if (taps_host && P.cout[l] == 128) {              // (the words of k_cyl_net_w25t: csrc/convnet_w25t.hip)
+        if (taps_host && P.cout[l] == 128) {              // (the row-6 words: csrc/convnet_w25t.hip)
             if (taps_host[l]) { P.taps[l] = taps_host[l]; P.relu[l] |= W25T_TAPS; }
             if (order & BUF_CYL_ROW6_FIRST) P.relu[l] |= W25T_FIRST;
         }
@@ -260,8 +256,8 @@ extern "C" int buf_cylindrical_net_wg(const float* x, int npatch, const float* c
     return buf_cylindrical_net_wg_form(x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, BUF_CYL_FORM_DEFAULT, y, stream);
 }
 
-// The same through k_cyl_net_w25 (wt25_host: per layer an optional F(2x5) set) or, without wt25_host, k_cyl_net_w24a; w25t: through
-// k_cyl_net_w25t with taps_host (per layer an optional row-6 tap set) and order
+// The same with sets of the layers' own: wt24_host (per layer an optional F(2x4) set), w25: wt25_host (per layer an optional F(2x5)
+// set), w25t: taps_host (per layer an optional row-6 tap set) and order.  All of them run k_cyl_net_w25t.
 static int cyl_net_own_sets(const char* who, const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
                             const int* cout_host, const int* relu_host, const float* const* wt24_host, const float* const* wt25_host, bool w25, float* y,
                             void* stream, bool w25t = false, const float* const* taps_host = nullptr, int order = 0)
@@ -276,14 +272,14 @@ static int cyl_net_own_sets(const char* who, const float* x, int npatch, const f
     return cyl_launch(*K, x, npatch, P, y, stream);
 }
 
-// x f32[np,Cin0,140] -> y f32[np,32,140] through k_cyl_net_w24a: buf_cylindrical_net_wg with, per layer, an optional F(2x4) set of its own
+// x f32[np,Cin0,140] -> y f32[np,32,140]: buf_cylindrical_net_wg with, per layer, an optional F(2x4) set of its own
 extern "C" int buf_cylindrical_net_wg_all(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
                                           const int* cout_host, const int* relu_host, const float* const* wt24_host, float* y, void* stream)
 {
     return cyl_net_own_sets("buf_cylindrical_net_wg_all", x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, nullptr, false, y, stream);
 }
 
-// x f32[np,Cin0,140] -> y f32[np,32,140] through k_cyl_net_w25: buf_cylindrical_net_wg_all with, per layer, an optional F(2x5) set
+// x f32[np,Cin0,140] -> y f32[np,32,140]: buf_cylindrical_net_wg_all with, per layer, an optional F(2x5) set
 extern "C" int buf_cylindrical_net_w25(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
                                        const int* cout_host, const int* relu_host, const float* const* wt24_host, const float* const* wt25_host, float* y,
                                        void* stream)
@@ -291,7 +287,7 @@ extern "C" int buf_cylindrical_net_w25(const float* x, int npatch, const float* 
     return cyl_net_own_sets("buf_cylindrical_net_w25", x, npatch, wt_host, bias_host, cin_host, cout_host, relu_host, wt24_host, wt25_host, true, y, stream);
 }
 
-// x f32[np,Cin0,140] -> y f32[np,32,140] through k_cyl_net_w25t: buf_cylindrical_net_w25 with, per 128-output layer, an optional row-6 tap
+// x f32[np,Cin0,140] -> y f32[np,32,140]: buf_cylindrical_net_w25 with, per 128-output layer, an optional row-6 tap
 // set, and the order of the two rounds there
 extern "C" int buf_cylindrical_net_w25t(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host, const int* cin_host,
                                         const int* cout_host, const int* relu_host, const float* const* wt24_host, const float* const* wt25_host,

@@ -1,4 +1,5 @@
-// A11 dense part -- k_cyl_net_w24: k_cyl_net_wg (csrc/convnet_wg.hip) with the layers of 128 output channels in the Winograd
+// A11 dense part -- w24_layer_pair, a layer form of the fused kernel (cyl_net_w25t_body, csrc/convnet_w25t.hip, and the K-split body of
+// csrc/convnet_w24k.hip): the layers of 128 output channels of k_cyl_net_wg (csrc/convnet_wg.hip) in the Winograd
 // F(2x4, 3x3) domain: tiles of 2 rows x 4 azimuth columns (20 = 5 x 4), a 4 x 6 input window, 4 x 6 = 24 components,
 //     Y = A2^T [ sum_c (G2 g G4^T)[c] (.) (B2^T d[c] B4) ] A4           (F(2,3) down the rows as before, F(4,3) along the azimuth:
 //                                                                         the points 0, +-1, +-2, infinity)
@@ -388,47 +389,8 @@ __device__ __forceinline__ void w24_layer_pair(float* __restrict__ act, const fl
     }
 }
 
-__device__ __forceinline__ void cyl_net_w24_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
-{
-    float* act = lds;                                // [128][160]
-    const int patch = blockIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    wg_load_input(x, P, act, patch);
-    WgAddrPark pk;
-    W24AddrPark pk24;
-    {
-        int lane0 = threadIdx.x & (WAVE - 1);
-        asm volatile("" : "+v"(lane0));
-        wg_park_addresses(act, lane0 & 15, lane0 >> 4, pk);
-        w24_park_addresses(act, lane0 & 15, lane0 >> 4, pk24);
-    }
-#pragma unroll 1
-    for (int l = 0; l < WG_LAYERS; l++) {
-        const int cin = P.cin[l], cout = P.cout[l];
-        if (cout == 128) w24_layer_pair(act, P.wt[l], P.bias[l], cin, P.relu[l], w, pk, pk24);
-        else if (cout == 64) wg_layer_msplit(act, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-        else if (l < WG_LAYERS - 1) wg_layer_mksplit<false>(act, nullptr, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-        else wg_layer_mksplit<true>(act, y + (size_t)patch * cout * 140, P.wt[l], P.bias[l], cin, cout, P.relu[l], w, pk);
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    cyl_net_w24_body(x, P, y, lds);
-}
-
-// The masked re-run of buf_cylindrical_net_split_safe, under its own kernel name (see k_cyl_net_wg_rerun)
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24_rerun(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    if (P.only_if[blockIdx.x] == 0) return;
-    cyl_net_w24_body(x, P, y, lds);
-}
-
 // Host helper: filters w [Cout][Cin][3][3] (BN folded) -> U = G2 g G4^T in fp64, rounded once: 4 row x 6 column components in the
-// tiling k_cyl_net_w24 streams,
+// tiling w24_layer_pair streams,
 //     out[24 * Cout * Cin] = [pair][i][k-step][ n2: [lk][li][q] | n2: [lk][li][j - 3] ]
 // with q = 0..3 the column components j = 0, 1, 2, 5 (2 x 256 floats) and then j = 3, 4 (2 x 128 floats) of
 // U[i][j][16 (2 pair + n2) + li][4 ks + lk].  No device work.

@@ -1,9 +1,9 @@
-// A11 dense part -- k_cyl_net_w24a: k_cyl_net_w24p (csrc/convnet_w24p.hip) with F(2x4, 3x3) tiles in EVERY layer the caller hands an
-// F(2x4) filter set for -- layer 0 and the 32-output layers of the released stack, which k_cyl_net_w24p still runs in the F(2x2) form at
-// 38 matrix instructions per (k-step, N-tile).  With all eight layers at 24 + 6 the released stack issues 30 x 736 = 22 080 matrix
-// instructions per patch (k_cyl_net_w24p: 22 848).
+// A11 dense part -- w24a_layer_psplit32, a layer form of the fused kernel (cyl_net_w25t_body, csrc/convnet_w25t.hip): F(2x4, 3x3) tiles in
+// EVERY layer the caller hands an F(2x4) filter set for -- layer 0 and the 32-output layers of the released stack, which a stack without
+// sets of its own runs in the F(2x2) form at 38 matrix instructions per (k-step, N-tile).  With all eight layers at 24 + 6 the released
+// stack issues 30 x 736 = 22 080 matrix instructions per patch (without the sets: 22 848).
 //
-// The layer forms, picked per layer from the widths and the kernel's relu word (bit 2 here means "P.wt[l] IS the layer's F(2x4) set";
+// The F(2x4) layer forms, picked per layer from the widths and the kernel's relu word (bit 2 there means "P.wt[l] IS the layer's F(2x4) set";
 // the launcher sets it for the layers that carry BUF_CYL_F24K and for those with a set of their own, see cyl_prepare, csrc/cnn_launch.hip):
 //   128 outputs                 w24_layer_pair (csrc/convnet_w24.hip), unchanged
 //   64 outputs, bit 2           w24p_layer_psplit (csrc/convnet_w24p.hip), unchanged: its k-loop runs Cin / 16 times, so Cin = 48 (layer 0:
@@ -210,49 +210,4 @@ __device__ __forceinline__ void w24a_layer_psplit32(float* __restrict__ act, flo
     __syncthreads();                                 // the partial outputs are in place AND every wavefront has finished reading the input
     if (w == 0) w24a_take<0, GLB>(f, Yb, relu, act, out_glb, lane_s);
     else if (w == 1) w24a_take<1, GLB>(f, Yb, relu, act, out_glb, lane_s);
-}
-
-// cyl_net_w24p_body with the 32-output form above; bit 2 of P.relu[l]: P.wt[l] is the layer's F(2x4) set
-__device__ __forceinline__ void cyl_net_w24a_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
-{
-    float* act = lds;                                // [128][160]
-    const int patch = blockIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    wg_load_input(x, P, act, patch);
-    WgAddrPark pk;
-    W24AddrPark pk24;
-    {
-        int lane0 = threadIdx.x & (WAVE - 1);
-        asm volatile("" : "+v"(lane0));
-        wg_park_addresses(act, lane0 & 15, lane0 >> 4, pk);
-        w24_park_addresses(act, lane0 & 15, lane0 >> 4, pk24);
-    }
-#pragma unroll 1
-    for (int l = 0; l < WG_LAYERS; l++) {
-        const int cin = P.cin[l], cout = P.cout[l], relu = P.relu[l] & 1;
-        const bool f24 = (P.relu[l] & W24K_FLAG) != 0;
-        float* yp = y + (size_t)patch * cout * 140;
-        if (cout == 128) w24_layer_pair(act, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (cout == 64 && f24) w24p_layer_psplit(act, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (cout == 64) wg_layer_msplit(act, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        else if (f24 && l < WG_LAYERS - 1) w24a_layer_psplit32<false>(act, nullptr, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (f24) w24a_layer_psplit32<true>(act, yp, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (l < WG_LAYERS - 1) wg_layer_mksplit<false>(act, nullptr, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        else wg_layer_mksplit<true>(act, yp, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24a(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    cyl_net_w24a_body(x, P, y, lds);
-}
-
-// The masked re-run of buf_cylindrical_net_split_safe_all, under its own kernel name (see k_cyl_net_wg_rerun)
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24a_rerun(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    if (P.only_if[blockIdx.x] == 0) return;
-    cyl_net_w24a_body(x, P, y, lds);
 }

@@ -1,5 +1,5 @@
-// A11 dense part -- k_cyl_net_w24k: k_cyl_net_w24 (csrc/convnet_w24.hip) with the F(2x4, 3x3) form in the layers of 64 output channels
-// as well, where Cin is a multiple of 64 (the released stack: 64 -> 64 twice and 128 -> 64; 256 of its 736 (k-step, N-tile) units, at
+// A11 dense part -- k_cyl_net_w24k: the F(2x4, 3x3) form of the 128-output layers (csrc/convnet_w24.hip) in the layers of 64 output
+// channels as well, where Cin is a multiple of 64 (the released stack: 64 -> 64 twice and 128 -> 64; 256 of its 736 (k-step, N-tile) units, at
 // 30 instead of 38 matrix instructions each: 22 848 per patch = 38 x 96 + 30 x 640 against 24 896).
 //
 // One F(2x4) M-tile carries the whole map, so the M split of wg_layer_msplit has nothing to split; the four wavefronts keep the
@@ -21,7 +21,7 @@
 // and layer this was left as it is and has not been measured on its own.)
 //
 // Opt-in: bit 2 of relu_host[l] (BUF_CYL_F24K) on a layer with 64 output channels and Cin % 64 == 0 says that the layer's buffer holds
-// the F(2x4) set (buf_winograd_f24_tile_weights) behind the F(2x2) set; the bit-1 rule of k_cyl_net_w24 holds beside it.  Stacks
+// the F(2x4) set (buf_winograd_f24_tile_weights) behind the F(2x2) set; the bit-1 rule of the 128-output layers holds beside it.  Stacks
 // without bit 2 never come here.
 #include "common.h"
 
@@ -112,7 +112,8 @@ __device__ __forceinline__ void w24k_layer_ksplit(float* __restrict__ act, const
     wg_store_row6<false>(Q[8], 2 * pair + half, relu, act, nullptr, lane_s & 15, lane_s >> 4);
 }
 
-// cyl_net_w24_body with one more layer form: P.relu[l] keeps bit 2 (W24K_FLAG) beside the ReLU bit
+// The body of the K-split stacks, the one form cyl_net_w25t_body (csrc/convnet_w25t.hip) does not hold: P.relu[l] keeps bit 2
+// (W24K_FLAG) beside the ReLU bit
 __device__ __forceinline__ void cyl_net_w24k_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
 {
     float* act = lds;                                // [128][160]

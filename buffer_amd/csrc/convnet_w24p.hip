@@ -1,4 +1,5 @@
-// A11 dense part -- k_cyl_net_w24p: k_cyl_net_w24k (csrc/convnet_w24k.hip) with its flagged 64-output layers in the "pass split" form.
+// A11 dense part -- w24p_layer_psplit, a layer form of the fused kernel (cyl_net_w25t_body, csrc/convnet_w25t.hip): the flagged
+// 64-output layers of k_cyl_net_w24k (csrc/convnet_w24k.hip) in the "pass split" form.
 // The same layers (64 output channels, Cin % 64 == 0, bit 2 of the relu word), the same filter buffers, the same 24 + 6 matrix
 // instructions per (k-step, N-tile) -- 22 848 per patch of the released stack -- but split over the four wavefronts by ROW COMPONENT
 // instead of by K half:
@@ -315,45 +316,4 @@ __device__ __forceinline__ void w24p_layer_psplit(float* __restrict__ act, const
     else w24p_take<3>(f, act, lane_s, Yk);
     w24_store_tile(Yk, w, relu, act, lane_s & 15, lane_s >> 4);
     wg_store_row6<false>(Yb, w, relu, act, nullptr, lane_s & 15, lane_s >> 4);
-}
-
-// cyl_net_w24k_body with the pass-split form in the layers that carry bit 2
-__device__ __forceinline__ void cyl_net_w24p_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
-{
-    float* act = lds;                                // [128][160]
-    const int patch = blockIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    wg_load_input(x, P, act, patch);
-    WgAddrPark pk;
-    W24AddrPark pk24;
-    {
-        int lane0 = threadIdx.x & (WAVE - 1);
-        asm volatile("" : "+v"(lane0));
-        wg_park_addresses(act, lane0 & 15, lane0 >> 4, pk);
-        w24_park_addresses(act, lane0 & 15, lane0 >> 4, pk24);
-    }
-#pragma unroll 1
-    for (int l = 0; l < WG_LAYERS; l++) {
-        const int cin = P.cin[l], cout = P.cout[l], relu = P.relu[l] & 1;
-        if (cout == 128) w24_layer_pair(act, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (cout == 64 && (P.relu[l] & W24K_FLAG)) w24p_layer_psplit(act, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (cout == 64) wg_layer_msplit(act, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        else if (l < WG_LAYERS - 1) wg_layer_mksplit<false>(act, nullptr, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        else wg_layer_mksplit<true>(act, y + (size_t)patch * cout * 140, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24p(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    cyl_net_w24p_body(x, P, y, lds);
-}
-
-// The masked re-run of buf_cylindrical_net_split_safe, under its own kernel name (see k_cyl_net_wg_rerun)
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w24p_rerun(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    if (P.only_if[blockIdx.x] == 0) return;
-    cyl_net_w24p_body(x, P, y, lds);
 }

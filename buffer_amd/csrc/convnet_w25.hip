@@ -1,8 +1,8 @@
-// A11 dense part -- k_cyl_net_w25: k_cyl_net_w24a (csrc/convnet_w24a.hip) with F(2x5, 3x3) tiles in every layer the caller hands an
-// F(2x5) filter set for.  Tiles of 2 rows x 5 azimuth columns carry the 7 x 20 map with exactly 4 x 4 = 16 regular tiles -- ONE full
+// A11 dense part -- w25_layer_psplit, a layer form of the fused kernel (cyl_net_w25t_body, csrc/convnet_w25t.hip): F(2x5, 3x3) tiles in
+// every layer the caller hands an F(2x5) filter set for.  Tiles of 2 rows x 5 azimuth columns carry the 7 x 20 map with exactly 4 x 4 = 16 regular tiles -- ONE full
 // M-tile, row 7 of the bottom tile row dropped -- where F(2x4) needs 17.5 tiles of 8 outputs, hence its special sixteenth lane and its
 // direct round of row 6, columns 0..15.  4 row components x 7 column components = 28 matrix instructions per (k-step, N-tile) against
-// 24 + 6; no direct round, no special lane, no row-6 store path.  Every layer without such a set runs as in k_cyl_net_w24a.
+// 24 + 6; no direct round, no special lane, no row-6 store path.  Every layer without such a set runs in its F(2x4) or F(2x2) form.
 //
 //     Y = A2^T [ sum_c (G2 g G5^T)[c] (.) (B2^T d[c] B5) ] A5        F(2,3) down the rows as before, F(5,3) along the azimuth on the seven
 //                                                                    points 0, +-1, +-2, +-1/2 (tools/f25_restate.py picked them)
@@ -327,60 +327,8 @@ __device__ __forceinline__ void w25_layer_psplit(float* __restrict__ act, float*
     }
 }
 
-// cyl_net_w24a_body with the F(2x5) form in the layers whose relu word carries W25_FLAG
-__device__ __forceinline__ void cyl_net_w25_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
-{
-    float* act = lds;                                // [128][160]
-    const int patch = blockIdx.x;
-    const int w0 = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    wg_load_input(x, P, act, patch);
-    WgAddrPark pk;
-    W24AddrPark pk24;
-    {
-        int lane0 = threadIdx.x & (WAVE - 1);
-        asm volatile("" : "+v"(lane0));
-        wg_park_addresses(act, lane0 & 15, lane0 >> 4, pk);
-        w24_park_addresses(act, lane0 & 15, lane0 >> 4, pk24);
-    }
-#pragma unroll 1
-    for (int l = 0; l < WG_LAYERS; l++) {
-        // What depends on the wavefront number is formed per layer, like what depends on the lane number: hoisted out of the layer loop
-        // for every layer form at once it spills scalar registers
-        int w = w0;
-        asm volatile("" : "+s"(w));
-        const int cin = P.cin[l], cout = P.cout[l], relu = P.relu[l] & 1;
-        const bool f24 = (P.relu[l] & W24K_FLAG) != 0, f25 = (P.relu[l] & W25_FLAG) != 0;
-        float* yp = y + (size_t)patch * cout * 140;
-        if (f25 && cout == 64) w25_layer_psplit<4, false>(act, nullptr, P.wt[l], P.bias[l], cin, relu, w);
-        else if (f25 && l < WG_LAYERS - 1) w25_layer_psplit<2, false>(act, nullptr, P.wt[l], P.bias[l], cin, relu, w);
-        else if (f25) w25_layer_psplit<2, true>(act, yp, P.wt[l], P.bias[l], cin, relu, w);
-        else if (cout == 128) w24_layer_pair(act, P.wt[l], P.bias[l], cin, relu, w0, pk, pk24);
-        else if (cout == 64 && f24) w24p_layer_psplit(act, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (cout == 64) wg_layer_msplit(act, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        else if (f24 && l < WG_LAYERS - 1) w24a_layer_psplit32<false>(act, nullptr, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (f24) w24a_layer_psplit32<true>(act, yp, P.wt[l], P.bias[l], cin, relu, w, pk, pk24);
-        else if (l < WG_LAYERS - 1) wg_layer_mksplit<false>(act, nullptr, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        else wg_layer_mksplit<true>(act, yp, P.wt[l], P.bias[l], cin, cout, relu, w, pk);
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w25(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    cyl_net_w25_body(x, P, y, lds);
-}
-
-// The masked re-run of buf_cylindrical_net_split_safe_w25, under its own kernel name (see k_cyl_net_wg_rerun)
-__global__ void __launch_bounds__(WG_THREADS, 2) k_cyl_net_w25_rerun(const float* __restrict__ x, CylWgParams P, float* __restrict__ y)
-{
-    extern __shared__ float lds[];
-    if (P.only_if[blockIdx.x] == 0) return;
-    cyl_net_w25_body(x, P, y, lds);
-}
-
 // Host helper: filters w [Cout][Cin][3][3] (BN folded) -> U = G2 g G5^T in fp64, rounded once: 4 row x 7 column components (the points
-// 0, +-1, +-2, +-1/2 in this order) in the tiling k_cyl_net_w25 streams,
+// 0, +-1, +-2, +-1/2 in this order) in the tiling w25_layer_psplit streams,
 //     out[28 * Cout * Cin] = [i][k-step][N-tile][ [lk][li][j = 0..3] | [lk][li][j = 4, 5] | [lk][li][j = 6] ]
 // (256 + 128 + 64 floats: a lane's seven components of a block row are a 16-, an 8- and a 4-byte buffer load) of
 // U[i][j][16 n + li][4 ks + lk].  No device work.

@@ -1,5 +1,6 @@
-// A11 dense part -- k_cyl_net_w25t: k_cyl_net_w25 (csrc/convnet_w25.hip) with two changes in the layers of 128 output channels
-// (w24_layer_pair, csrc/convnet_w24.hip), each behind a bit of the kernel's relu word that only the launcher sets:
+// A11 dense part -- k_cyl_net_w25t, the fused kernel of every layer form (cyl_net_w25t_body below lists them), and the forms this file
+// adds: two changes in the layers of 128 output channels (w24_layer_pair, csrc/convnet_w24.hip), each behind a bit of the kernel's relu
+// word that only the launcher sets:
 //
 //   W25T_TAPS    the direct round of output row 6, columns 0..15 runs on taps the HOST formed.  Row 6's window is the map rows 5, 6 and
 //                a padding row, so its six taps are rows 0 and 1 of the 3 x 3 filter as they stand,
@@ -13,8 +14,8 @@
 //                accumulation registers, and the Winograd round's 64 go from its last fold straight to the barrier and the stores
 //                (w24_layer_pair parks and fetches all 72: 128 more copies between the register files per wavefront and layer).
 //
-// A layer whose word carries neither bit runs w24_layer_pair itself, and every other layer form is cyl_net_w25_body's: without a tap
-// set and without the order bit the kernel returns k_cyl_net_w25's bits.
+// A layer whose word carries neither bit runs w24_layer_pair itself: without a tap set and without the order bit the kernel returns
+// the bits of the stack without them.
 //
 // Accumulators of the new direct round: one per AZIMUTH tap and N-tile, as in w24_round_direct (the filter rows a = 0, 1 add up in it, K
 // ascending), summed once at the end, (acc_0 + acc_1) + acc_2; the bias starts acc_2.  One per N-tile would put the six matrix
@@ -185,7 +186,15 @@ __device__ __forceinline__ void w25t_layer_pair(float* __restrict__ act, const f
     }
 }
 
-// cyl_net_w25_body with the forms above in the 128-output layers whose relu word carries W25T_TAPS or W25T_FIRST
+// The one body of the fused kernel: every layer form but the K split (csrc/convnet_w24k.hip) and the pinned all-F(2x2) stack
+// (csrc/convnet_wg.hip) is a branch of the ladder below, picked per layer from the widths and the kernel's relu word as cyl_prepare
+// (csrc/cnn_launch.hip) writes it.  To add a form, add a layer function and a branch in front of the forms it replaces; a word without
+// the new bit then runs what it ran before.
+//   W25_FLAG                    w25_layer_psplit (csrc/convnet_w25.hip): P.wt[l] is the layer's F(2x5) set; 64 or 32 outputs
+//   128 outputs                 w25t_layer_pair above with W25T_TAPS or W25T_FIRST, else w24_layer_pair (csrc/convnet_w24.hip)
+//   64 outputs, W24K_FLAG       w24p_layer_psplit (csrc/convnet_w24p.hip): P.wt[l] is the layer's F(2x4) set
+//   32 outputs, W24K_FLAG       w24a_layer_psplit32 (csrc/convnet_w24a.hip)
+//   anything else               wg_layer_msplit / wg_layer_mksplit (csrc/convnet_wg.hip): the F(2x2) form
 __device__ __forceinline__ void cyl_net_w25t_body(const float* __restrict__ x, const CylWgParams& P, float* __restrict__ y, float* __restrict__ lds)
 {
     float* act = lds;                                // [128][160]
@@ -202,7 +211,9 @@ __device__ __forceinline__ void cyl_net_w25t_body(const float* __restrict__ x, c
     }
 #pragma unroll 1
     for (int l = 0; l < WG_LAYERS; l++) {
-        int w = w0;                                  // (formed per layer: see cyl_net_w25_body)
+        // What depends on the wavefront number is formed per layer, like what depends on the lane number: hoisted out of the layer loop
+        // for every layer form at once it spills scalar registers
+        int w = w0;
         asm volatile("" : "+s"(w));
         const int cin = P.cin[l], cout = P.cout[l], relu = P.relu[l] & 1;
         const bool f24 = (P.relu[l] & W24K_FLAG) != 0, f25 = (P.relu[l] & W25_FLAG) != 0;

@@ -91,7 +91,7 @@ static int cyl_split_safe_own_sets(const char* who, const char* who_f32, const f
     return cyl_split_safe(x, npatch, wt_split_host, bias_host, cin_host, cout_host, relu_host, *K, P, head_params, y_or_equi, desc, status_dev, flags_ws, stream);
 }
 
-// The same through k_cyl_net_w24a (csrc/convnet_w24a.hip): wt24_host as for buf_cylindrical_net_wg_all, the re-run is k_cyl_net_w24a_rerun
+// The same with wt24_host as for buf_cylindrical_net_wg_all; the re-run of every entry point with sets is k_cyl_net_w25t_rerun
 extern "C" int buf_cylindrical_net_split_safe_all(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                                   const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                                   const float* const* wt24_host, const float* head_params, float* y_or_equi, float* desc,
@@ -101,7 +101,7 @@ extern "C" int buf_cylindrical_net_split_safe_all(const float* x, int npatch, co
                                    cin_host, cout_host, relu_host, wt24_host, nullptr, false, head_params, y_or_equi, desc, status_dev, flags_ws, stream);
 }
 
-// The same through k_cyl_net_w25 (csrc/convnet_w25.hip): wt24_host and wt25_host as for buf_cylindrical_net_w25, the re-run is k_cyl_net_w25_rerun
+// The same with wt24_host and wt25_host as for buf_cylindrical_net_w25
 extern "C" int buf_cylindrical_net_split_safe_w25(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                                   const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                                   const float* const* wt24_host, const float* const* wt25_host, const float* head_params,
@@ -111,7 +111,7 @@ extern "C" int buf_cylindrical_net_split_safe_w25(const float* x, int npatch, co
                                    cin_host, cout_host, relu_host, wt24_host, wt25_host, true, head_params, y_or_equi, desc, status_dev, flags_ws, stream);
 }
 
-// The same through k_cyl_net_w25t (csrc/convnet_w25t.hip): taps_host and order as for buf_cylindrical_net_w25t, the re-run is k_cyl_net_w25t_rerun
+// The same with taps_host and order as for buf_cylindrical_net_w25t
 extern "C" int buf_cylindrical_net_split_safe_w25t(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                                    const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                                    const float* const* wt24_host, const float* const* wt25_host, const float* const* taps_host,

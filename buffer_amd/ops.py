@@ -1131,17 +1131,17 @@ def winograd_f25_tile_weights(w):
 
 
 F24_FLAG = 2          # relu_host[l] bit 1 of buf_cylindrical_net_wg: the layer's buffer holds the F(2x4) set behind the F(2x2) set
-F24K_FLAG = 4         # bit 2: the same for a layer with 64 output channels and Cin % 64 == 0 (k_cyl_net_w24k / k_cyl_net_w24p)
-F24P_DEFAULT = True   # the form of the bit-2 layers: pass split (k_cyl_net_w24p) | K split (k_cyl_net_w24k); profiles/f24p_ab.md
-# What a net built without a form argument runs (k_cyl_net_w24a, csrc/convnet_w24a.hip; profiles/f24a_ab.md): F(2x4) tiles in 'all'
-# layers; 'out64': only in the 64-output layers k_cyl_net_w24p leaves in the F(2x2) form (the released stack: layer 0); 'out32': only in the
-# 32-output layers; 'off' or None: k_cyl_net_w24p as it is.  The argument f24a= of the two classes picks one per net.
+F24K_FLAG = 4         # bit 2: the same for a layer with 64 output channels and Cin % 64 == 0 (K split or pass split, as the call's form says)
+F24P_DEFAULT = True   # the form of the bit-2 layers: pass split (csrc/convnet_w24p.hip) | K split (csrc/convnet_w24k.hip); profiles/f24p_ab.md
+# F(2x4) sets of the layers' own (csrc/convnet_w24a.hip; profiles/f24a_ab.md): F(2x4) tiles in 'all' layers; 'out64': only in the
+# 64-output layers the flags leave in the F(2x2) form (the released stack: layer 0); 'out32': only in the 32-output layers; 'off' or
+# None: those layers stay in the F(2x2) form.  The argument f24a= of the two classes picks one per net.
 F24A_DEFAULT = 'all'
 F24A_PARTS = {'all': (64, 32), 'out64': (64,), 'out32': (32,), 'off': (), None: ()}
 
 
-# F(2x5) tiles (k_cyl_net_w25, csrc/convnet_w25.hip; profiles/f25_ab.md): the layers of these output widths run on an F(2x5) set of their
-# own -- 'all': the 64- and the 32-output layers, 'out64' / 'out32': one of the two, 'off' or None: k_cyl_net_w24a as it is, bit for bit.
+# F(2x5) tiles (csrc/convnet_w25.hip; profiles/f25_ab.md): the layers of these output widths run on an F(2x5) set of their
+# own -- 'all': the 64- and the 32-output layers, 'out64' / 'out32': one of the two, 'off' or None: no such layer, the other forms' bits.
 # The 128-output form ('out128') is not built.  The argument f25= of the two classes picks one per net.  The default is the part that met
 # both rules of the A/B (profiles/f25_ab.md): the 64-output layers; the 32-output form measured slower than its F(2x4) twin and stays off.
 F25_DEFAULT = 'out64'
@@ -1156,31 +1156,11 @@ def form_parts(name, value, default, table):
     return table[value]
 
 
-def cyl_f25_parts(f24, f24k, f24p, f25):
-    """The output widths whose layers get an F(2x5) set (k_cyl_net_w25).  An explicit f24 / f24k / f24p asks for one of the older
-    kernels: no such layers then, and asking for both is an error."""
-    explicit = not (f24 is None and f24k is None and f24p is None)
-    if f25 == 'out128':
-        raise ValueError("f25 = 'out128': the 128-output layers have no F(2x5) form (csrc/convnet_w25.hip)")
-    parts = form_parts('f25', f25, None if explicit else F25_DEFAULT, F25_PARTS)
-    if parts and explicit and not (f24 in (None, True) and f24k in (None, True) and f24p in (None, True)):
-        raise ValueError("f25 goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
-    return parts
-
-
-def cyl_f25_filters(layers, parts, device):
-    """Per layer the F(2x5) set in a buffer of its own (a tensor on `device`) where the layer has one of the output widths `parts` and
-    Cin % 16 == 0, else None; and the pointer array buf_cylindrical_net_w25 takes."""
-    sets = [torch.from_numpy(winograd_f25_tile_weights(w)).to(device)
-            if (w.shape[0] in parts and w.shape[0] in (32, 64) and w.shape[1] % 16 == 0) else None for w, _, _ in layers]
-    return sets, (C.c_void_p * len(sets))(*[None if t is None else t.data_ptr() for t in sets])
-
-
-# Row 6 of the 128-output layers (k_cyl_net_w25t, csrc/convnet_w25t.hip; profiles/cyl_taps_ab.md): 'taps': the direct round of output row 6
+# Row 6 of the 128-output layers (csrc/convnet_w25t.hip; profiles/cyl_taps_ab.md): 'taps': the direct round of output row 6
 # runs on the filter rows 0 and 1 as the host tiled them (a set of 6 Cout Cin floats per layer) instead of forming its taps per patch from
 # three Winograd block rows; 'order': the direct round runs in front of the Winograd round, whose 64 outputs per lane then need no parking;
-# 'both' (or 'all'); 'off' or None: k_cyl_net_w25 (or whatever the other arguments pick) as it is, bit for bit.  The argument row6= of the two classes
-# picks one per net; a net built with any other form argument keeps that kernel as it was unless row6= asks.  The default is what met both
+# 'both' (or 'all'); 'off' or None: the 128-output layers as the other arguments leave them, bit for bit.  The argument row6= of the two classes
+# picks one per net; a net built with any other form argument keeps its layer forms as they were unless row6= asks.  The default is what met both
 # rules of the A/B (profiles/cyl_taps_ab.md): both parts together.
 ROW6_DEFAULT = 'both'
 ROW6_PARTS = {'both': (True, True), 'all': (True, True), 'taps': (True, False), 'order': (False, True), 'off': (False, False), None: (False, False)}
@@ -1197,27 +1177,10 @@ def cyl_row6_tile_taps(w):
     return np.ascontiguousarray(np.transpose(t, (0, 1, 4, 2, 3, 5))).reshape(-1)                # [pair, ks, q, lk, li, e]
 
 
-def cyl_row6_parts(f24, f24k, f24p, row6, f24a=None, f25=None):
-    """(taps, order first) of the 128-output layers.  Any explicit form argument asks for one of the kernels before this one: neither
-    part then unless row6 says so, and asking for a part with f24, f24k or f24p false is an error."""
-    explicit = not (f24 is None and f24k is None and f24p is None and f24a is None and f25 is None)
-    parts = form_parts('row6', row6, None if explicit else ROW6_DEFAULT, ROW6_PARTS)
-    if any(parts) and not (f24 in (None, True) and f24k in (None, True) and f24p in (None, True)):
-        raise ValueError("row6 goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
-    return parts
-
-
-def cyl_row6_taps(layers, flags, taps, device):
-    """Per layer the row-6 tap set in a buffer of its own (a tensor on `device`) where `taps` and the layer carries the F(2x4) flag of the
-    128-output layers, else None; and the pointer array buf_cylindrical_net_w25t takes."""
-    sets = [torch.from_numpy(cyl_row6_tile_taps(w)).to(device) if (taps and flag == F24_FLAG) else None for (w, _, _), flag in zip(layers, flags)]
-    return sets, (C.c_void_p * len(sets))(*[None if t is None else t.data_ptr() for t in sets])
-
-
 def cyl_layer_filters(w, f24k=True):
     """The fp32 kernel's filter buffer of one layer and its F(2x4) flag: layers with 128 output channels run in the F(2x4) form
-    (flag 2) and, with f24k, so do the layers with 64 output channels whose Cin is a multiple of 64 (flag 4: k_cyl_net_w24k or
-    k_cyl_net_w24p, as the call's form says); both carry that set behind the F(2x2) one."""
+    (flag 2) and, with f24k, so do the layers with 64 output channels whose Cin is a multiple of 64 (flag 4: K split or pass split,
+    as the call's form says); both carry that set behind the F(2x2) one."""
     wt = winograd_tile_weights(w)
     cout, cin = w.shape[0], w.shape[1]
     if cout == 128:
@@ -1229,44 +1192,53 @@ def cyl_layer_filters(w, f24k=True):
     return np.concatenate([wt, winograd_f24_tile_weights(w)]), flag
 
 
-def cyl_f24a_parts(f24, f24k, f24p, f24a):
-    """The output widths whose unflagged layers get an F(2x4) set of their own (k_cyl_net_w24a), and the three older arguments with
-    their defaults filled in.  An explicit f24 / f24k / f24p asks for one of the older kernels: no such layers then."""
-    explicit = not (f24 is None and f24k is None and f24p is None)
+def cyl_forms(f24, f24k, f24p, f24a, f25, row6):
+    """The form arguments of the two net classes, resolved once -> (f24, f24k, f24p with their defaults filled in, the output widths
+    whose unflagged layers get an F(2x4) set of their own, the output widths whose layers get an F(2x5) set, (taps, order first) of the
+    128-output layers).  An explicit older argument switches the newer defaults off: f24 / f24k / f24p those of f24a and f25, any of the
+    five that of row6.  Asking for a newer form with f24, f24k or f24p false is an error."""
+    older = not (f24 is None and f24k is None and f24p is None)
+    kept = f24 in (None, True) and f24k in (None, True) and f24p in (None, True)
+    if f25 == 'out128':
+        raise ValueError("f25 = 'out128': the 128-output layers have no F(2x5) form (csrc/convnet_w25.hip)")
+    parts = {}
+    for name, value, default, table in (('f25', f25, None if older else F25_DEFAULT, F25_PARTS),
+                                        ('row6', row6, None if older or f24a is not None or f25 is not None else ROW6_DEFAULT, ROW6_PARTS),
+                                        ('f24a', f24a, None if older else F24A_DEFAULT, F24A_PARTS)):
+        parts[name] = form_parts(name, value, default, table)
+        if any(parts[name]) and not kept:
+            raise ValueError(name + " goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
     f24, f24k, f24p = (True if f24 is None else f24), (True if f24k is None else f24k), (F24P_DEFAULT if f24p is None else f24p)
-    parts = form_parts('f24a', f24a, None if explicit else F24A_DEFAULT, F24A_PARTS)
-    if parts and not (f24 and f24k and f24p):
-        raise ValueError("f24a goes with the default forms of the other layers (f24, f24k, f24p left alone or true)")
-    return f24, f24k, f24p, parts
+    return f24, f24k, f24p, parts['f24a'], parts['f25'], parts['row6']
 
 
-def cyl_f24a_filters(layers, flags, parts, device):
-    """Per layer the F(2x4) set in a buffer of its own (a tensor on `device`) where the layer carries no F(2x4) flag and has one of the
-    output widths `parts`, else None; and the pointer array buf_cylindrical_net_wg_all takes."""
-    sets = [torch.from_numpy(winograd_f24_tile_weights(w)).to(device)
-            if (flag == 0 and w.shape[0] in parts and w.shape[0] in (32, 64) and w.shape[1] % 16 == 0) else None
-            for (w, _, _), flag in zip(layers, flags)]
+def cyl_own_sets(layers, flags, takes, tiler, device):
+    """Per layer `tiler(w)` in a buffer of its own (a tensor on `device`) where `takes(w, flag)`, else None; and the pointer array the
+    entry points with sets take."""
+    sets = [torch.from_numpy(tiler(w)).to(device) if takes(w, flag) else None for (w, _, _), flag in zip(layers, flags)]
     return sets, (C.c_void_p * len(sets))(*[None if t is None else t.data_ptr() for t in sets])
 
 
 class CylindricalNet:
-    """Device weights of Cylindrical_Net for csrc/convnet_wg.hip / csrc/convnet_w24.hip / csrc/convnet_w24k.hip / csrc/convnet_w24p.hip /
-    csrc/convnet_w24a.hip: per layer U = G g G^T in the kernel's tiling (layers in the F(2x4) form: that set behind it, flagged in the relu
-    word; for k_cyl_net_w24a the remaining layers' F(2x4) sets in buffers of their own, `wt24`), biases."""
+    """Device weights of Cylindrical_Net for the fused fp32 kernels (csrc/convnet_w*.hip): per layer U = G g G^T in the kernel's tiling
+    (layers flagged for the F(2x4) form: that set behind it, flagged in the relu word), the sets of the layers' own in buffers of their
+    own (`wt24`: F(2x4), `wt25`: F(2x5), `taps`: row 6), biases."""
 
     def __init__(self, layers, device, f24=None, f24k=None, f24p=None, f24a=None, f25=None, row6=None):
-        """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  No form argument: k_cyl_net_w24a with F(2x4)
-        tiles in every layer (F24A_DEFAULT; f24a = 'all' | 'out64' | 'out32' | 'off' picks the parts).  An explicit f24, f24k or f24p gives
-        one of the older kernels with the defaults f24 = f24k = True, f24p = F24P_DEFAULT: f24 = False: the F(2x2) form in every
-        layer (k_cyl_net_wg; the cross-check of the tests and the A side of an A/B); f24k = False: F(2x4) in the 128-output layers
-        only (k_cyl_net_w24); f24p: the flagged 64-output layers in the pass-split form (k_cyl_net_w24p), else K split (k_cyl_net_w24k).
-        f25 = 'all' | 'out64' | 'out32' | 'off' (F25_DEFAULT): F(2x5) tiles in the layers of those output widths (k_cyl_net_w25); the
-        other layers as the remaining arguments say.
-        row6 = 'both' | 'taps' | 'order' | 'off' (ROW6_DEFAULT): host-formed row-6 taps and / or the direct round first in the 128-output
-        layers (k_cyl_net_w25t)."""
-        parts25 = cyl_f25_parts(f24, f24k, f24p, f25)
-        row6_taps, row6_first = cyl_row6_parts(f24, f24k, f24p, row6, f24a, f25)
-        f24, f24k, f24p, parts = cyl_f24a_parts(f24, f24k, f24p, f24a)
+        """layers: list of 8 (w [Cout,Cin,3,3] np.float32 with BN folded, b [Cout], relu).  Each argument selects a layer form; no form
+        argument: every default below.
+        f24 (True): the 128-output layers on F(2x4) tiles; False: the F(2x2) form in every layer (the cross-check of the tests and the
+        A side of an A/B).
+        f24k (True): the 64-output layers with Cin % 64 == 0 on F(2x4) tiles as well; False: F(2x4) in the 128-output layers only.
+        f24p (F24P_DEFAULT): those 64-output layers in the pass-split form, else K split.
+        f24a = 'all' | 'out64' | 'out32' | 'off' (F24A_DEFAULT): F(2x4) sets of their own for the remaining layers of those output
+        widths.
+        f25 = 'all' | 'out64' | 'out32' | 'off' (F25_DEFAULT): F(2x5) tiles in the layers of those output widths; the other layers as
+        the remaining arguments say.
+        row6 = 'both' | 'taps' | 'order' | 'off' (ROW6_DEFAULT): host-formed row-6 taps and / or the direct round first in the
+        128-output layers.
+        An explicit older argument switches the defaults of the newer ones off (cyl_forms)."""
+        f24, f24k, f24p, parts, parts25, (row6_taps, row6_first) = cyl_forms(f24, f24k, f24p, f24a, f25, row6)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_wg"            # the family (CylindricalNetSplit: "buf_cylindrical_net_split"); self.fn is what is called
         self.form = 1 if f24p else 0
@@ -1284,19 +1256,21 @@ class CylindricalNet:
         self._ci = (C.c_int * n)(*self.cin)
         self._co = (C.c_int * n)(*self.cout)
         self._re = (C.c_int * n)(*[r | f for r, f in zip(self.relu, flags)])
-        # the layers k_cyl_net_w24a runs on an F(2x4) set of their own; f24_all: every layer of the stack runs on F(2x4) tiles
-        self.wt24, self._w24p = cyl_f24a_filters(layers, flags, parts, device)
+        small = lambda w: w.shape[0] in (32, 64) and w.shape[1] % 16 == 0
+        # the unflagged layers that run on an F(2x4) set of their own; f24_all: every layer of the stack runs on F(2x4) tiles
+        self.wt24, self._w24p = cyl_own_sets(layers, flags, lambda w, flag: flag == 0 and w.shape[0] in parts and small(w),
+                                             winograd_f24_tile_weights, device)
         self.f24_layers = [l for l, t in enumerate(self.wt24) if t is not None]
         self.f24_all = bool(self.f24_layers) and all(f or t is not None for f, t in zip(flags, self.wt24))
-        # the layers k_cyl_net_w25 runs on an F(2x5) set (it wins over the layer's F(2x4) flag or set)
-        self.wt25, self._w25p = cyl_f25_filters(layers, parts25, device)
+        # the layers that run on an F(2x5) set (it wins over the layer's F(2x4) flag or set)
+        self.wt25, self._w25p = cyl_own_sets(layers, flags, lambda w, flag: w.shape[0] in parts25 and small(w), winograd_f25_tile_weights, device)
         self.f25_layers = [l for l, t in enumerate(self.wt25) if t is not None]
-        # The entry point, chosen once: the fp32 call, the split-safe call of CylindricalNetSplit, and what both take between the relu
-        # words and the outputs
-        # the 128-output layers k_cyl_net_w25t runs on a row-6 tap set, and the order of their two rounds
-        self.taps, self._tapsp = cyl_row6_taps(layers, flags, row6_taps, device)
+        # the 128-output layers that run on a row-6 tap set, and the order of their two rounds
+        self.taps, self._tapsp = cyl_own_sets(layers, flags, lambda w, flag: row6_taps and flag == F24_FLAG, cyl_row6_tile_taps, device)
         self.taps_layers = [l for l, t in enumerate(self.taps) if t is not None]
         self.row6_first = bool(row6_first and F24_FLAG in flags)
+        # The entry point, chosen once: the fp32 call, the split-safe call of CylindricalNetSplit, and what both take between the relu
+        # words and the outputs
         if self.taps_layers or self.row6_first:
             fn, safe, self._extra = "w25t", "split_safe_w25t", (self._w24p, self._w25p, self._tapsp, 1 if self.row6_first else 0)
         elif self.f25_layers:
@@ -1338,11 +1312,8 @@ class CylindricalNetSplit:
     the status word was set."""
 
     def __init__(self, layers, device, f24k=None, f24p=None, f24a=None, f25=None, row6=None):
-        """f24k, f24p, f24a, f25, row6: the fp32 re-run's kernel, as in CylindricalNet (no form argument: k_cyl_net_w24a_rerun, or
-        k_cyl_net_w25_rerun where F25_DEFAULT names layers, or k_cyl_net_w25t_rerun where ROW6_DEFAULT names a part)"""
-        cyl_f25_parts(None, f24k, f24p, f25)             # (the arguments are checked whether or not the fp32 side gets built)
-        cyl_row6_parts(None, f24k, f24p, row6, f24a, f25)
-        form = cyl_f24a_parts(None, f24k, f24p, f24a)[2]
+        """f24k, f24p, f24a, f25, row6: the layer forms of the fp32 re-run, as in CylindricalNet"""
+        form = cyl_forms(None, f24k, f24p, f24a, f25, row6)[2]       # (the arguments are checked whether or not the fp32 side gets built)
         self.wt, self.bias, self.cin, self.cout, self.relu = [], [], [], [], []
         self.entry = "buf_cylindrical_net_split"
         self.f24_layers, self.f24_all, self.f25_layers, self.taps_layers, self.row6_first = [], False, [], [], False

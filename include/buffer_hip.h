@@ -310,7 +310,7 @@ int     buf_winograd_group(int cin, int cout);                                  
 int     buf_winograd_tile_weights(const float* w_host, int cout, int cin, float* out_host);   /* host only: [Cout,Cin,3,3] -> 16*Cout*Cin floats */
 int     buf_winograd_tile_filters(const float* w_host, int cout, int cin, int ng, int nblk, float* out_host);
                                                    /* host only: the same tiling with N-groups of ng and nblk = 4 | 5 blocks -> 4*nblk*Cout*Cin floats */
-/* The F(2x4, 3x3) form of the layers with 128 output channels (csrc/convnet_w24.hip, kernel k_cyl_net_w24: tiles of 2 x 4 outputs along
+/* The F(2x4, 3x3) form of the layers with 128 output channels (csrc/convnet_w24.hip, w24_layer_pair: tiles of 2 x 4 outputs along
  * the azimuth, 30 instead of 38 matrix instructions per 4 input x 16 output channels in those layers; the other layers as above;
  * all fp32).  Opt-in per call through relu_host[l]: bit 0 is the ReLU as before, bit 1 (BUF_CYL_F24) says that wt_host[l] holds,
  * BEHIND the 16*Cout*Cin floats above, the 24*Cout*Cin floats of buf_winograd_f24_tile_weights: U = G2 g G4^T (4 row x 6 column
@@ -330,7 +330,7 @@ int     buf_winograd_f24_tile_weights(const float* w_host, int cout, int cin, fl
 int     buf_cylindrical_net_wg(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                const int* cin_host, const int* cout_host, const int* relu_host, float* y, void* stream);
 /* The layers that carry bit 2 have two forms of the same arithmetic up to the order of summation: the K split above (k_cyl_net_w24k) and
- * the pass split (csrc/convnet_w24p.hip, kernel k_cyl_net_w24p: each wavefront owns one row component of the F(2,3) row transform for all
+ * the pass split (csrc/convnet_w24p.hip, a layer form of k_cyl_net_w25t: each wavefront owns one row component of the F(2,3) row transform for all
  * four N-tiles over the whole K, folds once and hands three N-tiles' partial outputs over through LDS).  Same buffers, same flags;
  * `form` picks one per call (no process-wide state), BUF_CYL_FORM_DEFAULT what buf_cylindrical_net_wg runs: the pass split
  * (profiles/f24p_ab.md).  A form outside -1..1 is
@@ -341,12 +341,12 @@ int     buf_cylindrical_net_wg(const float* x, int npatch, const float* const* w
 int     buf_cylindrical_net_wg_form(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                     const int* cin_host, const int* cout_host, const int* relu_host, int form, float* y, void* stream);
 int     buf_cylindrical_net_wg_supports(const int* cin_host, const int* cout_host);   /* host only: 0 if the kernel is built for these 8 widths */
-/* F(2x4) tiles in EVERY layer (csrc/convnet_w24a.hip, kernel k_cyl_net_w24a): buf_cylindrical_net_wg with one more array.  wt_host,
+/* F(2x4) tiles in EVERY layer (csrc/convnet_w24a.hip, layer forms of k_cyl_net_w25t): buf_cylindrical_net_wg with one more array.  wt_host,
  * bias_host and relu_host are exactly what buf_cylindrical_net_wg takes (same buffers, same words, same rules and messages for the words).
  * wt24_host[8]: per layer null, or the 24*Cout*Cin floats of buf_winograd_f24_tile_weights ([pair][i][k-step][768]) in a buffer of their
  * own -- allowed on a layer that carries neither BUF_CYL_F24 nor BUF_CYL_F24K and has 64 or 32 output channels, else BUF_EINVAL.  A
- * 64-output layer with a set runs the pass-split form of k_cyl_net_w24p (any Cin that is a multiple of 16: layer 0's 48), a 32-output
- * layer with a set the pass split over its one N-tile pair; a layer without a set runs as it does in k_cyl_net_w24p.  The widths rules
+ * 64-output layer with a set runs the pass-split form of the bit-2 layers (any Cin that is a multiple of 16: layer 0's 48), a 32-output
+ * layer with a set the pass split over its one N-tile pair; a layer without a set runs as it does through buf_cylindrical_net_wg.  The widths rules
  * are those of buf_cylindrical_net_wg_supports with one change: the rule "only 32-output layers follow a 32-output layer" binds from the
  * first 32-output layer WITHOUT a set on, to the end of the stack (its form leaves partial sums in zero words that later, wider layers
  * would read as padding); behind 32-output layers that all have their sets any supported layer may follow.  All checks happen before
@@ -356,7 +356,7 @@ int     buf_cylindrical_net_wg_all_flags(const int* cin_host, const int* cout_ho
 int     buf_cylindrical_net_wg_all(const float* x, int npatch, const float* const* wt_host, const float* const* bias_host,
                                    const int* cin_host, const int* cout_host, const int* relu_host, const float* const* wt24_host,
                                    float* y, void* stream);
-/* F(2x5, 3x3) tiles (csrc/convnet_w25.hip, kernel k_cyl_net_w25): tiles of 2 rows x 5 azimuth columns carry the 7 x 20 map with 4 x 4
+/* F(2x5, 3x3) tiles (csrc/convnet_w25.hip, a layer form of k_cyl_net_w25t): tiles of 2 rows x 5 azimuth columns carry the 7 x 20 map with 4 x 4
  * regular tiles, 28 matrix instructions per 4 input x 16 output channels and no direct round of row 6 (F(2x4): 24 + 6).
  * buf_cylindrical_net_wg_all with one more array, wt25_host[8]: per layer null, or the 28*Cout*Cin floats of
  * buf_winograd_f25_tile_weights -- U = G2 g G5^T (4 row x 7 column components; points 0, +-1, +-2, +-1/2; fp64 on the host) tiled
@@ -425,13 +425,13 @@ int     buf_cylindrical_net_split_safe_form(const float* x, int npatch, const vo
                                             const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                             int form, const float* head_params, float* y_or_equi, float* desc, int* status_dev, int* flags_ws,
                                             void* stream);
-/* The same with the fp32 re-run through k_cyl_net_w24a_rerun: wt24_host as for buf_cylindrical_net_wg_all (a flagged patch is bit-identical
+/* The same with the fp32 re-run through k_cyl_net_w25t_rerun: wt24_host as for buf_cylindrical_net_wg_all (a flagged patch is bit-identical
  * to that entry point's result) */
 int     buf_cylindrical_net_split_safe_all(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                            const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                            const float* const* wt24_host, const float* head_params, float* y_or_equi, float* desc,
                                            int* status_dev, int* flags_ws, void* stream);
-/* The same with the fp32 re-run through k_cyl_net_w25_rerun: wt24_host and wt25_host as for buf_cylindrical_net_w25 */
+/* The same with wt24_host and wt25_host as for buf_cylindrical_net_w25 */
 int     buf_cylindrical_net_split_safe_w25(const float* x, int npatch, const void* const* wt_split_host, const float* const* wt_wg_host,
                                            const float* const* bias_host, const int* cin_host, const int* cout_host, const int* relu_host,
                                            const float* const* wt24_host, const float* const* wt25_host, const float* head_params,

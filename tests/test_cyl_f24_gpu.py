@@ -1,4 +1,4 @@
-"""k_cyl_net_w24 (csrc/convnet_w24.hip): the descriptor CNN with its 128-output layers in the Winograd F(2x4, 3x3) form, against the
+"""The 128-output layers' F(2x4) form (w24_layer_pair, csrc/convnet_w24.hip): the descriptor CNN with its 128-output layers in the Winograd F(2x4, 3x3) form, against the
 float64 torch stack under the project's bound (1e-5 of the output scale: fp32 accumulation over K <= 9 x 128 products per output leaves
 ~1e-7 x sqrt(K) of the scale per layer, eight layers; the F(2x4) transforms measured 1.0e-6 on the CPU restatement), against the
 F(2x2) kernel on the same inputs and weights (2e-5: the sum of the two bounds), and bit for bit under a batch permutation and in the masked

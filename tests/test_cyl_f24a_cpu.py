@@ -1,17 +1,19 @@
-"""Host side and code object of k_cyl_net_w24a / k_cyl_net_w24a_rerun (csrc/convnet_w24a.hip: F(2x4) tiles in every layer of the
-descriptor CNN -- layer 0 through the pass-split form of the 64-output layers, the 32-output layers through a pass split over one N-tile
+"""Host side and code object of the layer forms on F(2x4) sets of their own in the fused kernel k_cyl_net_w25t / k_cyl_net_w25t_rerun
+(csrc/convnet_w24a.hip: F(2x4) tiles in every layer of the descriptor CNN -- layer 0 through the pass-split form of the 64-output layers, the 32-output layers through a pass split over one N-tile
 pair): the argument checks of the new entry points, what the two ops classes run with and without a form argument, and what the
 kernels compiled to, read off the gfx950 code object of the in-tree library.  No GPU needed."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
 
-from test_cyl_code_object_cpu import code_object, kernel_meta, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_code_object_cpu import code_object, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_f24_code_object_cpu import KERNELS, beyond, mfma_per_loop
 from test_cyl_f24k_cpu import RELEASED_IN, RELEASED_OUT, ints
+from test_cyl_f24p_cpu import W24P_LOOPS
 
-KERNELS = ['k_cyl_net_w24a', 'k_cyl_net_w24a_rerun']
+# MFMAs per k-loop of the body whose newest forms were these (test_matrix_instruction_count says which form accounts for which)
+W24A_LOOPS = [24] * 6 + [32] * 12 + [48] * 7 + [96]
 WORDS = (1, 5, 3, 3, 5, 5, 1, 0)
 
 
@@ -87,8 +89,8 @@ def test_argument_checks():
 
 
 def test_ops_defaults_and_explicit_arguments():
-    """No form argument -> k_cyl_net_w24a with a set of its own for layer 0 and the 32-output layers; an explicit f24, f24k or f24p ->
-    exactly the older kernels' arguments.  The relu words and the per-layer buffers are the same either way."""
+    """No form argument -> a set of its own for layer 0 and the 32-output layers; an explicit f24, f24k or f24p -> exactly the
+    arguments of the stacks without such sets.  The relu words and the per-layer buffers are the same either way."""
     from buffer_amd import ops
     layers = zero_layers()
     assert ops.F24A_DEFAULT in ops.F24A_PARTS
@@ -125,41 +127,23 @@ def test_ops_defaults_and_explicit_arguments():
 
 
 @pytest.mark.parametrize('name', KERNELS)
-def test_resources(code_object, name):
-    asm, notes = code_object
-    m = kernel_meta(notes, name)
-    print(name, m)
-    assert m['private_segment_fixed_size'] == 0, 'scratch memory'
-    assert m['vgpr_spill_count'] == 0 and m['sgpr_spill_count'] == 0
-    assert m['vgpr_count'] <= 256 and m['agpr_count'] <= 256          # the unified file, both kinds counted: two workgroups per CU
-    assert m['group_segment_fixed_size'] == 0, 'static LDS beside the dynamic 80 KB buffer'
-    text = kernel_text(asm, name)
-    assert not [op for _, op, _ in text if re.match(r'v_pk_\w+_f32', op)]
-    assert not [op for _, op, _ in text if op.startswith('scratch_')]
-    ls = loops(text)
-    assert ls, 'no loop found: the disassembly format changed?'
-    for a, b in ls:
-        bad = [op for _, op, _ in text[a:b + 1] if op == 'ds_read2_b64']
-        assert not bad, f'{len(bad)} ds_read2_b64 in the loop at {text[a][0]:#x}'
-
-
-@pytest.mark.parametrize('name', KERNELS)
 def test_matrix_instruction_count(code_object, name):
-    """Static count per k-loop (four k-steps per iteration), one set of loops per layer form in the kernel:
+    """Static count per k-loop (four k-steps per iteration), one set of loops per layer form, W24A_LOOPS:
     * 128 outputs (w24_layer_pair): four pass loops of 48 and the pair's direct round, one loop of 48;
     * 64 outputs on an F(2x4) set (w24p_layer_psplit): ONE pass loop of 96 and a direct loop of 24 (one N-tile);
     * 32 outputs on an F(2x4) set (w24a_layer_psplit32), built twice (LDS / global stores): ONE pass loop of 48 (6 column components x
       2 N-tiles x 4 k-steps) and a direct loop of 24 (one N-tile, run over half of K);
     * the F(2x2) forms for layers without such a set: 64 outputs (wg_layer_msplit), four loops of 32 and a direct loop of 24; 32 outputs
       (wg_layer_mksplit, built twice), eight loops of 32 and two of 24.
-    [24] x (1 + 2 + 1 + 2) + [32] x (4 + 8) + [48] x (5 + 2) + [96]."""
+    [24] x (1 + 2 + 1 + 2) + [32] x (4 + 8) + [48] x (5 + 2) + [96].  Beyond W24P_LOOPS (tests/test_cyl_f24p_cpu.py) that is the 32-output
+    form's pass loop and direct loop, twice, and the fused kernel holds every one of them (its loops outside the k-loops:
+    tests/test_cyl_taps_cpu.py)."""
     asm, _ = code_object
-    text = kernel_text(asm, name)
-    counts = sorted(sum(1 for _, op, _ in text[a:b + 1] if op.startswith('v_mfma_f32_16x16x4')) for a, b in loops(text))
-    counts = [c for c in counts if c]
+    counts = mfma_per_loop(kernel_text(asm, name))
     print(f'MFMAs per k-loop of {name}:', counts)
-    assert counts == [24] * 6 + [32] * 12 + [48] * 7 + [96], counts
-    assert sum(1 for _, op, _ in text if op.startswith('v_mfma')) == sum(counts)       # none outside the k-loops
+    assert W24A_LOOPS == [24] * 6 + [32] * 12 + [48] * 7 + [96]
+    assert beyond(W24A_LOOPS, W24P_LOOPS) == ([24] * 2 + [48] * 2, [])
+    assert beyond(counts, W24A_LOOPS)[1] == [], counts
 
 
 @pytest.mark.parametrize('name', KERNELS)

@@ -1,10 +1,10 @@
-"""k_cyl_net_w24a (csrc/convnet_w24a.hip): the descriptor CNN with F(2x4) tiles in every layer -- layer 0 (Cin = 48, and 16 in the second
+"""The layer forms on F(2x4) sets of their own (csrc/convnet_w24a.hip): the descriptor CNN with F(2x4) tiles in every layer -- layer 0 (Cin = 48, and 16 in the second
 stack) through the pass-split form of the 64-output layers, the 32-output layers through the pass split over one N-tile pair.  Each
 comparison has two bounds: against the float64 torch stack 1e-5 of the output scale, whole map and row 6 separately (the CPU restatement
-of this summation order, tools/f24a_restate.py, measured 1.2e-6 at worst), and against the same filters in the older kernels 2e-5, the
-sum of two bounds: k_cyl_net_w24p (f24p=True) and F(2x2) throughout (k_cyl_net_wg, f24=False).
+of this summation order, tools/f24a_restate.py, measured 1.2e-6 at worst), and against the same filters in the older forms 2e-5, the
+sum of two bounds: the pass split in the flagged layers only (f24p=True) and F(2x2) throughout (k_cyl_net_wg, f24=False).
 
-Stack A puts a 32-output layer directly in front of a wider one.  The older kernels reject such widths (their 32-output form runs its
+Stack A puts a 32-output layer directly in front of a wider one.  The older forms reject such widths (their 32-output form runs its
 exchange over the zero words of the channels 64..95), which the test asserts.  So the ONLY independent reference for stack A is the float64
 stack: the second net it is compared with (f24a='out32', the F(2x2) form in the 64-output layer 0) runs the same new code in the 32-output
 layers and checks layer 0 alone.  Likewise no kernel here takes a Cin that is not a multiple of 16 (every k-loop runs four k-steps per
@@ -28,7 +28,7 @@ RELEASED_NEW = [0, 6, 7]
 
 
 def nets_of(layers, dev, older=True):
-    """[F(2x4) in all layers, k_cyl_net_w24p, F(2x2)], or with older = False [all layers, the 32-output layers only]"""
+    """[F(2x4) in all layers, F(2x4) in the flagged layers only (f24p=True), F(2x2)], or with older = False [all layers, the 32-output layers only]"""
     from buffer_amd import _lib, ops
     new = ops.CylindricalNet(layers, dev, f24a='all')
     assert new.f24_all and new.f24_layers == [l for l, (w, _, _) in enumerate(layers) if w.shape[0] == 32 or (w.shape[0] == 64 and w.shape[1] % 64)]
@@ -202,8 +202,9 @@ def test_a_width_no_form_takes(dev):
 
 
 def test_the_older_forms_in_the_new_kernel_bit_for_bit(released, dev):
-    """k_cyl_net_w24a without a single F(2x4) set of a layer's own runs the layer forms of k_cyl_net_w24p in every layer -- the 64-output
-    layers 1, 4 and 5 among them, whose form the two kernels share when the sets are there as well: bit for bit that kernel's output."""
+    """buf_cylindrical_net_wg_all without a single F(2x4) set of a layer's own runs the layer forms of buf_cylindrical_net_wg_form (pass
+    split) in every layer -- the 64-output layers 1, 4 and 5 among them, whose form the two share when the sets are there as well: bit for
+    bit that entry point's output (both reach k_cyl_net_w25t: cyl_prepare hands it the same parameters)."""
     from buffer_amd import _lib, ops
     layers, nets = released
     old = nets[1]
@@ -217,7 +218,7 @@ def test_the_older_forms_in_the_new_kernel_bit_for_bit(released, dev):
 
 
 def test_masked_rerun_takes_the_same_kernel(released, dev):
-    """Through ops.CylindricalNetSplit the fp32 re-run of the flagged patches (an overflowing patch, a NaN) is k_cyl_net_w24a_rerun: the
+    """Through ops.CylindricalNetSplit the fp32 re-run of the flagged patches (an overflowing patch, a NaN) is k_cyl_net_w25t_rerun: the
     plain call's result, bit for bit."""
     from buffer_amd import ops
     layers, nets = released

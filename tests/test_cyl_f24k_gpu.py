@@ -3,7 +3,7 @@
 project's bound (1e-5 of the output scale, on all rows and on row 6 separately: fp32 accumulation over K <= 9 x 128 products per output
 leaves ~1e-7 x sqrt(K) of the scale per layer, eight layers; the CPU restatement of this arithmetic, tools/f24k_restate.py, measured
 1.6e-6 at worst), and against the same filters in the two older forms (2e-5: the sum of the two bounds): F(2x4) in the 128-output layers
-only (k_cyl_net_w24, f24k=False) and F(2x2) throughout (k_cyl_net_wg, f24=False)."""
+only (f24k=False) and F(2x2) throughout (k_cyl_net_wg, f24=False)."""
 import numpy as np
 import pytest
 import torch
@@ -139,12 +139,12 @@ def test_k_halves_and_bias_made_gross(dev, layer, fault):
 
 
 def test_the_bit_1_kernel_stays_exercised(released, dev):
-    """k_cyl_net_w24 (f24k=False: bit 1 only) on its own against float64: the product no longer runs it."""
+    """A stack with bit 1 only (f24k=False: F(2x4) in the 128-output layers alone) on its own against float64: the product no longer runs it."""
     layers, nets = released
     g = torch.Generator(device='cpu').manual_seed(12)
     x = (torch.rand((67, 48, 140), generator=g) * 2 - 1).to(dev)
     e_all, e6, e05, scale = errors(nets[1](x), stack64(x, layers, dev))
-    print(f'k_cyl_net_w24: scale {scale:.3e} | vs float64: all {e_all:.2e} row 6 {e6:.2e} rows 0..5 {e05:.2e}')
+    print(f'bit 1 only: scale {scale:.3e} | vs float64: all {e_all:.2e} row 6 {e6:.2e} rows 0..5 {e05:.2e}')
     assert e6 < BOUND and e05 < BOUND and e_all < BOUND
 
 

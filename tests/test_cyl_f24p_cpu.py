@@ -1,16 +1,17 @@
-"""Host side and code object of k_cyl_net_w24p / k_cyl_net_w24p_rerun (csrc/convnet_w24p.hip: the flagged 64-output layers of the
-descriptor CNN split over the wavefronts by row component): how the form is chosen (an argument of buf_cylindrical_net_wg_form and
-buf_cylindrical_net_split_safe_form, not the relu word) and what the kernels compiled to, read off the gfx950 code object of the in-tree
+"""Host side and code object of the pass-split form (w24p_layer_psplit, csrc/convnet_w24p.hip: the flagged 64-output layers of the
+descriptor CNN split over the wavefronts by row component) in the fused kernel k_cyl_net_w25t / k_cyl_net_w25t_rerun: how the form is
+chosen (an argument of buf_cylindrical_net_wg_form and buf_cylindrical_net_split_safe_form, not the relu word) and what the kernels compiled to, read off the gfx950 code object of the in-tree
 library.  No GPU needed."""
 import ctypes as C
-import re
 
 import pytest
 
-from test_cyl_code_object_cpu import code_object, kernel_meta, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_code_object_cpu import code_object, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_f24_code_object_cpu import KERNELS, W24_LOOPS, beyond, mfma_per_loop
 from test_cyl_f24k_cpu import RELEASED_IN, RELEASED_OUT, ints
 
-KERNELS = ['k_cyl_net_w24p', 'k_cyl_net_w24p_rerun']
+# MFMAs per k-loop of the body whose newest form was the pass split (test_matrix_instruction_count says which form accounts for which)
+W24P_LOOPS = [24] * 4 + [32] * 12 + [48] * 5 + [96]
 
 
 def test_form_argument():
@@ -40,40 +41,22 @@ def test_form_argument():
 
 
 @pytest.mark.parametrize('name', KERNELS)
-def test_resources(code_object, name):
-    asm, notes = code_object
-    m = kernel_meta(notes, name)
-    print(name, m)
-    assert m['private_segment_fixed_size'] == 0, 'scratch memory'
-    assert m['vgpr_spill_count'] == 0 and m['sgpr_spill_count'] == 0
-    assert m['vgpr_count'] <= 256 and m['agpr_count'] <= 256          # the unified file: two workgroups per CU
-    assert m['group_segment_fixed_size'] == 0, 'static LDS beside the dynamic 80 KB buffer'
-    text = kernel_text(asm, name)
-    assert not [op for _, op, _ in text if re.match(r'v_pk_\w+_f32', op)]
-    assert not [op for _, op, _ in text if op.startswith('scratch_')]
-    ls = loops(text)
-    assert ls, 'no loop found: the disassembly format changed?'
-    for a, b in ls:
-        bad = [op for _, op, _ in text[a:b + 1] if op == 'ds_read2_b64']
-        assert not bad, f'{len(bad)} ds_read2_b64 in the loop at {text[a][0]:#x}'
-
-
-@pytest.mark.parametrize('name', KERNELS)
 def test_matrix_instruction_count(code_object, name):
-    """Static count per k-loop (four k-steps per iteration), one set of loops per layer form in the kernel:
+    """Static count per k-loop (four k-steps per iteration), one set of loops per layer form, W24P_LOOPS:
     * 128 outputs (w24_layer_pair): four pass loops of 48 and the pair's direct round, one loop of 48;
     * 64 outputs, flagged (w24p_layer_psplit): ONE pass loop of 96 (6 column components x 4 N-tiles x 4 k-steps: the wavefront's row
       component for the whole layer) and a direct loop of 24 (one N-tile);
     * 64 outputs, unflagged (wg_layer_msplit: layer 0): four loops of 32 and a direct loop of 24;
     * 32 outputs (wg_layer_mksplit), built twice (LDS / global stores): eight loops of 32 and two of 24.
-    [24] x 4 + [32] x 12 + [48] x 5 + [96].  Per wavefront and k-step of a flagged layer 24 + 6, as in the K split: 22 848 per patch."""
+    [24] x 4 + [32] x 12 + [48] x 5 + [96].  Per wavefront and k-step of a flagged layer 24 + 6, as in the K split: 22 848 per patch.
+    Beyond W24_LOOPS (tests/test_cyl_f24_code_object_cpu.py) that is the pass-split form's own two loops, and the fused kernel holds every
+    one of them (its loops outside the k-loops: tests/test_cyl_taps_cpu.py)."""
     asm, _ = code_object
-    text = kernel_text(asm, name)
-    counts = sorted(sum(1 for _, op, _ in text[a:b + 1] if op.startswith('v_mfma_f32_16x16x4')) for a, b in loops(text))
-    counts = [c for c in counts if c]
+    counts = mfma_per_loop(kernel_text(asm, name))
     print(f'MFMAs per k-loop of {name}:', counts)
-    assert counts == [24] * 4 + [32] * 12 + [48] * 5 + [96], counts
-    assert sum(1 for _, op, _ in text if op.startswith('v_mfma')) == sum(counts)       # none outside the k-loops
+    assert W24P_LOOPS == [24] * 4 + [32] * 12 + [48] * 5 + [96]
+    assert beyond(W24P_LOOPS, W24_LOOPS) == ([24, 96], [])
+    assert beyond(counts, W24P_LOOPS)[1] == [], counts
 
 
 @pytest.mark.parametrize('name', KERNELS)

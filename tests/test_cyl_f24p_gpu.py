@@ -1,4 +1,4 @@
-"""k_cyl_net_w24p (csrc/convnet_w24p.hip): the flagged 64-output layers of the descriptor CNN in the pass-split form -- wavefront w owns
+"""The pass-split form (w24p_layer_psplit, csrc/convnet_w24p.hip): the flagged 64-output layers of the descriptor CNN in the pass-split form -- wavefront w owns
 row component w of the F(2,3) row transform for all four N-tiles over the whole K, folds once, and wavefront q finishes N-tile q from
 three received partial outputs.  Against the float64 torch stack under the project's bound (1e-5 of the output scale: the CPU restatement
 of this summation order, tools/f24p_restate.py, measured 1.6e-6 at worst) and against the same filters in the older forms (2e-5, the sum
@@ -140,7 +140,7 @@ def test_zero_filters_and_a_random_bias(dev, second_input, layer):
 
 
 def test_masked_rerun_takes_the_same_form(released, dev):
-    """Through ops.CylindricalNetSplit the fp32 re-run of the flagged patches (an overflowing patch, a NaN) is k_cyl_net_w24p_rerun: the
+    """Through ops.CylindricalNetSplit the fp32 re-run of the flagged patches (an overflowing patch, a NaN) is k_cyl_net_w25t_rerun: the
     plain call's result, bit for bit."""
     from buffer_amd import ops
     layers, nets = released

@@ -1,19 +1,22 @@
-"""Host side and code object of k_cyl_net_w25 / k_cyl_net_w25_rerun (csrc/convnet_w25.hip: F(2x5, 3x3) tiles -- 2 rows x 5 azimuth
+"""Host side and code object of the F(2x5) layer forms in the fused kernel k_cyl_net_w25t / k_cyl_net_w25t_rerun (csrc/convnet_w25.hip:
+F(2x5, 3x3) tiles -- 2 rows x 5 azimuth
 columns, 4 x 4 regular tiles for the 7 x 20 map, 28 matrix instructions per (k-step, N-tile) and no direct round -- in the 64- and
 32-output layers of the descriptor CNN): the filter transform against a float64 numpy statement of G2 g G5^T and the transform identity
 it rests on, the argument checks of the new entry points, what the two ops classes run with and without f25=, and what the kernels
 compiled to, read off the gfx950 code object of the in-tree library.  No GPU needed."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
 
-from test_cyl_code_object_cpu import code_object, kernel_meta, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_code_object_cpu import code_object, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_f24_code_object_cpu import KERNELS, beyond, mfma_per_loop
+from test_cyl_f24a_cpu import W24A_LOOPS
 from test_cyl_f24k_cpu import RELEASED_IN, RELEASED_OUT, ints
 from test_winograd_f24_cpu import A2T, B2T, correlate
 
-KERNELS = ['k_cyl_net_w25', 'k_cyl_net_w25_rerun']
+# MFMAs per k-loop of the body whose newest forms were these (test_matrix_instruction_count says which form accounts for which)
+W25_LOOPS = W24A_LOOPS + [56] * 2 + [112]
 WORDS = (1, 5, 3, 3, 5, 5, 1, 0)
 G2 = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], np.float64)
 POINTS = [0, 1, -1, 2, -2, .5, -.5]
@@ -188,26 +191,6 @@ def test_ops_defaults_and_explicit_arguments():
             ops.CylindricalNet(layers, 'cpu', f25=bad)
 
 
-@pytest.mark.parametrize('name', KERNELS)
-def test_resources(code_object, name):
-    """No scratch, no spills, and both register kinds together within the 256 that let two workgroups share a CU"""
-    asm, notes = code_object
-    m = kernel_meta(notes, name)
-    print(name, m)
-    assert m['private_segment_fixed_size'] == 0, 'scratch memory'
-    assert m['vgpr_spill_count'] == 0 and m['sgpr_spill_count'] == 0
-    assert m['vgpr_count'] <= 256 and m['agpr_count'] <= 128          # .vgpr_count of the unified file counts both kinds
-    assert m['group_segment_fixed_size'] == 0, 'static LDS beside the dynamic 80 KB buffer'
-    text = kernel_text(asm, name)
-    assert not [op for _, op, _ in text if re.match(r'v_pk_\w+_f32', op)]
-    assert not [op for _, op, _ in text if op.startswith('scratch_')]
-    ls = loops(text)
-    assert ls, 'no loop found: the disassembly format changed?'
-    for a, b in ls:
-        bad = [op for _, op, _ in text[a:b + 1] if op == 'ds_read2_b64']
-        assert not bad, f'{len(bad)} ds_read2_b64 in the loop at {text[a][0]:#x}'
-
-
 def loop_stats(text):
     out = []
     for a, b in loops(text):
@@ -220,15 +203,17 @@ def loop_stats(text):
 
 @pytest.mark.parametrize('name', KERNELS)
 def test_matrix_instruction_count(code_object, name):
-    """Static count per k-loop (four k-steps per iteration): every loop of k_cyl_net_w24a (tests/test_cyl_f24a_cpu.py) and, for the
-    F(2x5) forms, ONE pass loop of 4 x 28 = 112 (64 outputs) and one of 4 x 14 = 56 built twice (32 outputs: LDS / global stores).  The
-    F(2x5) forms have no direct loop: no loop of 24 beyond those of the other forms."""
+    """Static count per k-loop (four k-steps per iteration), W25_LOOPS: every loop of W24A_LOOPS (tests/test_cyl_f24a_cpu.py) and, for
+    the F(2x5) forms, ONE pass loop of 4 x 28 = 112 (64 outputs) and one of 4 x 14 = 56 built twice (32 outputs: LDS / global stores).
+    The F(2x5) forms have no direct loop: no loop of 24 beyond those of the other forms.  The fused kernel holds every one of them, and
+    no loop of 56 or 112 beyond these three (its loops outside the k-loops: tests/test_cyl_taps_cpu.py)."""
     asm, _ = code_object
-    text = kernel_text(asm, name)
-    counts = sorted(s['mfma'] for s in loop_stats(text))
+    counts = mfma_per_loop(kernel_text(asm, name))
     print(f'MFMAs per k-loop of {name}:', counts)
-    assert counts == [24] * 6 + [32] * 12 + [48] * 7 + [56] * 2 + [96] + [112], counts
-    assert sum(1 for _, op, _ in text if op.startswith('v_mfma')) == sum(counts)       # none outside the k-loops
+    assert sorted(W25_LOOPS) == [24] * 6 + [32] * 12 + [48] * 7 + [56] * 2 + [96] + [112]
+    assert beyond(W25_LOOPS, W24A_LOOPS) == ([56, 56, 112], [])
+    assert beyond(counts, W25_LOOPS)[1] == [], counts
+    assert [c for c in counts if c in (24, 56, 112)] == [24] * 6 + [56] * 2 + [112]
 
 
 @pytest.mark.parametrize('name', KERNELS)
@@ -248,7 +233,7 @@ def test_the_new_pass_loops(code_object, name):
 
 def test_issued_count_of_the_released_stack():
     """28 per (k-step, N-tile) in the 64- and 32-output layers (352 units), 30 in the 128-output layers (384): 21 376 per patch, against
-    the 22 080 of k_cyl_net_w24a."""
+    the 22 080 of F(2x4) tiles in every layer."""
     units = {co: 0 for co in (32, 64, 128)}
     for ci, co in zip(RELEASED_IN, RELEASED_OUT):
         units[co] += (ci // 4) * (co // 16)

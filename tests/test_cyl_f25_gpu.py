@@ -1,11 +1,11 @@
-"""k_cyl_net_w25 (csrc/convnet_w25.hip): the descriptor CNN with F(2x5, 3x3) tiles -- 2 rows x 5 azimuth columns, 4 x 4 regular tiles
+"""The F(2x5) layer forms (csrc/convnet_w25.hip): the descriptor CNN with F(2x5, 3x3) tiles -- 2 rows x 5 azimuth columns, 4 x 4 regular tiles
 for the 7 x 20 map, no direct round of row 6 -- in the 64- and 32-output layers.  Each comparison has two bounds: against the float64
 torch stack 1e-5 of the output scale, on the whole map and on row 6 alone (the CPU restatement of this summation order,
-tools/f25_restate.py, measured 1.5e-6 at worst), and against the same filters in the older kernels 2e-5, the sum of two bounds:
-k_cyl_net_w24a (f24a='all', f25='off') and F(2x2) throughout (k_cyl_net_wg, f24=False).
+tools/f25_restate.py, measured 1.5e-6 at worst), and against the same filters in the older forms 2e-5, the sum of two bounds:
+F(2x4) tiles in every layer (f24a='all', f25='off') and F(2x2) throughout (k_cyl_net_wg, f24=False).
 
-Stack A puts a 32-output layer directly in front of a wider one, which the F(2x2) kernels reject (tests/test_cyl_f24a_gpu.py): its
-references are the float64 stack and k_cyl_net_w24a.  The impulses put a single 1.0 at every map position: a wrong halo word, a wrong
+Stack A puts a 32-output layer directly in front of a wider one, which the F(2x2) forms reject (tests/test_cyl_f24a_gpu.py): its
+references are the float64 stack and the F(2x4) forms.  The impulses put a single 1.0 at every map position: a wrong halo word, a wrong
 padding factor of the rows -1, 7 and 8, or a wrong window at the edges tx = 3 / ty = 3 shows there as an error of the order of a filter
 tap.
 
@@ -26,7 +26,7 @@ RELEASED_F25 = [0, 1, 4, 5, 6, 7]
 
 
 def nets_of(layers, dev, older=True):
-    """[F(2x5) in the 64- and 32-output layers, k_cyl_net_w24a, F(2x2)]; older = False: without the last"""
+    """[F(2x5) in the 64- and 32-output layers, F(2x4) in every layer, F(2x2)]; older = False: without the last"""
     from buffer_amd import ops
     new = ops.CylindricalNet(layers, dev, f25='all')
     assert new.f25_layers == [l for l, (w, _, _) in enumerate(layers) if w.shape[0] in (32, 64)]
@@ -123,7 +123,7 @@ def test_stack_b(stack_b, dev, n):
 
 @pytest.mark.parametrize("part", ['out64', 'out32'])
 def test_the_parts_alone(released, dev, part):
-    """F(2x5) in the layers of one output width only, the others as in k_cyl_net_w24a: the two forms next to each other in one stack"""
+    """F(2x5) in the layers of one output width only, the others on F(2x4) tiles: the two forms next to each other in one stack"""
     from buffer_amd import ops
     layers, nets = released
     net = ops.CylindricalNet(layers, dev, f25=part)
@@ -152,7 +152,8 @@ def test_zero_filters_and_a_random_bias(dev, input_b, layer):
 
 
 def test_without_a_set_bit_for_bit_k_cyl_net_w24a(released, dev):
-    """k_cyl_net_w25 without a single F(2x5) set runs the layer forms of k_cyl_net_w24a in every layer: bit for bit that kernel's output"""
+    """buf_cylindrical_net_w25 without a single F(2x5) set runs the layer forms of buf_cylindrical_net_wg_all in every layer: bit for bit that
+    entry point's output (both reach k_cyl_net_w25t: cyl_prepare hands it the same parameters)"""
     from buffer_amd import _lib, ops
     layers, nets = released
     old = nets[1]
@@ -166,7 +167,7 @@ def test_without_a_set_bit_for_bit_k_cyl_net_w24a(released, dev):
 
 
 def test_masked_rerun_takes_the_same_kernel(released, dev):
-    """Through ops.CylindricalNetSplit the fp32 re-run of the flagged patches (an overflowing patch, a NaN) is k_cyl_net_w25_rerun: the
+    """Through ops.CylindricalNetSplit the fp32 re-run of the flagged patches (an overflowing patch, a NaN) is k_cyl_net_w25t_rerun: the
     plain call's result, bit for bit -- non-finite values included, which the padding factor of the rows outside the map turns into NaN
     in both alike."""
     from buffer_amd import ops

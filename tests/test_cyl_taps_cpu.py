@@ -1,5 +1,5 @@
-"""Host side and code object of k_cyl_net_w25t / k_cyl_net_w25t_rerun (csrc/convnet_w25t.hip: k_cyl_net_w25 with, in the layers of 128
-output channels, the direct round of output row 6 on host-formed taps and in front of the Winograd round): the tap tiler against a numpy
+"""Host side and code object of k_cyl_net_w25t / k_cyl_net_w25t_rerun (csrc/convnet_w25t.hip: the fused kernel of every layer form, and
+in the layers of 128 output channels the direct round of output row 6 on host-formed taps and in front of the Winograd round): the tap tiler against a numpy
 restatement, the argument checks of the new entry points, what the two ops classes run with and without row6=, and what the kernels
 compiled to, read off the gfx950 code object of the in-tree library.  No GPU needed."""
 import ctypes as C
@@ -10,9 +10,12 @@ import pytest
 
 from test_cyl_code_object_cpu import code_object, kernel_meta, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
 from test_cyl_f24k_cpu import RELEASED_IN, RELEASED_OUT, ints
-from test_cyl_f25_cpu import loop_stats, zero_layers
+from test_cyl_f24_code_object_cpu import KERNELS
+from test_cyl_f25_cpu import W25_LOOPS, loop_stats, zero_layers
 
-KERNELS = ['k_cyl_net_w25t', 'k_cyl_net_w25t_rerun']
+# MFMAs per k-loop of the fused kernel: every form before this file's (tests/test_cyl_f25_cpu.py) and three forms of the 128-output layers,
+# each with four Winograd passes and one direct loop of 48
+W25T_LOOPS = sorted(W25_LOOPS + [48] * 15)
 WORDS = (1, 5, 3, 3, 5, 5, 1, 0)
 
 
@@ -157,7 +160,8 @@ def test_ops_defaults_and_explicit_arguments():
 
 @pytest.mark.parametrize('name', KERNELS)
 def test_resources(code_object, name):
-    """No scratch, no spills, and at most 128 + 128 registers: two workgroups share a CU"""
+    """No scratch, no spills, and at most 128 + 128 registers: two workgroups share a CU.  (The one copy for the fused kernel and every
+    layer form in it; k_cyl_net_wg and k_cyl_net_w24k have theirs in tests/test_cyl_code_object_cpu.py and tests/test_cyl_f24k_cpu.py.)"""
     asm, notes = code_object
     m = kernel_meta(notes, name)
     print(name, m)
@@ -169,7 +173,9 @@ def test_resources(code_object, name):
     text = kernel_text(asm, name)
     assert not [op for _, op, _ in text if re.match(r'v_pk_\w+_f32', op)]
     assert not [op for _, op, _ in text if op.startswith('scratch_')]
-    for a, b in loops(text):
+    ls = loops(text)
+    assert ls, 'no loop found: the disassembly format changed?'
+    for a, b in ls:
         assert 'ds_read2_b64' not in [op for _, op, _ in text[a:b + 1]]
 
 
@@ -180,18 +186,15 @@ def is_new_direct(s):
 
 @pytest.mark.parametrize('name', KERNELS)
 def test_matrix_instruction_count(code_object, name):
-    """Every k-loop of k_cyl_net_w25 is here with its count (the layers without a part run them); the forms of the 128-output layers add
-    loops of 48 only: per form four Winograd passes and one direct loop."""
+    """The whole list of the fused kernel, exactly.  Every k-loop of W25_LOOPS is here with its count (the layers without a part run
+    them); the forms of the 128-output layers add loops of 48 only: per form four Winograd passes and one direct loop."""
     asm, _ = code_object
     stats = loop_stats(kernel_text(asm, name))
     counts = sorted(s['mfma'] for s in stats)
-    parent = sorted(s['mfma'] for s in loop_stats(kernel_text(asm, name.replace('w25t', 'w25'))))
     print(f'MFMAs per k-loop of {name}:', counts)
-    assert parent == [24] * 6 + [32] * 12 + [48] * 7 + [56] * 2 + [96] + [112]
-    rest = list(counts)
-    for c in parent:
-        rest.remove(c)
-    assert rest == [48] * 15, rest                                   # three forms x (4 passes + 1 direct loop)
+    assert sorted(W25_LOOPS) == [24] * 6 + [32] * 12 + [48] * 7 + [56] * 2 + [96] + [112]
+    assert W25T_LOOPS == [24] * 6 + [32] * 12 + [48] * 22 + [56] * 2 + [96] + [112]      # three forms x (4 passes + 1 direct loop) more
+    assert counts == W25T_LOOPS, counts
     assert sum(1 for s in stats if is_new_direct(s)) == 2            # taps and order | taps only
 
 
@@ -199,7 +202,8 @@ def test_matrix_instruction_count(code_object, name):
 def test_the_new_direct_loops(code_object, name):
     """Per iteration four k-steps: 48 MFMAs, the window words of two rows as six paired 4-byte LDS reads per two k-steps, three 16-byte
     buffer loads per k-step -- and no tap arithmetic: no float addition, subtraction or multiplication at all, no copies between the
-    register files.  The last iteration stands behind the loop: 48 more MFMAs per direct round outside the k-loops."""
+    register files.  The last iteration stands behind the loop: 48 more MFMAs per direct round outside the k-loops, and no other layer
+    form has a matrix instruction outside its k-loops."""
     asm, _ = code_object
     text = kernel_text(asm, name)
     new = []

@@ -1,7 +1,7 @@
-"""k_cyl_net_w25t (csrc/convnet_w25t.hip): k_cyl_net_w25 with, in the layers of 128 output channels, the direct round of output row 6 on
+"""k_cyl_net_w25t (csrc/convnet_w25t.hip): the fused kernel with, in the layers of 128 output channels, the direct round of output row 6 on
 taps the host formed (the filter rows 0 and 1 as they are) and in front of the Winograd round.  The reference is the float64 stack (torch
 on the CPU); the metric is the largest error over the output scale of the whole map, stated for the whole map and for row 6 alone, each
-beside the figure of the parent kernel (k_cyl_net_w25, row6='off') on the same input.  Bounds: 1e-5 against float64 (that of
+beside the figure of the parent form (row6='off') on the same input.  Bounds: 1e-5 against float64 (that of
 tests/test_cyl_f25_gpu.py), and row 6 no worse than twice the parent's figure (the 2 x rule of profiles/f25_ab.md).
 
 The taps are another rounding of row 6 (exact filter values instead of differences of rounded Winograd blocks), so the new kernel is
@@ -195,7 +195,8 @@ def test_a_layer_without_relu(dev, input_b, layer):
 
 
 def test_without_sets_and_in_the_old_order_bit_for_bit_k_cyl_net_w25(released, dense70, dev):
-    """k_cyl_net_w25t without a tap set and with order = 0 runs the layer forms of k_cyl_net_w25 in every layer"""
+    """buf_cylindrical_net_w25t without a tap set and with order = 0 runs the layer forms of buf_cylindrical_net_w25 in every layer (both
+    reach k_cyl_net_w25t: cyl_prepare hands it the same parameters)"""
     from buffer_amd import _lib, ops
     layers, nets = released
     old = nets[1]
@@ -208,7 +209,7 @@ def test_without_sets_and_in_the_old_order_bit_for_bit_k_cyl_net_w25(released, d
 
 
 def test_the_parts_alone(released, dense70, dev):
-    """Taps only and order only: each equals itself across repeated calls.  The order alone changes no arithmetic: k_cyl_net_w25's bits;
+    """Taps only and order only: each equals itself across repeated calls.  The order alone changes no arithmetic: the bits of row6='off';
     and with the taps the order changes nothing either."""
     from buffer_amd import ops
     layers, nets = released

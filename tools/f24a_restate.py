@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""The descriptor CNN restated on the CPU in float32 with the summation order of k_cyl_net_w24a (csrc/convnet_w24a.hip): F(2x4) tiles in
-every layer -- the 128-output layers as k_cyl_net_w24 runs them, every 64-output layer (layer 0 included) and the 32-output layers in the
+"""The descriptor CNN restated on the CPU in float32 with the summation order of the forms on F(2x4) sets of their own (csrc/convnet_w24a.hip): F(2x4) tiles in
+every layer -- the 128-output layers as w24_layer_pair runs them, every 64-output layer (layer 0 included) and the 32-output layers in the
 pass-split order of tools/f24p_restate.py (one accumulator set per row component over the whole K, A4^T folded once per row component,
 row 0 = (f_0 + f_1) + f_2, row 1 = (f_1 - f_2) - f_3), with the direct round of row 6 summed over the two K halves separately in the
 32-output layers.  Against the float64 stack -- the figure the kernel's tests are bounded by (1e-5 of the output scale) -- beside the
-order of k_cyl_net_w24p.
+order of the pass split in the flagged layers only.
 
     python tools/f24a_restate.py [patches]
 
@@ -60,4 +60,4 @@ if __name__ == '__main__':
                 ref = k.stack64(x, layers)
                 worst['a'] = max(worst['a'], np.abs(stack32_all(x, layers) - ref).max() / np.abs(ref).max())
                 worst['p'] = max(worst['p'], np.abs(p.stack32_pass_split(x, layers) - ref).max() / np.abs(ref).max())
-            print(f'{name}, {"signed" if signed else "non-negative"}, {n} patches: F(2x4) in all layers {worst["a"]:.2e} | k_cyl_net_w24p order {worst["p"]:.2e}')
+            print(f'{name}, {"signed" if signed else "non-negative"}, {n} patches: F(2x4) in all layers {worst["a"]:.2e} | flagged layers only {worst["p"]:.2e}')

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The descriptor CNN restated on the CPU in float32 with the summation order of k_cyl_net_w24p (csrc/convnet_w24p.hip): in the flagged
+"""The descriptor CNN restated on the CPU in float32 with the summation order of the pass-split form (csrc/convnet_w24p.hip): in the flagged
 64-output layers one fresh accumulator set per row component I over the whole K (the bias starts in column component 1 of I = 1), A4^T
-folded once per row component, then  row 0 = (f_0 + f_1) + f_2,  row 1 = (f_1 - f_2) - f_3;  the 128-output layers as k_cyl_net_w24 runs
+folded once per row component, then  row 0 = (f_0 + f_1) + f_2,  row 1 = (f_1 - f_2) - f_3;  the 128-output layers as w24_layer_pair runs
 them (the accumulators run on through the passes), F(2x2) elsewhere.  Against the float64 stack -- the figure the kernel's tests are
 bounded by (1e-5 of the output scale) -- beside the K-split order of tools/f24k_restate.py.
 

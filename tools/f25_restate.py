@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""The descriptor CNN restated on the CPU in float32 with the summation order of k_cyl_net_w25 (csrc/convnet_w25.hip): F(2x5, 3x3) tiles
+"""The descriptor CNN restated on the CPU in float32 with the summation order of the F(2x5) forms (csrc/convnet_w25.hip): F(2x5, 3x3) tiles
 of 2 rows x 5 azimuth columns (4 x 4 tiles carry the 7 x 20 map, the eighth row dropped) in the layers of the chosen output widths, in
 the pass-split order -- one fresh accumulator set per row component I over the whole K (the bias starts in the column component of
 point +1 of I = 1), A5^T folded once per row component, then  row 0 = (f_0 + f_1) + f_2,  row 1 = (f_1 - f_2) - f_3  -- and the order of
-k_cyl_net_w24a (tools/f24a_restate.py) in every other layer.  Against the float64 stack -- the figure the kernel's tests are bounded by
+the F(2x4) forms (tools/f24a_restate.py) in every other layer.  Against the float64 stack -- the figure the kernel's tests are bounded by
 (1e-5 of the output scale) -- beside the parent order, F(2x4) in all layers.
 
     python tools/f25_restate.py [patches] [point set ...]

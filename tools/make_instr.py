@@ -25,7 +25,7 @@ for r in csv.DictReader(open(path)):
     e = rows[k].setdefault(r['Dispatch_Id'], {'grid': int(r['Grid_Size'])})
     e[r['Counter_Name']] = e.get(r['Counter_Name'], 0.0) + float(r['Counter_Value'])
 kernels = {}
-for k in ('k_patch_voxelize', 'k_cyl_net_wg', 'k_cyl_net_w24', 'k_cyl_net_w24k', 'k_cyl_net_w24p', 'k_cyl_net_w24a', 'k_cyl_net_w25', 'k_cyl_net_w25t', 'k_cyl_net_h3', 'k_desc_head', 'k_select_patches_grid'):
+for k in ('k_patch_voxelize', 'k_cyl_net_wg', 'k_cyl_net_w24k', 'k_cyl_net_w25t', 'k_cyl_net_h3', 'k_desc_head', 'k_select_patches_grid'):
     d = list(rows.get(k, {}).values())
     if not d:
         continue

@@ -16,7 +16,7 @@ bench = json.load(open(bench_file))            # the uncompacted record (bench.p
 
 # kernels whose launch covers a FIXED number of units (one workgroup per patch): only the dispatches with the full-step grid count.
 # (Round 4 averaged one 64-patch accuracy-probe launch of each CNN kernel into the mean: traffic under-reported by 1/6 and 1/4.)
-FULL_GRID_ONLY = ('k_cyl_net_wg', 'k_cyl_net_w24', 'k_cyl_net_w24k', 'k_cyl_net_w24p', 'k_cyl_net_w24a', 'k_cyl_net_w25', 'k_cyl_net_w25t', 'k_cyl_net_h3', 'k_desc_head', 'k_patch_voxelize', 'k_select_patches_grid')
+FULL_GRID_ONLY = ('k_cyl_net_wg', 'k_cyl_net_w24k', 'k_cyl_net_w25t', 'k_cyl_net_h3', 'k_desc_head', 'k_patch_voxelize', 'k_select_patches_grid')
 dropped = collections.defaultdict(int)
 
 
@@ -68,11 +68,7 @@ matches = cost['avg_algorithmic_flops'] / 51905536.0
 # unit of work per launch and the algorithmic bytes per unit (SURVEY 8d formulas)
 units = {
     'k_cyl_net_wg': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
-    'k_cyl_net_w24': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
     'k_cyl_net_w24k': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
-    'k_cyl_net_w24p': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
-    'k_cyl_net_w24a': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
-    'k_cyl_net_w25': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
     'k_cyl_net_w25t': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
     'k_desc_head': (patches, 'patch', 2 * 32 * 140 * 4 + 128),
     'k_patch_voxelize': (patches, 'patch', 12 * 512 + 4 * 16 * 420),
