@@ -137,6 +137,9 @@ _SIGNATURES = {
     "buf_fpfh": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "buf_iss_keypoints": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "buf_row_normals": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "buf_grid_knn": (_i, [C.POINTER(buf_grid_t), _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "buf_outlier_statistical_ws_bytes": (_sz, [_i]),
+    "buf_outlier_statistical": (_i, [_vp, _i, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "buf_feature_match_ws_bytes": (_sz, [C.c_longlong, C.c_longlong, _i]),
     "buf_feature_match": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "buf_fgr_ws_bytes": (_sz, [_i, _i, _i]),

@@ -42,3 +42,4 @@
 #include "sc2.hip"
 #include "clique.hip"
 #include "vgicp.hip"
+#include "knn3.hip"

@@ -19,16 +19,27 @@ def pack_pair(raws, seeds, meta, consts):
     {src,tgt}_fds_pts, {src,tgt}_sds_pts.  `raws` may be lazy: a cloud is taken when its turn comes."""
     out = dict(meta)
     for side, raw, seed in zip(('src', 'tgt'), raws, seeds):
-        it = preprocess.prepare_fragment(raw, consts.downsample, consts.voxel_size_0, consts.max_num_pts, seed=seed)
+        it = preprocess.prepare_fragment(raw, consts.downsample, consts.voxel_size_0, consts.max_num_pts, seed=seed,
+                                         denoise=getattr(consts, 'denoise', None))
         out[f'{side}_fds_pts'], out[f'{side}_sds_pts'] = it['fds_pts'], it['sds_pts']
+        _log_denoise(consts, [it])
     return out
+
+
+def _log_denoise(consts, fragments):
+    """the removed fractions of denoised fragments -> consts.denoise_log, where the driver keeps one (run)"""
+    log = getattr(consts, 'denoise_log', None)
+    if log is not None:
+        log.extend(f['denoise_removed'] for f in fragments if 'denoise_removed' in f)
 
 
 def pack_pairs(raws, seeds, metas, consts):
     """pack_pair for B pairs with the normals of all 2B clouds estimated in ONE stacked pass (preprocess.prepare_fragments); pair by
     pair the result is that of pack_pair.  raws, seeds: 2B entries (src, tgt of pair 0, src, tgt of pair 1, ...); metas: B dicts,
     read AFTER the stacked pass is queued (a generator keeps the work of making them behind it)."""
-    frs = preprocess.prepare_fragments(raws, consts.downsample, consts.voxel_size_0, consts.max_num_pts, seeds)
+    frs = preprocess.prepare_fragments(raws, consts.downsample, consts.voxel_size_0, consts.max_num_pts, seeds,
+                                       denoise=getattr(consts, 'denoise', None))
+    _log_denoise(consts, frs)
     out = []
     for k, meta in enumerate(metas):
         s = dict(meta)
@@ -199,12 +210,55 @@ def add_descriptor_args(ap):
                          '(preprocess.estimate_normals_radius); the summary carries "fpfh_normals"')
 
 
+def add_denoise_args(ap):
+    """--denoise and its settings: outlier removal on the first-level clouds, the same on every driver (parse_with_preset adds them)"""
+    ap.add_argument('--denoise', default=None, choices=('statistical', 'radius'),
+                    help='remove outliers from every first-level cloud before the second voxel level (preprocess.prepare_fragments, '
+                         'denoise=).  statistical: open3d remove_statistical_outlier, a point stays iff the mean distance to its '
+                         '--denoise-neighbors nearest points is below the cloud\'s mean + --denoise-std-ratio standard deviations.  radius: '
+                         'remove_radius_outlier, a point stays iff more than --denoise-neighbors points lie inside --denoise-radius; the '
+                         'summary carries "denoise" = the method, its parameters and the mean removed fraction')
+    ap.add_argument('--denoise-neighbors', type=int, default=None, metavar='N',
+                    help='--denoise statistical: the neighbours of the mean distance, 1..64 (default 20); radius: the count to exceed (default 16)')
+    ap.add_argument('--denoise-std-ratio', type=float, default=None, metavar='S', help='--denoise statistical: the ratio, > 0 (default 2.0)')
+    ap.add_argument('--denoise-radius', type=float, default=None, metavar='R', help='--denoise radius: the ball radius, finite and > 0 (required)')
+
+
+def denoise_option(a):
+    """the parsed --denoise options -> prepare_fragments' `denoise` dict, None without --denoise"""
+    if getattr(a, 'denoise', None) is None:
+        return None
+    if a.denoise == 'statistical':
+        return dict(method='statistical', nb_neighbors=20 if a.denoise_neighbors is None else a.denoise_neighbors,
+                    std_ratio=2.0 if a.denoise_std_ratio is None else a.denoise_std_ratio)
+    return dict(method='radius', nb_points=16 if a.denoise_neighbors is None else a.denoise_neighbors, radius=a.denoise_radius)
+
+
 def parse_with_preset(ap, argv, driver_name):
     """-> (args, Config of --preset); a preset of another data set is an argument error"""
     from .config import preset
     add_refine_args(ap)
     add_descriptor_args(ap)
+    add_denoise_args(ap)
     a = ap.parse_args(argv)
+    if a.denoise is None:
+        for name in ('neighbors', 'std_ratio', 'radius'):
+            if getattr(a, 'denoise_' + name) is not None:
+                ap.error(f'--denoise-{name.replace("_", "-")} {getattr(a, "denoise_" + name)} is a setting of --denoise: it needs --denoise')
+    if a.denoise == 'statistical' and a.denoise_radius is not None:
+        ap.error(f'--denoise-radius {a.denoise_radius} is the ball of --denoise radius')
+    if a.denoise == 'radius' and a.denoise_std_ratio is not None:
+        ap.error(f'--denoise-std-ratio {a.denoise_std_ratio} is the ratio of --denoise statistical')
+    if a.denoise == 'radius' and a.denoise_radius is None:
+        ap.error('--denoise radius needs --denoise-radius')
+    if a.denoise_radius is not None and not (0.0 < a.denoise_radius < float('inf')):
+        ap.error(f'--denoise-radius {a.denoise_radius}: must be finite and > 0')
+    if a.denoise_std_ratio is not None and not (0.0 < a.denoise_std_ratio < float('inf')):
+        ap.error(f'--denoise-std-ratio {a.denoise_std_ratio}: must be finite and > 0')
+    if a.denoise == 'statistical' and a.denoise_neighbors is not None and not (1 <= a.denoise_neighbors <= 64):
+        ap.error(f'--denoise-neighbors {a.denoise_neighbors}: must be in 1..64 with --denoise statistical')
+    if a.denoise == 'radius' and a.denoise_neighbors is not None and a.denoise_neighbors < 0:
+        ap.error(f'--denoise-neighbors {a.denoise_neighbors}: must be >= 0')
     if a.descriptor == 'fpfh' and a.stage_metrics:
         ap.error('--stage-metrics measures the stages of the learned path: not available with --descriptor fpfh')
     if a.estimator != 'ransac' and a.descriptor != 'fpfh':
@@ -255,6 +309,9 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
     from . import dist as bdist
     from .pipeline import BufferPipeline
     rank, world, dev, cdev = ranks
+    denoise = denoise_option(a)
+    if denoise is not None:                                  # read by pack_pair / pack_pairs, which log the removed fractions
+        ds.denoise, ds.denoise_log = denoise, []
     fpfh = getattr(a, 'descriptor', 'buffer') == 'fpfh'
     if fpfh:
         from .fpfh import FpfhRegistration
@@ -275,6 +332,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
             pipe.calibrate(host)
         pipe.limits = bdist.broadcast_limits(pipe.limits if rank == 0 else [0, 0, 0], device=cdev)
     ids = bdist.shard_indices(len(ds), rank, world)
+    if denoise is not None:
+        ds.denoise_log.clear()                               # (the calibration pairs come again below)
     t0 = time.perf_counter()
     refine = None
     if getattr(a, 'refine', None):
@@ -328,6 +387,8 @@ def run(a, cfg, ds, ranks, *, summarize, dgr_thresholds, labels, log_root, calib
                 kc = np.concatenate(pipe.keypoint_counts_log or [np.zeros(0, np.int64)])
                 out['keypoints'] = dict(detector='iss', salient_radius=pipe.iss_salient_radius, non_max_radius=pipe.iss_non_max_radius,
                                         mean_per_cloud=float(kc.mean()) if len(kc) else 0.0)
+        if denoise is not None:                              # (the mean is this rank's: the fractions stay on the rank that found them)
+            out['denoise'] = dict(denoise, removed=float(np.mean(ds.denoise_log)) if ds.denoise_log else 0.0)
         if ref_out is not None:
             out['refined'] = ref_out
             if 'normals' in refine:

@@ -106,6 +106,9 @@ class FpfhRegistration:
     salient / non-max radii iss_salient_factor / iss_non_max_factor * cfg.voxel_size_0 (open3d's 6 x / 4 x resolution heuristic, the
     voxel size standing in for the resolution), iss_gamma = (gamma_21, gamma_32) and iss_min_neighbors; FPFH is still computed for
     every point, matching and the estimator then run on the keypoints' rows alone (fewer than 3 matches: the identity, as ever).
+    iss_resolution='voxel' (default): those radii.  iss_resolution='estimate': the two factors times open3d's own resolution, the mean
+    nearest-neighbour distance (preprocess.cloud_resolution) averaged over the clouds of the call: one more k = 2 search and one host
+    wait per call; `iss_radii` keeps the last call's two radii.
     `keypoint_counts` keeps the last call's keypoints per cloud (int64[2B], host); refine_batch goes on refining on the dense clouds.
     match_ratio=None (default): the mutual matches as they are.  match_ratio=R in (0, 1): Lowe's ratio test on top (match_batch).  Either
     way all pairs of a batch are matched in one match_batch call, with the rows match() gives pair by pair.
@@ -117,8 +120,11 @@ class FpfhRegistration:
 
     def __init__(self, cfg, device='cuda:0', radius_factor=5.0, max_nn=100, dist_factor=1.5, edge_similarity=0.9, estimator='ransac',
                  keypoints=None, iss_salient_factor=6.0, iss_non_max_factor=4.0, iss_gamma=(0.975, 0.975), iss_min_neighbors=5,
-                 match_ratio=None, normals='given', normal_radius_factor=2.0, normal_max_nn=30):
+                 match_ratio=None, normals='given', normal_radius_factor=2.0, normal_max_nn=30, iss_resolution='voxel'):
         self.cfg, self.device = cfg, torch.device(device)
+        if iss_resolution not in ('voxel', 'estimate'):
+            raise ValueError(f"FpfhRegistration: unknown iss_resolution {iss_resolution!r} (one of ('voxel', 'estimate'))")
+        self.iss_resolution, self.iss_factors = iss_resolution, (float(iss_salient_factor), float(iss_non_max_factor))
         if normals not in NORMALS:
             raise ValueError(f'FpfhRegistration: unknown normals {normals!r} (one of {NORMALS})')
         self.normals, self.normal_radius, self.normal_max_nn = normals, float(normal_radius_factor) * cfg.voxel_size_0, int(normal_max_nn)
@@ -196,9 +202,16 @@ class FpfhRegistration:
         grid, then the keypoints' coordinates and descriptor rows -> (points f32[K,3], per-cloud keypoint counts int32[2B], F f64[K,33]):
         what matching and the estimators then see in place of the dense clouds"""
         from . import keypoints
-        grid = ops.CellGrid(pts, lens, max(self.radius, self.iss_salient_radius, self.iss_non_max_radius))
+        r_sal, r_nms = self.iss_salient_radius, self.iss_non_max_radius
+        if self.iss_resolution == 'estimate':
+            from . import preprocess
+            res = preprocess.cloud_resolution(pts, lens)
+            res = float(res[torch.isfinite(res)].mean().item()) if bool(torch.isfinite(res).any()) else self.cfg.voxel_size_0
+            r_sal, r_nms = self.iss_factors[0] * res, self.iss_factors[1] * res
+        self.iss_radii = (r_sal, r_nms)
+        grid = ops.CellGrid(pts, lens, max(self.radius, r_sal, r_nms))
         F = compute_fpfh(pts, nrm, self.radius, self.max_nn, lens, grid=grid)
-        idx, counts = keypoints.iss_keypoints(pts, self.iss_salient_radius, self.iss_non_max_radius, self.iss_gamma[0], self.iss_gamma[1],
+        idx, counts = keypoints.iss_keypoints(pts, r_sal, r_nms, self.iss_gamma[0], self.iss_gamma[1],
                                               self.iss_min_neighbors, lengths=lens, grid=grid)
         self.keypoint_counts = counts
         self.keypoint_counts_log.append(counts)

@@ -91,6 +91,37 @@ class CellGrid:
                                _ptr(out), _ptr(cnt), _ptr(max_count), _ptr(todo), _stream()), "buf_grid_query")
         return (out, cnt) if counts else out
 
+    def knn(self, queries, q_lengths, k, q_order=None, return_d2=False):
+        """grid_knn on this grid."""
+        return grid_knn(self, queries, q_lengths, k, q_order, return_d2)
+
+
+def grid_knn(grid, queries, q_lengths, k, q_order=None, return_d2=False):
+    """buf_grid_knn: the exact k nearest supports (1 <= k <= 64) of every query f32[nq,3] inside its own batch element of `grid` (a
+    CellGrid built at any radius: the cell edge affects speed only) -> int32[nq,k] (, f32[nq,k] squared distances).  Rows ascending by
+    (d2, index) like CellGrid.query's, padded with ns (+inf) where the element holds fewer than k finite supports.  q_order int32[nq]
+    (a permutation, e.g. CellGrid.order for a self query): the processing order, speed only."""
+    if not isinstance(grid, CellGrid):
+        raise ValueError("grid_knn: grid is not a CellGrid")
+    if int(k) != k or not 1 <= int(k) <= 64:
+        raise ValueError(f"grid_knn: k={k} (1 <= k <= 64)")
+    queries = _dev(queries, torch.float32, "grid_knn.queries")
+    if queries.dim() != 2 or queries.shape[1] != 3:
+        raise ValueError(f"grid_knn: queries {tuple(queries.shape)} is not [N,3]")
+    q_lengths = _host_i32(q_lengths)
+    nq = int(queries.shape[0])
+    if q_lengths.shape[0] != grid.nb or int(q_lengths.sum()) != nq or (q_lengths < 0).any():
+        raise ValueError(f"grid_knn: q_lengths {q_lengths.tolist()[:8]} do not split {nq} queries over the grid's {grid.nb} elements")
+    if q_order is not None:
+        q_order = _dev(q_order, torch.int32, "grid_knn.q_order")
+        if tuple(q_order.shape) != (nq,):
+            raise ValueError(f"grid_knn: q_order {tuple(q_order.shape)} is not [{nq}]")
+    nbr = torch.empty((nq, int(k)), dtype=torch.int32, device=queries.device)
+    d2 = torch.empty((nq, int(k)), dtype=torch.float32, device=queries.device) if return_d2 else None
+    check(_lib.lib().buf_grid_knn(C.byref(grid.g), _ptr(queries), nq, _hptr(q_lengths), _ptr(q_order), int(k), _ptr(nbr), _ptr(d2), _stream()),
+          "buf_grid_knn")
+    return (nbr, d2) if return_d2 else nbr
+
 
 def radius_neighbors(queries, supports, q_lengths, s_lengths, radius, k=None):
     """batch_query semantics on device: int32[nq, max_count] when k is None (two passes: count, fill)."""

@@ -188,7 +188,160 @@ def estimate_covariances(points, radius, max_nn=30, camera=(0.0, 0.0, 0.0), orie
     return ops.row_normals(pts, nbr, 0, None, return_cov=True)[1]
 
 
-def prepare_fragments(raws, downsample, voxel_size_0, max_num_pts=30000, seeds=None, with_normals=True):
+def _stacked(fn, points, lengths):
+    """points f32[n,3] on the device and the host lengths of the stacked clouds (one cloud without `lengths`)"""
+    pts = _dev(points, torch.float32, fn)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"{fn}: points {tuple(pts.shape)} is not [N,3]")
+    n = int(pts.shape[0])
+    lens = np.array([n], np.int32) if lengths is None else np.asarray(lengths, np.int32).reshape(-1)
+    if lens.shape[0] < 1 or (lens < 0).any() or int(lens.sum()) != n:
+        raise ValueError(f"{fn}: lengths sum to {int(lens.sum())}, points holds {n} rows")
+    return pts, lens
+
+
+def _knn_pilot_cell(pts, lens, k):
+    """Cell edge for a k-NN search: the median distance to the k-th neighbour over a few hundred sampled points of the largest cloud
+    (the pilot of estimate_normals; plumbing, it sets the grid's cell edge and so the speed, never the result)."""
+    b = int(np.argmax(lens))
+    lo, n0 = int(lens[:b].sum()), int(lens[b])
+    if n0 < 2:
+        return 1.0
+    g = torch.Generator(device=pts.device).manual_seed(0)
+    sel = torch.randperm(n0, generator=g, device=pts.device)[:256]
+    cloud = pts[lo:lo + n0].double()
+    d = torch.cdist(cloud[sel], cloud)
+    d = torch.where(torch.isfinite(d), d, torch.full_like(d, float('inf')))
+    kth = torch.topk(d, min(int(k), n0), dim=1, largest=False).values[:, -1]
+    kth = kth[torch.isfinite(kth)]
+    edge = float(kth.median().item()) if kth.numel() else 0.0
+    return edge if 0.0 < edge < float('inf') else 1.0
+
+
+def knn_search(points, k, lengths=None, grid=None, cell=None):
+    """The k nearest neighbours (1 <= k <= 64, open3d KDTreeSearchParamKNN) of every point f32[n,3] (device; several clouds stacked when
+    `lengths` int[nc] is given) inside its own cloud, itself included -> (idx int32[n,k], d2 f32[n,k]): ascending by (d2, index),
+    padded with n / +inf where the cloud holds fewer than k finite points.  One CellGrid (grid: one built elsewhere over the same points
+    and lengths, at any radius; cell: the edge to build one with; neither: a pilot's median k-th distance, the call's one host wait)
+    and one buf_grid_knn launch in the grid's order (include/buffer_hip.h N14).  The cell edge affects speed only."""
+    if int(k) != k or not 1 <= int(k) <= 64:
+        raise ValueError(f"knn_search: k={k} (1 <= k <= 64)")
+    if cell is not None and not (0.0 < float(cell) < float('inf')):
+        raise ValueError(f"knn_search: cell={cell} (finite, > 0)")
+    if cell is not None and grid is not None:
+        raise ValueError("knn_search: both a grid and a cell edge given")
+    pts, lens = _stacked("knn_search", points, lengths)
+    n = int(pts.shape[0])
+    if grid is not None and (grid.ns != n or not np.array_equal(grid.s_lengths, lens)):
+        raise ValueError("knn_search: the given grid does not cover these clouds")
+    if n == 0:
+        return (torch.zeros((0, int(k)), dtype=torch.int32, device=pts.device), torch.zeros((0, int(k)), dtype=torch.float32, device=pts.device))
+    if grid is None:
+        grid = ops.CellGrid(pts, lens, float(cell) if cell is not None else _knn_pilot_cell(pts, lens, k))
+    return ops.grid_knn(grid, grid.supports, lens, int(k), q_order=grid.order, return_d2=True)
+
+
+def nearest_neighbor_distance(points, lengths=None):
+    """open3d compute_nearest_neighbor_distance: f64[n], sqrt((double) d2) of column 1 of the k = 2 rows of knn_search -- the distance
+    from every point to the nearest OTHER point of its cloud: 0 for a duplicate, +inf for a one-point cloud (and for a non-finite point)."""
+    idx, d2 = knn_search(points, 2, lengths)
+    return d2[:, 1].double().sqrt()
+
+
+def cloud_resolution(points, lengths=None):
+    """The mean nearest-neighbour distance of every cloud over its finite values (open3d's usual `resolution`) -> f64[nc] on the device;
+    NaN for a cloud without a finite value."""
+    pts, lens = _stacked("cloud_resolution", points, lengths)
+    d = nearest_neighbor_distance(pts, lens)
+    seg = torch.repeat_interleave(torch.arange(len(lens), device=d.device), torch.as_tensor(lens, dtype=torch.int64, device=d.device))
+    ok = torch.isfinite(d)
+    s = torch.zeros(len(lens), dtype=torch.float64, device=d.device).index_add_(0, seg[ok], d[ok])
+    c = torch.zeros(len(lens), dtype=torch.float64, device=d.device).index_add_(0, seg[ok], torch.ones_like(d[ok]))
+    return s / c
+
+
+def remove_statistical_outlier(points, nb_neighbors=20, std_ratio=2.0, lengths=None):
+    """open3d remove_statistical_outlier (0.13, restated: include/buffer_hip.h N15 holds the rule) for stacked clouds ->
+    (keep bool[n], new_lengths int32[nc] on the host, mean_i f64[n], [mu, sd, thr] f64[nc,3]).  mean_i = the mean distance from a point
+    to its nb_neighbors nearest (itself counted); a point stays iff 0 < mean_i < mu + std_ratio * sd of its cloud.  knn_search, then
+    buf_outlier_statistical (fixed summation order: a cloud's numbers are the same bits alone or stacked); one read-back, the counts
+    (behind knn_search's pilot)."""
+    if int(nb_neighbors) != nb_neighbors or not 1 <= int(nb_neighbors) <= 64:
+        raise ValueError(f"remove_statistical_outlier: nb_neighbors={nb_neighbors} (1 <= nb_neighbors <= 64)")
+    if not float(std_ratio) > 0.0:
+        raise ValueError(f"remove_statistical_outlier: std_ratio={std_ratio} (> 0)")         # open3d: std_ratio <= 0 is an error
+    pts, lens = _stacked("remove_statistical_outlier", points, lengths)
+    L = _lib.lib()
+    n, nc, k = int(pts.shape[0]), int(lens.shape[0]), int(nb_neighbors)
+    _, d2 = knn_search(pts, k, lens)
+    mean = torch.empty((n,), dtype=torch.float64, device=pts.device)
+    stats = torch.empty((nc, 3), dtype=torch.float64, device=pts.device)
+    keep = torch.empty((n,), dtype=torch.uint8, device=pts.device)
+    kept = torch.empty((nc,), dtype=torch.int32, device=pts.device)
+    nbytes = L.buf_outlier_statistical_ws_bytes(nc)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    check(L.buf_outlier_statistical(_ptr(d2), n, k, lens.ctypes.data_as(C.c_void_p), nc, float(std_ratio), _ptr(mean), _ptr(stats),
+                                    _ptr(keep), _ptr(kept), _ptr(ws), nbytes, _stream()), "buf_outlier_statistical")
+    return keep.bool(), kept.cpu().numpy(), mean, stats
+
+
+def remove_radius_outlier(points, nb_points, radius, lengths=None):
+    """open3d remove_radius_outlier for stacked clouds -> (keep bool[n], new_lengths int32[nc] on the host): a point stays iff more than
+    nb_points points of its cloud, itself counted, lie within `radius` of it (d2 < r * r in fp32, the grid's test).  The untruncated
+    counts of one count-only CellGrid.query; one read-back, the per-cloud counts."""
+    if int(nb_points) != nb_points or int(nb_points) < 0:
+        raise ValueError(f"remove_radius_outlier: nb_points={nb_points} (an integer >= 0)")
+    r = float(radius)
+    if not (0.0 < r < float('inf')):
+        raise ValueError(f"remove_radius_outlier: radius={radius} (finite, > 0)")
+    pts, lens = _stacked("remove_radius_outlier", points, lengths)
+    n = int(pts.shape[0])
+    if n == 0:
+        return torch.zeros((0,), dtype=torch.bool, device=pts.device), np.zeros(len(lens), np.int32)
+    grid = ops.CellGrid(pts, lens, r)
+    _, cnt = grid.query(pts, lens, 0, radius=r, q_order=grid.order, counts=True)
+    keep = cnt > int(nb_points)
+    seg = torch.repeat_interleave(torch.arange(len(lens), device=pts.device), torch.as_tensor(lens, dtype=torch.int64, device=pts.device))
+    kept = torch.zeros(len(lens), dtype=torch.int64, device=pts.device).index_add_(0, seg, keep.long())
+    return keep, kept.cpu().numpy().astype(np.int32)
+
+
+def estimate_normals_knn(points, knn=30, camera=(0.0, 0.0, 0.0), orient=True, lengths=None, return_cov=False):
+    """open3d estimate_normals(KDTreeSearchParamKNN(knn)) [+ orient_normals_towards_camera_location(camera)] in one pass: knn_search,
+    then ops.row_normals on those rows (the arithmetic of estimate_normals_radius on the knn nearest points, the point itself counted)
+    -> unit normals f32[n,3] (, covariances f64[n,6]).  Two launches behind the grid build, no retry loop, nothing read back after
+    the pilot.  Not bit-equal to estimate_normals, which re-ranks 40 fp32 candidates in fp64 and sums about the origin."""
+    if int(knn) != knn or not 1 <= int(knn) <= 64:
+        raise ValueError(f"estimate_normals_knn: knn={knn} (1 <= knn <= 64)")
+    pts, lens = _stacked("estimate_normals_knn", points, lengths)
+    if int(pts.shape[0]) == 0:
+        out = torch.zeros((0, 3), dtype=torch.float32, device=pts.device)
+        return (out, torch.zeros((0, 6), dtype=torch.float64, device=pts.device)) if return_cov else out
+    idx, _ = knn_search(pts, int(knn), lens)
+    return ops.row_normals(pts, idx, 0, camera if orient else None, return_cov=return_cov)
+
+
+def denoise_clouds(points, lengths, denoise):
+    """The `denoise` option of prepare_fragments on stacked clouds f32[n,3]: dict(method='statistical', nb_neighbors=20, std_ratio=2.0)
+    or dict(method='radius', nb_points=16, radius=...) -> (keep bool[n], new_lengths int32[nc] on the host)."""
+    opt = dict(denoise)
+    method = opt.pop('method', None)
+    if method == 'statistical':
+        nb, ratio = opt.pop('nb_neighbors', 20), opt.pop('std_ratio', 2.0)
+        if opt:
+            raise ValueError(f"denoise: unknown option(s) {sorted(opt)} for method 'statistical'")
+        return remove_statistical_outlier(points, nb, ratio, lengths)[:2]
+    if method == 'radius':
+        if 'radius' not in opt:
+            raise ValueError("denoise: method 'radius' needs a radius")
+        nb, radius = opt.pop('nb_points', 16), opt.pop('radius')
+        if opt:
+            raise ValueError(f"denoise: unknown option(s) {sorted(opt)} for method 'radius'")
+        return remove_radius_outlier(points, nb, radius, lengths)
+    raise ValueError(f"denoise: method={method!r} ('statistical' or 'radius')")
+
+
+def prepare_fragments(raws, downsample, voxel_size_0, max_num_pts=30000, seeds=None, with_normals=True, denoise=None):
     """The test-split branch of ThreeDMatchDataset.__getitem__ (dataset.py:93-95,125-153) for SEVERAL fragments:
     raws: list of f32[n,3] device tensors -> list of dict(fds_pts f32[N,3] shuffled, sds_pts f32[M,6] = shuffled
     second-level points + normals).  The two voxel levels and the shuffles run per fragment (second level on the first
@@ -200,6 +353,11 @@ def prepare_fragments(raws, downsample, voxel_size_0, max_num_pts=30000, seeds=N
         return out
     # both voxel levels for all fragments at once (second level on the first level's fp64 means: chained open3d calls)
     fds_all, fds_lens = voxel_down_sample_batch(torch.cat(raws) if len(raws) > 1 else raws[0], [int(r.shape[0]) for r in raws], downsample)
+    removed = None
+    if denoise is not None:                # outlier removal on the first level (fp32 cast of the means), all fragments in one stacked pass
+        keep, kept_lens = denoise_clouds(fds_all.float(), fds_lens, denoise)
+        removed = 1.0 - kept_lens / np.maximum(fds_lens, 1)
+        fds_all, fds_lens = fds_all[keep], kept_lens.astype(fds_lens.dtype)
     sds_all64, sds_lens = voxel_down_sample_batch(fds_all, fds_lens, voxel_size_0)
     fds32, sds32_all = fds_all.float(), sds_all64.float()
     fo = np.concatenate([[0], np.cumsum(fds_lens)])
@@ -228,11 +386,13 @@ def prepare_fragments(raws, downsample, voxel_size_0, max_num_pts=30000, seeds=N
         for i, s in enumerate(sds_all):
             sds_all[i] = torch.cat([s, nrm[lo:lo + lens[i]]], dim=1).contiguous()
             lo += lens[i]
-    for o, s in zip(out, sds_all):
+    for i, (o, s) in enumerate(zip(out, sds_all)):
         o['sds_pts'] = s
+        if removed is not None:
+            o['denoise_removed'] = float(removed[i])     # fraction of the fragment's first-level points the filter took out
     return out
 
 
-def prepare_fragment(raw_points, downsample, voxel_size_0, max_num_pts=30000, seed=0, with_normals=True):
+def prepare_fragment(raw_points, downsample, voxel_size_0, max_num_pts=30000, seed=0, with_normals=True, denoise=None):
     """One fragment of prepare_fragments: raw f32[n,3] -> dict(fds_pts f32[N,3] shuffled, sds_pts f32[M,6])."""
-    return prepare_fragments([raw_points], downsample, voxel_size_0, max_num_pts, [seed], with_normals)[0]
+    return prepare_fragments([raw_points], downsample, voxel_size_0, max_num_pts, [seed], with_normals, denoise)[0]

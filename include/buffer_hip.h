@@ -709,6 +709,49 @@ int     buf_row_normals(const float* pts, int n, const int* nbr, int k_nbr, int 
                         const double* camera_host, int orient, float* normals_out /* f32[n,3], nullable */,
                         double* cov_out /* f64[n,6], nullable */, int* count_out /* int32[n], nullable */, void* stream);
 
+/* N14  Exact k nearest neighbours in 3-D on the cell grid (open3d KDTreeSearchParamKNN).  One launch for any number of stacked clouds,
+ * no workspace beyond the grid's, nothing read back.
+ * g: a grid of buf_grid_build, at whatever radius it was built (the cell edge affects speed only).  queries f32[nq,3], element b of the
+ * grid owning the next q_batches_host[b] of them: a query's candidates are the supports of its own element.
+ * Distance: d2 = (dx*dx + dy*dy) + dz*dz in fp32 without contraction, buf_grid_query's.  A pair whose d2 is not finite -- a NaN or
+ * infinite coordinate on either side, or an overflow -- matches nothing (buf_grid_query's d2 < r*r never accepts one either): a
+ * non-finite support is in no row and a non-finite query has a fully padded row.
+ * Row qi of nbr_out int32[nq,k]: the k smallest keys (bits of d2, global support index) in ascending order, so ties go to the lower
+ * index exactly as in a buf_grid_query row -- wherever such a row at some radius holds k entries or more, its first k are this row.
+ * Fewer than k matches: the tail is padded with ns (g->ns).  d2_out (nullable) f32[nq,k]: the d2 of every entry, +inf in the padding.
+ * 1 <= k <= 64.  q_order (nullable) int32[nq]: slot t of the launch handles query q_order[t], as in buf_grid_query (an entry outside
+ * [0, nq) is skipped); the result does not depend on it.
+ * Search: rings of cells at Chebyshev distance 0, 1, 2, ... around the query's cell (a query outside the box starts from the nearest
+ * border cell), closed once the k-th d2 lies strictly below the squared distance from the query to the nearest face of the visited
+ * cube inside the grid (taken in fp64 from the build's cell arithmetic, reduced by a margin that covers the fp32 rounding of d2), or
+ * once the cube covers the element's grid.  At most max(dim) + 1 rings on any input.
+ * No atomics: a query's row is the same bits alone, in any batch, under any q_order and on reruns.
+ * BUF_EINVAL before any device work, buf_last_error naming the value, for a null g or q_batches_host, nq < 0, k outside [1, 64],
+ * lengths that are negative or do not sum to nq, and with nq > 0 a null queries or nbr_out.  nq == 0 succeeds and writes no output;
+ * the queries of an empty element get padded rows. */
+int     buf_grid_knn(const buf_grid_t* g, const float* queries, int nq, const int* q_batches_host, const int* q_order /* nullable */,
+                     int k, int* nbr_out /* int32[nq,k] */, float* d2_out /* nullable f32[nq,k] */, void* stream);
+
+/* N15  The sums of open3d's remove_statistical_outlier (0.13, restated from the published form, parity unpinned: this text is the
+ * specification) on k-NN rows: nc stacked clouds per call, two launches, no float atomics, nothing read back.
+ * d2 f32[n,k]: a buf_grid_knn d2 row per point (self query, the point itself in column 0, +inf padding at the tail); cloud c owns
+ * the next lengths_host[c] rows.
+ *   mean_i  = the fp64 sum, in column order, of sqrt((double) d2_ij) over the row's entries before the first that is not finite,
+ *             divided by their number; -1 for a row without entries.                                         -> mean_out f64[n]
+ *   V       = the cloud's number of rows with entries; mu = (sum of the mean_i > 0) / V;
+ *   sd      = sqrt(sum over mean_i > 0 of (mean_i - mu)^2 / (V - 1)); thr = mu + std_ratio * sd.     -> stats_out f64[nc,3] = mu, sd, thr
+ *   keep_i  = mean_i > 0 && mean_i < thr.                                -> keep_out u8[n], kept_out int32[nc] = kept rows per cloud
+ * The rule is followed literally: a cloud of one point has V - 1 = 0, sd = NaN and keeps nothing; a cloud of two points has sd = 0,
+ * thr = mu = both means and keeps nothing; an empty cloud has mu = NaN.
+ * Sums per cloud: thread t of 256 adds the cloud's rows t, t + 256, ... in that order, the 256 partial sums are folded by a binary
+ * tree with strides 128, 64, ..., 1.  The order depends on the cloud's length alone: a cloud's numbers are the same bits alone or stacked.
+ * ws: int32[nc + 1] device scratch (buf_outlier_statistical_ws_bytes).  BUF_EINVAL for n < 0, k < 1, nc < 1, a NaN std_ratio, lengths
+ * that are negative or do not sum to n, a null lengths_host, stats_out, kept_out or ws, and with n > 0 a null d2, mean_out or keep_out. */
+size_t  buf_outlier_statistical_ws_bytes(int nc);
+int     buf_outlier_statistical(const float* d2, int n, int k, const int* lengths_host, int nc, double std_ratio,
+                                double* mean_out /* f64[n] */, double* stats_out /* f64[nc,3] */, unsigned char* keep_out /* u8[n] */,
+                                int* kept_out /* int32[nc] */, void* ws, size_t ws_bytes, void* stream);
+
 /* N12  Batched descriptor matching with a mutual and a ratio filter: exact, ragged, `pairs` pairs per call.  One scan launch for both
  * directions of all pairs, two small launches for the filters and the ordered output; no atomics; the host reads nothing back.
  * Pair p owns a_lengths_host[p] / b_lengths_host[p] consecutive rows of fa / fb (f32[., d], device, 1 <= d <= 64): A_p and B_p.
