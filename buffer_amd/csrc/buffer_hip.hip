@@ -33,7 +33,8 @@
 #include "costnet.hip"
 #include "costnet_w24.hip"
 #include "costnet_w24b.hip"
-#include "cnn_launch.hip"             // the host side of the six fused CNN kernels above: behind all of them
+#include "costnet_body.hip"           // the cost net's one body and kernel pair: behind the layer forms of the three files above
+#include "cnn_launch.hip"             // the host side of the four fused CNN kernels above: behind all of them
 #include "split_safe.hip"
 #include "fpfh.hip"
 #include "iss.hip"

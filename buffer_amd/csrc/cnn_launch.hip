@@ -3,8 +3,9 @@
 //   descriptor net   k_cyl_net_wg | _w24k | _w25t (csrc/convnet_wg.hip, _w24k.hip, _w25t.hip) and their _rerun twins take the same
 //                    arguments (CylWgParams): cyl_check states the rules of a stack once, cyl_prepare fills the parameters and picks
 //                    the kernel (cyl_kernel_for), cyl_launch launches it -- the plain kernel, or with P.only_if its masked twin.
-//   cost net         k_cost_net | _w24 | _w24b (csrc/costnet*.hip) differ in their parameter struct: cost_net_prepare / cost_net_launch
-//                    are templates over it, cost_net_run is what the six dense and gathered entry points share.
+//   cost net         k_cost_net_w24b and its _rerun twin (csrc/costnet_body.hip) run every layer form: cost_net_prepare fills the
+//                    parameters with the filter sets an entry point takes (none, three or five; the rest null), cost_net_launch
+//                    launches, cost_net_run is what the six dense and gathered entry points share.
 //
 // Everything is checked before the first device call, and every message names the entry point it always named.  The split-safe entry
 // points (csrc/split_safe.hip) prepare the same way and hand the prepared fp32 re-run to one body per family.
@@ -298,29 +299,16 @@ extern "C" int buf_cylindrical_net_w25t(const float* x, int npatch, const float*
 }
 
 // ---- cost net ---------------------------------------------------------------------------------------------------------------------
-// A kernel and its masked twin over the parameter struct Q (CostNetParams, or CostNetW24Params / CostNetW24BParams: the same with the
-// filter sets f24[] behind it); name: what CV_STAMP prints
-template <typename Q>
-struct CostKernel { void (*plain)(const float*, const float*, Q, float*); void (*rerun)(const float*, const float*, Q, float*); const char* name; LdsGrant grant, grant_rerun; };
-static CostKernel<CostNetParams> cost_f22 = { k_cost_net, k_cost_net_rerun, "k_cost_net" };
-static CostKernel<CostNetW24Params> cost_w24 = { k_cost_net_w24, k_cost_net_w24_rerun, "k_cost_net_w24" };
-static CostKernel<CostNetW24BParams> cost_w24b = { k_cost_net_w24b, k_cost_net_w24b_rerun, "k_cost_net_w24b" };
+// The kernel and its masked twin; the LDS grants are per kernel symbol
+struct CostKernel { void (*plain)(const float*, const float*, CostNetParams, float*); void (*rerun)(const float*, const float*, CostNetParams, float*); LdsGrant grant, grant_rerun; };
+static CostKernel cost_kernel = { k_cost_net_w24b, k_cost_net_w24b_rerun };
 
-static CostNetParams& cost_net_base(CostNetParams& P) { return P; }
-template <typename Q> static CostNetParams& cost_net_base(Q& q) { return q.P; }
-static void cost_net_sets(CostNetParams&, const float* const*) {}
-template <typename Q> static void cost_net_sets(Q& q, const float* const* f24_host)
+// The kernel parameters of a launch.  f24_host: the first nsets (0, 3 or 5: what the entry point takes) filter sets of CostNetParams::f24,
+// DEVICE pointers with nullable entries; the sets behind them are null, and a layer without a set runs its first form.  only_if: the
+// masked twin's flags.
+static int cost_net_prepare(CostNetParams& P, const float* const* wt_host, const float* const* bias_host, const float* const* f24_host, int nsets,
+                            const long long* s_rows, const long long* t_rows, int ele_n, const int* only_if, const char* who)
 {
-    for (size_t i = 0; i < sizeof(q.f24) / sizeof(q.f24[0]); i++) q.f24[i] = f24_host[i];
-}
-
-// The kernel parameters of a launch; f24_host (DEVICE pointers, nullable entries: a layer without a set runs as in the kernel before)
-// is read by the kernels that take sets.  only_if: the masked twin's flags.
-template <typename Q>
-static int cost_net_prepare(Q& q, const float* const* wt_host, const float* const* bias_host, const float* const* f24_host, const long long* s_rows,
-                            const long long* t_rows, int ele_n, const int* only_if, const char* who)
-{
-    CostNetParams& P = cost_net_base(q);
     for (int l = 0; l < CV_LAYERS; l++) {
         P.wt[l] = wt_host[l]; P.bias[l] = bias_host[l];
         BUF_REQUIRE(P.wt[l] && P.bias[l], BUF_EINVAL, "%s: null weights for layer %d", who, l);
@@ -330,12 +318,12 @@ static int cost_net_prepare(Q& q, const float* const* wt_host, const float* cons
     P.row_floats = 32 * P.chan_floats;
     P.skip_floats = s_rows ? 20 : 0;                         // elevation row 0 of every channel is not part of the cost volume
     P.only_if = only_if;
-    cost_net_sets(q, f24_host);
+    for (int i = 0; i < 5; i++) P.f24[i] = i < nsets ? f24_host[i] : nullptr;
     return BUF_OK;
 }
 
-// EXECUTED flops per match of k_cost_net: layer 0 in its separated form (S-term 60 x 480 x 32, T-term 54 x 288 x 32 MAC instead of the
-// dense 972 x 864 x 32), then the valid convolutions 18x3x18 -> 16x1x16 -> 14 -> 12 -> 10 -> 8 -> 6 -> 4 -> 2 -> 1:
+// EXECUTED flops per match of the net with every layer in its first form: layer 0 in its separated form (S-term 60 x 480 x 32,
+// T-term 54 x 288 x 32 MAC instead of the dense 972 x 864 x 32), then the valid convolutions 18x3x18 -> 16x1x16 -> 14 -> 12 -> 10 -> 8 -> 6 -> 4 -> 2 -> 1:
 // 2 * sum(out positions * K * Cout), layers 1..5 with 16 products per 2 x 2 output tile (Winograd) = 0.0519 GFLOP.  The dense algorithmic count of SURVEY 8d is 0.160 GFLOP/match
 // (bench.py reports both; the roofline fraction is taken on the executed count).
 static const double cost_net_macs_per_match =
@@ -350,7 +338,7 @@ static int cv_stamp_begin(int m, long long** stamps)
     BUF_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cv_stamp_ptr), stamps, sizeof(*stamps)));
     return BUF_OK;
 }
-static int cv_stamp_end(int m, long long* stamps, void* stream, const char* kernel)
+static int cv_stamp_end(int m, long long* stamps, void* stream)
 {
     if (m >= 2048) {
         BUF_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
@@ -360,7 +348,7 @@ static int cv_stamp_end(int m, long long* stamps, void* stream, const char* kern
         double d[8] = {};
         for (int b = m / 2; b < m; b++)
             for (int i = 0; i < 8; i++) d[i] += (double)(h[(size_t)b * 16 + i + 1] - h[(size_t)b * 16 + i]);
-        for (int i = 0; i < 8; i++) fprintf(stderr, "  CV_STAMP %s %-20s %8.0f cycles per match\n", kernel, name[i], d[i] / (m - m / 2));
+        for (int i = 0; i < 8; i++) fprintf(stderr, "  CV_STAMP k_cost_net_w24b %-20s %8.0f cycles per match\n", name[i], d[i] / (m - m / 2));
         free(h);
     }
     (void)hipFree(stamps);
@@ -368,53 +356,51 @@ static int cv_stamp_end(int m, long long* stamps, void* stream, const char* kern
 }
 #endif
 
-// m matches through kernel K with the prepared q; with only_if in it the masked twin instead
-template <typename Q>
-static int cost_net_launch(CostKernel<Q>& K, const float* s_eq, const float* t_eq, int m, Q q, float* ind_out, void* stream)
+// m matches through the kernel with the prepared P; with only_if in it the masked twin instead
+static int cost_net_launch(const float* s_eq, const float* t_eq, int m, const CostNetParams& P, float* ind_out, void* stream)
 {
-    const bool rerun = cost_net_base(q).only_if != nullptr;
+    const bool rerun = P.only_if != nullptr;
     size_t lds = sizeof(float) * CV_BUF;
-    if (int rc = rerun ? grant_dynamic_lds((const void*)K.rerun, lds, K.grant_rerun) : grant_dynamic_lds((const void*)K.plain, lds, K.grant)) return rc;
-    // every kernel's span keeps k_cost_net's figure (16 products per 2 x 2 tile in layers 1..5, layer 6 direct): bench.py counts the
-    // matches of a launch by it (a masked re-run is not a full launch)
+    if (int rc = rerun ? grant_dynamic_lds((const void*)cost_kernel.rerun, lds, cost_kernel.grant_rerun) : grant_dynamic_lds((const void*)cost_kernel.plain, lds, cost_kernel.grant)) return rc;
+    // whatever forms the layers take, the span keeps the first forms' figure (16 products per 2 x 2 tile in layers 1..5, layer 6 direct):
+    // bench.py counts the matches of a launch by it (a masked re-run is not a full launch)
     TimedSpan span;
     bool timed = !rerun && timing_begin((hipStream_t)stream, &span, 2.0 * cost_net_macs_per_match * m, BUF_TIMED_COST_NET);
 #ifdef CV_STAMP
     long long* stamps = nullptr;
     if (int rc = cv_stamp_begin(m, &stamps)) return rc;
 #endif
-    const auto kernel = rerun ? K.rerun : K.plain;
-    kernel<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, q, ind_out);
+    const auto kernel = rerun ? cost_kernel.rerun : cost_kernel.plain;
+    kernel<<<m, CV_THREADS, lds, (hipStream_t)stream>>>(s_eq, t_eq, P, ind_out);
     if (timed) timing_end((hipStream_t)stream, &span);
     BUF_LAUNCH_CHECK();
 #ifdef CV_STAMP
-    if (int rc = cv_stamp_end(m, stamps, stream, K.name)) return rc;
+    if (int rc = cv_stamp_end(m, stamps, stream)) return rc;
 #endif
     return BUF_OK;
 }
 
 // What the dense and the gathered entry points share.  Dense (s_rows, t_rows null): s_eq, t_eq f32[m,32,5,20]; gathered: s_eq = t_eq =
-// equi f32[rows,32,ele_n,20] with int64 row ids on the device.  The kernels that take sets need f24_host.
-template <typename Q>
-static int cost_net_run(const char* who, CostKernel<Q>& K, bool gathered, const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows,
+// equi f32[rows,32,ele_n,20] with int64 row ids on the device.  nsets: the filter sets the entry point takes; those that take any need f24_host.
+static int cost_net_run(const char* who, int nsets, bool gathered, const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows,
                         const long long* t_rows, int m, const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
                         float* ind_out, void* stream)
 {
     if (gathered) BUF_REQUIRE(m >= 0 && ele_n == 7, BUF_EINVAL, "%s: m=%d ele_n=%d (the kernel is built for ele_n = 7)", who, m, ele_n);
     else BUF_REQUIRE(m >= 0, BUF_EINVAL, "%s: m=%d", who, m);
     if (m == 0) return BUF_OK;
-    BUF_REQUIRE(s_eq && t_eq && (!gathered || (s_rows && t_rows)) && wt_host && bias_host && (f24_host || std::is_same<Q, CostNetParams>::value) && ind_out,
+    BUF_REQUIRE(s_eq && t_eq && (!gathered || (s_rows && t_rows)) && wt_host && bias_host && (f24_host || nsets == 0) && ind_out,
                 BUF_EINVAL, "%s: null argument", who);
-    Q q;
-    if (int rc = cost_net_prepare(q, wt_host, bias_host, f24_host, s_rows, t_rows, ele_n, nullptr, who)) return rc;
-    return cost_net_launch(K, s_eq, t_eq, m, q, ind_out, stream);
+    CostNetParams P;
+    if (int rc = cost_net_prepare(P, wt_host, bias_host, f24_host, nsets, s_rows, t_rows, ele_n, nullptr, who)) return rc;
+    return cost_net_launch(s_eq, t_eq, m, P, ind_out, stream);
 }
 
 // s_eq, t_eq f32[m,32,5,20] (elevation rows 1..5 of the equivariant maps) -> ind f32[m]
 extern "C" int buf_cost_volume_net(const float* s_eq, const float* t_eq, int m, const float* const* wt_host,
                                    const float* const* bias_host, float* ind_out, void* stream)
 {
-    return cost_net_run("buf_cost_volume_net", cost_f22, false, s_eq, t_eq, 7, nullptr, nullptr, m, wt_host, bias_host, nullptr, ind_out, stream);
+    return cost_net_run("buf_cost_volume_net", 0, false, s_eq, t_eq, 7, nullptr, nullptr, m, wt_host, bias_host, nullptr, ind_out, stream);
 }
 
 // The same with the gather fused in: equi f32[rows,32,ele_n,20] holds the FULL equivariant maps of all keypoints, match i pairs
@@ -422,37 +408,37 @@ extern "C" int buf_cost_volume_net(const float* s_eq, const float* t_eq, int m, 
 extern "C" int buf_cost_volume_net_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
                                           const float* const* wt_host, const float* const* bias_host, float* ind_out, void* stream)
 {
-    return cost_net_run("buf_cost_volume_net_gather", cost_f22, true, equi, equi, ele_n, s_rows, t_rows, m, wt_host, bias_host, nullptr, ind_out, stream);
+    return cost_net_run("buf_cost_volume_net_gather", 0, true, equi, equi, ele_n, s_rows, t_rows, m, wt_host, bias_host, nullptr, ind_out, stream);
 }
 
 // buf_cost_volume_net with f24_host[3] (nullable entries, DEVICE pointers): the F(2x4) sets of layers 2 and 4 (buf_winograd_f24_tile_weights
-// of the [Cout][Cin][3][3] filters) and the F(2x2) set of layer 6 (buf_winograd_tile_filters, group 1).  A layer without a set runs as in
-// k_cost_net from wt_host.
+// of the [Cout][Cin][3][3] filters) and the F(2x2) set of layer 6 (buf_winograd_tile_filters, group 1).  A layer without a set runs its
+// F(2x2) form (layer 6: the direct form) from wt_host, as in buf_cost_volume_net.
 extern "C" int buf_cost_volume_net_w24(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
                                        const float* const* f24_host, float* ind_out, void* stream)
 {
-    return cost_net_run("buf_cost_volume_net_w24", cost_w24, false, s_eq, t_eq, 7, nullptr, nullptr, m, wt_host, bias_host, f24_host, ind_out, stream);
+    return cost_net_run("buf_cost_volume_net_w24", 3, false, s_eq, t_eq, 7, nullptr, nullptr, m, wt_host, bias_host, f24_host, ind_out, stream);
 }
 
 extern "C" int buf_cost_volume_net_w24_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
                                               const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
                                               float* ind_out, void* stream)
 {
-    return cost_net_run("buf_cost_volume_net_w24_gather", cost_w24, true, equi, equi, ele_n, s_rows, t_rows, m, wt_host, bias_host, f24_host, ind_out, stream);
+    return cost_net_run("buf_cost_volume_net_w24_gather", 3, true, equi, equi, ele_n, s_rows, t_rows, m, wt_host, bias_host, f24_host, ind_out, stream);
 }
 
 // buf_cost_volume_net_w24 with f24_host[5] (nullable entries, DEVICE pointers): the three sets of that entry point, then the F(2x4) sets
 // (buf_winograd_f24_tile_weights) of layer 1's collapsed filter [64][96 = (dk, c)][dn][dl] and of layer 3's [128][64][3][3].  A layer
-// without a set runs as in k_cost_net_w24.
+// without a set runs its F(2x2) form from wt_host.
 extern "C" int buf_cost_volume_net_w24b(const float* s_eq, const float* t_eq, int m, const float* const* wt_host, const float* const* bias_host,
                                         const float* const* f24_host, float* ind_out, void* stream)
 {
-    return cost_net_run("buf_cost_volume_net_w24b", cost_w24b, false, s_eq, t_eq, 7, nullptr, nullptr, m, wt_host, bias_host, f24_host, ind_out, stream);
+    return cost_net_run("buf_cost_volume_net_w24b", 5, false, s_eq, t_eq, 7, nullptr, nullptr, m, wt_host, bias_host, f24_host, ind_out, stream);
 }
 
 extern "C" int buf_cost_volume_net_w24b_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
                                                const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
                                                float* ind_out, void* stream)
 {
-    return cost_net_run("buf_cost_volume_net_w24b_gather", cost_w24b, true, equi, equi, ele_n, s_rows, t_rows, m, wt_host, bias_host, f24_host, ind_out, stream);
+    return cost_net_run("buf_cost_volume_net_w24b_gather", 5, true, equi, equi, ele_n, s_rows, t_rows, m, wt_host, bias_host, f24_host, ind_out, stream);
 }

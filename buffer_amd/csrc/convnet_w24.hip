@@ -154,7 +154,7 @@ __device__ __forceinline__ void w24_pass(unsigned (&RA)[4], __amdgpu_buffer_rsrc
 // The bias enters column component 1 -- the one A4^T carries into all four columns with weight 1 -- before pass 1.
 // On entry W holds the first two k-steps at wp, on exit those at wp_after.
 // NOBIAS: bias_lane may be null, as in wg_round (the upper K half of w24k_layer_ksplit, csrc/convnet_w24k.hip, carries no bias).
-// KSTEP: LDS bytes between k-steps, as in wg_round (k_cost_net_w24's maps, csrc/costnet_w24.hip).
+// KSTEP: LDS bytes between k-steps, as in wg_round (the cost net's maps, csrc/costnet_w24.hip).
 template <bool NOBIAS = false, unsigned KSTEP = WG_KSTEP>
 __device__ __forceinline__ void w24_round(unsigned (&RA)[4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_after, unsigned lofs4, unsigned lofs2,
                                           int niter, unsigned pstride, const float* __restrict__ bias_lane, wgf4 (&W4)[2][2], wgf2 (&W2)[2][2],

@@ -141,7 +141,7 @@ __device__ __forceinline__ wgf4 wg_ldw(__amdgpu_buffer_rsrc_t rs, unsigned unifo
 // offsets ride in the instructions, the weights (W[n][k-step]: one 16-byte load per lane) are reloaded in place half an
 // iteration ahead, and the last iteration fetches the weights of whatever runs next (wp_next) instead of its own.  Every
 // pass reads its own first two steps.  The N-tiles of a pair are neighbours in the weight tiling (256 floats apart).
-// KSTEP: LDS bytes between k-steps (4 channels) -- k_cost_net's Winograd layers run the same passes over other map sizes.
+// KSTEP: LDS bytes between k-steps (4 channels) -- the cost net's Winograd layers run the same passes over other map sizes.
 // PRIMED: the previous pass already fetched this pass's first two steps into D; INEXT >= 0: this pass fetches those of the row
 // component INEXT in its last iteration (the LDS latency of a pass start is then covered by the previous pass's MFMAs).
 // Weights: W[n][k-step & 1], a ring of TWO k-steps per N-tile -- the registers of a k-step are reloaded with the k-step two
@@ -225,7 +225,7 @@ __device__ __forceinline__ void wg_pass(unsigned (&RA)[3][4], __amdgpu_buffer_rs
 // -- three accumulator clears and half of the output-transform adds less per N-tile.  The bias (when this wavefront carries
 // it: K-split layers add it once) enters component (1, 1)'s accumulator before pass 1: F_1, F_2, F_3 then carry it once in
 // both columns.
-// FENCE (k_cost_net's rounds): a scheduling fence between a pass and its fold.
+// FENCE (the cost net's rounds): a scheduling fence between a pass and its fold.
 template <int NN, int T0, int T1, unsigned KSTEP = WG_KSTEP, bool FENCE = false>
 __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_rsrc_t rs, unsigned wp, unsigned wp_after, unsigned lofs, int niter,
                                          int wstride, unsigned pstride, const float* __restrict__ bias_lane, wgf4 (&W)[NN][2], wgf4 (&Y)[NN][3][2][2])
@@ -258,7 +258,7 @@ __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_r
         }
         constexpr int ICHAIN = (INEXT != 0 && wg_chains(I)) ? INEXT : -1;      // the next row component of this round, if any
         wg_pass<I, NN, T0, T1, wg_chains(I - 1), ICHAIN, KSTEP>(RA, rs, wp + I * pstride, INEXT == 0 ? wp_after : wp + (I + 1) * pstride, lofs, niter, wstride, W, acc, D);
-        if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);     // the fold is not mixed into the pass's end (k_cost_net spills without it)
+        if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);     // the fold is not mixed into the pass's end (the cost net spills without it)
 #pragma unroll
         for (int n = 0; n < NN; n++)
 #pragma unroll
@@ -277,7 +277,7 @@ __device__ __forceinline__ void wg_round(unsigned (&RA)[3][4], __amdgpu_buffer_r
                 else { Y[n][t][1][0] -= f0; Y[n][t][1][1] -= f1; }
                 // the folded values exist HERE and are pinned: left free, the compiler sinks these sums below the next pass's loop and
                 // carries the accumulators of this pass (twice the registers) through it instead -- copies (+0.8 % on k_cyl_net_wg)
-                // and, in k_cost_net, spills
+                // and, in the cost net, spills
                 if constexpr (I == 2) asm volatile("" : "+v"(Y[n][t][0][0]), "+v"(Y[n][t][0][1]));
                 else asm volatile("" : "+v"(Y[n][t][1][0]), "+v"(Y[n][t][1][1]));
             }

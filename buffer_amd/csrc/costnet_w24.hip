@@ -1,5 +1,6 @@
-// A13 -- k_cost_net_w24: k_cost_net (csrc/costnet.hip) with cheaper tilings in three of its layers.  Phase A (layer 0 separated, layer 1
-// in chunks), layers 3 and 5, layers 7..9 and the softmax are that file's code, shared and not copied (cost_net_body<W24>).
+// A13 -- the F(2x4) layer of the fused fp32 cost net (cw24_layer): the second form of layers 2 and 4, which cost_net_body
+// (csrc/costnet_body.hip) runs where CostNetParams::f24[0] / f24[1] hold the layer's F(2x4) set.  With the Winograd form of layer 6
+// (f24[2]: cw_layer of csrc/costnet.hip on an F(2x2) set) these are the three forms the entry points *_w24 added:
 //
 //   layer 2 (64 -> 64, 16 x 16 -> 14 x 14)    F(2x4, 3x3) tiles of 2 rows x 4 columns: 7 x 4 = 28 tiles in two M-tiles (16 + 12),
 //                                             2 x 24 = 48 matrix instructions per (k-step, N-tile) instead of the 64 of F(2x2)
@@ -16,14 +17,8 @@
 // (layer 2) / 10, 11 (layer 4), which are dropped; they are finite and of the map's scale, so the round-off they add to the kept
 // columns through A4^T is that of any other window word.
 //
-// Every layer is switched by its filter set: a null set runs the layer as k_cost_net does.  The kernel is cost_net_body<true> of
-// csrc/costnet.hip; this file has the F(2x4) layer and the kernels; their entry points: csrc/cnn_launch.hip.
+// Every layer is switched by its filter set: a null set runs the layer's F(2x2) form (layer 6: the direct form) of csrc/costnet.hip.
 #include "common.h"
-
-struct CostNetW24Params {
-    CostNetParams P;
-    const float* f24[3];           // nullable: the F(2x4) sets of layers 2 and 4 (buf_winograd_f24_tile_weights), the F(2x2) set of layer 6 (group 1)
-};
 
 // the 16 spare words behind the HIN rows of every channel of the map [C][CS]
 template <int C, int CS, int USED>
@@ -89,20 +84,4 @@ __device__ __forceinline__ void cw24_layer(float* __restrict__ map, const float*
                 if (wide) *reinterpret_cast<wgf2*>(d + 2) = (wgf2){ fmaxf(Y[n][u][2][r], 0.f), fmaxf(Y[n][u][3][r], 0.f) };
             }
     }
-}
-
-__global__ void __launch_bounds__(CV_THREADS, 2) k_cost_net_w24(const float* __restrict__ s_eq, const float* __restrict__ t_eq, CostNetW24Params Q,
-                                                            float* __restrict__ ind_out)
-{
-    extern __shared__ float lds[];
-    cost_net_body<true>(s_eq, t_eq, Q.P, ind_out, lds, Q.f24);
-}
-
-// The masked re-run of buf_cost_volume_net_split_safe_w24, under its own kernel name (see k_cost_net_rerun)
-__global__ void __launch_bounds__(CV_THREADS, 2) k_cost_net_w24_rerun(const float* __restrict__ s_eq, const float* __restrict__ t_eq, CostNetW24Params Q,
-                                                                  float* __restrict__ ind_out)
-{
-    extern __shared__ float lds[];
-    if (Q.P.only_if[blockIdx.x] == 0) return;
-    cost_net_body<true>(s_eq, t_eq, Q.P, ind_out, lds, Q.f24);
 }

@@ -1,11 +1,11 @@
-// A13 -- k_cost_net_w24b: k_cost_net_w24 (csrc/costnet_w24.hip) with cheaper tilings in two more layers.  Everything else is
-// cost_net_body of csrc/costnet.hip, shared and not copied (cost_net_body<true, true>).
+// A13 -- the second forms of layers 1 and 3 of the fused fp32 cost net (cw24b_layer1, cw24b_layer3), which cost_net_body
+// (csrc/costnet_body.hip) runs where CostNetParams::f24[3] / f24[4] hold the layer's F(2x4) set:
 //
 //   layer 1 (96 -> 64, 18 x 18 -> 16 x 16)    F(2x4, 3x3) tiles: 8 x 4 = 32 tiles in exactly two M-tiles, 2 x 24 = 48 matrix instructions per
 //                                             (k-step, N-tile) instead of the 64 of F(2x2): 6 144 -> 4 608 per match, no padded lane
 //   layer 3 (64 -> 128, 14 x 14 -> 12 x 12)   a hybrid: 5 x 3 = 15 F(2x4) tiles in ONE M-tile (output rows 0..9, 24 per unit) and the last
 //                                             tile row (output rows 10, 11) in F(2x2) (16 per unit): 40 instead of 48, 6 144 -> 5 120
-// 26 608 -> 24 048 matrix instructions per match.
+// 26 608 (the forms of csrc/costnet_w24.hip in layers 2, 4 and 6) -> 24 048 matrix instructions per match.
 //
 // Layer 1 keeps ONE k' plane of the layer-0 activation resident at a time: 32 channels x 18 rows, channel-major [32][CWB_CS1] with rows of
 // CWB_RS1 words, formed once per plane (18 rows per plane; the chunked F(2x2) form makes 24 row formations over its four overlapping
@@ -24,7 +24,7 @@
 // 13 of a 14-word row: no overread), then the round of cw_layer's M-tile 2 (tile rows 4, 5) on the existing F(2x2) set, of which only
 // tile row 5 is stored.  All outputs wait for the barrier that ends the reads.
 //
-// Every layer is switched by its filter set: a null set runs the layer as k_cost_net_w24 does.
+// Every layer is switched by its filter set: a null set runs the layer's F(2x2) form of csrc/costnet.hip (layer 1: in four chunks).
 #include "common.h"
 
 #ifndef CWB_RS1           // (a development build may pass another pair, e.g. the compact -DCWB_RS1=18 -DCWB_CS1=326: profiles/cost_f24b_ab.md)
@@ -34,11 +34,6 @@
 static_assert(32 * CWB_CS1 <= CVA_SM, "the plane ends in front of the layer-0 maps");
 static_assert(17 * CWB_RS1 + 4 * 3 + 6 <= CWB_CS1 && CWB_RS1 % 2 == 0 && CWB_CS1 % 2 == 0, "the last window stays inside the channel; ds_read_b64");
 static_assert(64 * CW_CS1 <= CV_BUF, "layer 1's output map");
-
-struct CostNetW24BParams {
-    CostNetParams P;
-    const float* f24[5];           // nullable: the three sets of k_cost_net_w24, then the F(2x4) sets of layers 1 and 3
-};
 
 // all 18 rows n' of plane kq: X[c][n' * CWB_RS1 + l'] = relu(Smap[kq][(l' - n') mod 20][c] + Tb[kq][l'][c])
 __device__ __forceinline__ void cw24b_form_plane(float* __restrict__ X, const float* __restrict__ SM, const float* __restrict__ TB, int kq)
@@ -257,20 +252,4 @@ __device__ __forceinline__ void cw24b_layer3(float* __restrict__ map, const floa
                     *reinterpret_cast<wgf2*>(p + r * CSO + u * RSO) = (wgf2){ fmaxf(Y2[n][0][u][0][r], 0.f), fmaxf(Y2[n][0][u][1][r], 0.f) };
         }
     }
-}
-
-__global__ void __launch_bounds__(CV_THREADS, 2) k_cost_net_w24b(const float* __restrict__ s_eq, const float* __restrict__ t_eq, CostNetW24BParams Q,
-                                                             float* __restrict__ ind_out)
-{
-    extern __shared__ float lds[];
-    cost_net_body<true, true>(s_eq, t_eq, Q.P, ind_out, lds, Q.f24);
-}
-
-// The masked re-run of buf_cost_volume_net_split_safe_w24b, under its own kernel name (see k_cost_net_rerun)
-__global__ void __launch_bounds__(CV_THREADS, 2) k_cost_net_w24b_rerun(const float* __restrict__ s_eq, const float* __restrict__ t_eq, CostNetW24BParams Q,
-                                                                   float* __restrict__ ind_out)
-{
-    extern __shared__ float lds[];
-    if (Q.P.only_if[blockIdx.x] == 0) return;
-    cost_net_body<true, true>(s_eq, t_eq, Q.P, ind_out, lds, Q.f24);
 }

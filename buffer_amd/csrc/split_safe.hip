@@ -5,7 +5,7 @@
 // watch tripped.  Here the decision is made on the device, per patch / per match, in the same stream, without a host round trip:
 //   1. the flags (int32 per patch) are cleared, the split kernel runs and sets flags[p] = 1 for every patch whose input or hidden
 //      activation left the range (a NaN counts: the watch compares bit patterns / uses !(a < limit));
-//   2. the fp32 kernel (csrc/convnet_wg.hip, csrc/costnet.hip) is launched over the same grid with only_if = flags: a workgroup whose
+//   2. the fp32 kernel (csrc/convnet_wg.hip, csrc/costnet_body.hip) is launched over the same grid with only_if = flags: a workgroup whose
 //      flag is clear returns at once, a flagged one recomputes its patch with the fp32 kernel's arithmetic and overwrites the result.
 // The outputs are therefore those of the split kernel where it is valid and, bit for bit, those of the fp32 kernel elsewhere; nothing
 // is ever returned from behind an overflow.  Cost when nothing trips (the normal case): one memset and np workgroups that exit on
@@ -125,25 +125,25 @@ extern "C" int buf_cylindrical_net_split_safe_w25t(const float* x, int npatch, c
 
 // The cost net likewise: dense inputs (s_rows == null: s_eq, t_eq f32[m,32,5,20]) or the gathered form (s_eq = t_eq = equi
 // f32[rows,32,ele_n,20] with ele_n = 7 and int64 row ids).  wt_split_host: 11 planes (buf_split_tile_gemm), wt_f32_host: the 10 matrices of
-// buf_cost_volume_net; the two bias sets as for those entry points.  flags_ws: DEVICE int32[m].  The re-run is K's masked twin with
-// f24_host as the fp32 entry point of that kernel takes it, so the flagged matches carry, bit for bit, what that call returns.
-template <typename Q>
-static int cost_split_safe(const char* who, CostKernel<Q>& K, const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows,
+// buf_cost_volume_net; the two bias sets as for those entry points.  flags_ws: DEVICE int32[m].  The re-run is the fp32 kernel's masked twin with
+// the nsets sets of f24_host as the fp32 entry point of the same suffix takes them, so the flagged matches carry, bit for bit, what that
+// call returns.
+static int cost_split_safe(const char* who, int nsets, const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows,
                            const long long* t_rows, int m, const void* const* wt_split_host, const float* const* bias_split_host,
                            const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host, float* ind_out,
                            int* status_dev, int* flags_ws, void* stream)
 {
     BUF_REQUIRE(m >= 0, BUF_EINVAL, "%s: m=%d", who, m);
     if (m == 0) return BUF_OK;
-    BUF_REQUIRE(s_eq && t_eq && wt_split_host && bias_split_host && wt_f32_host && bias_f32_host && (f24_host || std::is_same<Q, CostNetParams>::value) &&
+    BUF_REQUIRE(s_eq && t_eq && wt_split_host && bias_split_host && wt_f32_host && bias_f32_host && (f24_host || nsets == 0) &&
                 ind_out && flags_ws, BUF_EINVAL, "%s: null argument", who);
     BUF_REQUIRE((s_rows == nullptr) == (t_rows == nullptr), BUF_EINVAL, "%s: one row list without the other", who);
     BUF_REQUIRE(!s_rows || ele_n == 7, BUF_EINVAL, "%s: ele_n=%d (the kernels are built for ele_n = 7)", who, ele_n);
-    Q q;
-    if (int rc = cost_net_prepare(q, wt_f32_host, bias_f32_host, f24_host, s_rows, t_rows, ele_n, flags_ws, who)) return rc;
+    CostNetParams P;
+    if (int rc = cost_net_prepare(P, wt_f32_host, bias_f32_host, f24_host, nsets, s_rows, t_rows, ele_n, flags_ws, who)) return rc;
     BUF_CHECK_HIP(hipMemsetAsync(flags_ws, 0, sizeof(int) * (size_t)m, (hipStream_t)stream));
     if (int rc = cost_net_h3_launch(s_eq, t_eq, m, wt_split_host, bias_split_host, s_rows, t_rows, ele_n, ind_out, status_dev, stream, who, flags_ws)) return rc;
-    return cost_net_launch(K, s_eq, t_eq, m, q, ind_out, stream);
+    return cost_net_launch(s_eq, t_eq, m, P, ind_out, stream);
 }
 
 extern "C" int buf_cost_volume_net_split_safe(const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows, const long long* t_rows,
@@ -151,7 +151,7 @@ extern "C" int buf_cost_volume_net_split_safe(const float* s_eq, const float* t_
                                               const float* const* wt_f32_host, const float* const* bias_f32_host, float* ind_out,
                                               int* status_dev, int* flags_ws, void* stream)
 {
-    return cost_split_safe("buf_cost_volume_net_split_safe", cost_f22, s_eq, t_eq, ele_n, s_rows, t_rows, m, wt_split_host, bias_split_host, wt_f32_host,
+    return cost_split_safe("buf_cost_volume_net_split_safe", 0, s_eq, t_eq, ele_n, s_rows, t_rows, m, wt_split_host, bias_split_host, wt_f32_host,
                            bias_f32_host, nullptr, ind_out, status_dev, flags_ws, stream);
 }
 
@@ -161,7 +161,7 @@ extern "C" int buf_cost_volume_net_split_safe_w24(const float* s_eq, const float
                                                   const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,
                                                   float* ind_out, int* status_dev, int* flags_ws, void* stream)
 {
-    return cost_split_safe("buf_cost_volume_net_split_safe_w24", cost_w24, s_eq, t_eq, ele_n, s_rows, t_rows, m, wt_split_host, bias_split_host, wt_f32_host,
+    return cost_split_safe("buf_cost_volume_net_split_safe_w24", 3, s_eq, t_eq, ele_n, s_rows, t_rows, m, wt_split_host, bias_split_host, wt_f32_host,
                            bias_f32_host, f24_host, ind_out, status_dev, flags_ws, stream);
 }
 
@@ -171,6 +171,6 @@ extern "C" int buf_cost_volume_net_split_safe_w24b(const float* s_eq, const floa
                                                    const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,
                                                    float* ind_out, int* status_dev, int* flags_ws, void* stream)
 {
-    return cost_split_safe("buf_cost_volume_net_split_safe_w24b", cost_w24b, s_eq, t_eq, ele_n, s_rows, t_rows, m, wt_split_host, bias_split_host, wt_f32_host,
+    return cost_split_safe("buf_cost_volume_net_split_safe_w24b", 5, s_eq, t_eq, ele_n, s_rows, t_rows, m, wt_split_host, bias_split_host, wt_f32_host,
                            bias_f32_host, f24_host, ind_out, status_dev, flags_ws, stream);
 }

@@ -1471,9 +1471,9 @@ def separate_cost_layer0(w):
     return ws.reshape(-1, cout).astype(np.float32), wt.reshape(-1, cout).astype(np.float32)
 
 
-# What a cost net built without a form argument runs (k_cost_net_w24, csrc/costnet_w24.hip; profiles/cost_f24_ab.md): 'all': F(2x4) tiles in
-# layers 2 and 4 and the Winograd F(2x2) form in layer 6; 'l2', 'l4', 'l6': one of the three alone; 'off' or None: k_cost_net as it is, bit
-# for bit.  The argument f24= of CostVolumeNet, CostVolumeNetSplit and registration.CostVolume picks one per net.
+# What a cost net built without a form argument runs (the forms of csrc/costnet_w24.hip; profiles/cost_f24_ab.md): 'all': F(2x4) tiles in
+# layers 2 and 4 and the Winograd F(2x2) form in layer 6; 'l2', 'l4', 'l6': one of the three alone; 'off' or None: every layer in its first
+# form (F(2x2) in layers 1..5, layer 6 direct), bit for bit.  The argument f24= of CostVolumeNet, CostVolumeNetSplit and registration.CostVolume picks one per net.
 COST_F24_DEFAULT = 'all'
 COST_F24_PARTS = {'all': (2, 4, 6), 'l2': (2,), 'l4': (4,), 'l6': (6,), 'off': (), None: ()}
 
@@ -1483,7 +1483,7 @@ def cost_f24_parts(f24):
 
 
 def cost_f24_filters(layers, parts):
-    """The three extra filter sets of k_cost_net_w24 (None where the layer keeps k_cost_net's form): layers 2 and 4 in the F(2x4) tiling
+    """The three extra filter sets of the *_w24 entry points (None where the layer keeps its first form): layers 2 and 4 in the F(2x4) tiling
     (winograd_f24_tile_weights of the (3,1,3) filters as [Cout][Cin][3][3]), layer 6 in the F(2x2) tiling with one N-tile per group."""
     sets = []
     for l in (2, 4, 6):
@@ -1497,10 +1497,10 @@ def cost_f24_filters(layers, parts):
     return sets
 
 
-# The forms of k_cost_net_w24b (csrc/costnet_w24b.hip; profiles/cost_f24b_ab.md) beside those above: 'all': layer 1 on F(2x4) tiles and layer 3
-# as F(2x4) rows with an F(2x2) tail; 'l1', 'l3': one of the two alone; 'off': k_cost_net_w24 (or k_cost_net) as it is, bit for bit.  The
+# The forms of csrc/costnet_w24b.hip (profiles/cost_f24b_ab.md) beside those above: 'all': layer 1 on F(2x4) tiles and layer 3
+# as F(2x4) rows with an F(2x2) tail; 'l1', 'l3': one of the two alone; 'off': layers 1 and 3 in their F(2x2) form, bit for bit.  The
 # argument f24b= picks one per net.  Left alone it is COST_F24B_DEFAULT for a net built with no form argument at all, and 'off' beside an
-# explicit f24=, which asks for one of the older kernels.
+# explicit f24=, which asks for the net as it was before these two forms.
 COST_F24B_DEFAULT = 'all'
 COST_F24B_PARTS = {'all': (1, 3), 'l1': (1,), 'l3': (3,), 'off': ()}
 
@@ -1510,7 +1510,7 @@ def cost_f24b_parts(f24, f24b):
 
 
 def cost_f24b_filters(layers, parts):
-    """The two extra filter sets of k_cost_net_w24b (None where the layer keeps its form): winograd_f24_tile_weights of layer 1's collapsed
+    """The two extra filter sets of the *_w24b entry points (None where the layer keeps its form): winograd_f24_tile_weights of layer 1's collapsed
     filter [64][96 = (dk, c)][dn][dl] and of layer 3's (3,1,3) filter as [128][64][3][3]."""
     sets = []
     for l in (1, 3):
@@ -1532,8 +1532,8 @@ class CostVolumeNet:
     """Device weights of CostNet re-laid for csrc/costnet.hip: layer 0 in its separated form (separate_cost_layer0: Ws then
     Wt in one buffer), layers 6..9 as Wt[((dn*KH+dk)*KW+dl)*Cin + c][Cout], MFMA-tiled; layers 1..5 as U = G g G^T in the
     Winograd tiling (winograd_tile_weights; groups per buf_cost_winograd_group; layer 1 with its three k planes as channels).
-    f24: the parts that run in k_cost_net_w24's forms (COST_F24_DEFAULT); their sets live in buffers of their own (self.wt24).
-    f24b: the parts that run in k_cost_net_w24b's forms (cost_f24b_parts); their sets: self.wt24b."""
+    f24: the parts that run in the forms of csrc/costnet_w24.hip (COST_F24_DEFAULT); their sets live in buffers of their own (self.wt24).
+    f24b: the parts that run in the forms of csrc/costnet_w24b.hip (cost_f24b_parts); their sets: self.wt24b."""
 
     def __init__(self, layers, device, f24=None, f24b=None):
         """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout])"""
@@ -1543,7 +1543,7 @@ class CostVolumeNet:
         self.wt24 = [None if a is None else torch.from_numpy(a).to(device) for a in cost_f24_filters(layers, self.parts)]
         self._fp = (C.c_void_p * 3)(*[None if t is None else t.data_ptr() for t in self.wt24])
         self.wt24b = [None if a is None else torch.from_numpy(a).to(device) for a in cost_f24b_filters(layers, self.parts_b)]
-        self._fpb = (C.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in self.wt24 + self.wt24b])      # k_cost_net_w24b's five
+        self._fpb = (C.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in self.wt24 + self.wt24b])      # the five of the *_w24b entry points
         self.wt, self.bias = [], []
         for i, (w, b) in enumerate(layers):
             cout, cin = w.shape[0], w.shape[1]
@@ -1575,7 +1575,8 @@ class CostVolumeNet:
             self.bias.append(torch.from_numpy(np.ascontiguousarray(b)).to(device))
         self._wp = (C.c_void_p * 10)(*[t.data_ptr() for t in self.wt])
         self._bp = (C.c_void_p * 10)(*[t.data_ptr() for t in self.bias])
-        # The kernel, chosen once: the suffix of its dense, gathered and split-safe entry points and the sets they take behind the biases
+        # The family of entry points, chosen once (one kernel runs all three): the suffix of its dense, gathered and split-safe entry
+        # points and the sets they take behind the biases
         if self.parts_b:
             self.kernel, self._sets = "_w24b", (self._fpb,)
         elif self.parts:
@@ -1611,7 +1612,7 @@ class CostVolumeNetSplit:
     Layer 0 in its separated form (separate_cost_layer0), layer 1 with its three k' planes as channels, every layer direct form."""
 
     def __init__(self, layers, device, f24=None, f24b=None):
-        """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout]); f24, f24b: the fp32 re-run's kernel, as in CostVolumeNet"""
+        """layers: 10 x (w [Cout,Cin,KD,KH,KW] np.float32 with BN folded, b [Cout]); f24, f24b: the fp32 re-run's layer forms, as in CostVolumeNet"""
         assert len(layers) == 10
         self.parts = cost_f24_parts(f24)
         self.parts_b = cost_f24b_parts(f24, f24b)

@@ -23,9 +23,9 @@ class CostVolume:
             layers.append(_fold_bn(W[f'{p}.{i}.weight'], W[f'{p}.{i}.bias'], W[f'{p}.{bn}.running_mean'], W[f'{p}.{bn}.running_var']))
         layers.append((np.asarray(W[f'{p}.27.weight'], np.float32), np.asarray(W[f'{p}.27.bias'], np.float32)))
         # 'split': csrc/costnet_h3.hip -- the same network on the f16 matrix pipe, operands split hi + 2^-11 lo' (fp32-equivalent)
-        # f24: the parts of the fp32 kernel (and of the split form's fp32 re-run) in k_cost_net_w24's forms: 'all' | 'l2' | 'l4' | 'l6' | 'off'
+        # f24: the parts of the fp32 kernel (and of the split form's fp32 re-run) in the forms of csrc/costnet_w24.hip: 'all' | 'l2' | 'l4' | 'l6' | 'off'
         # (None: ops.COST_F24_DEFAULT)
-        # f24b: the parts in k_cost_net_w24b's forms beside them: 'all' | 'l1' | 'l3' | 'off' (None: ops.COST_F24B_DEFAULT when f24 is left
+        # f24b: the parts in the forms of csrc/costnet_w24b.hip beside them: 'all' | 'l1' | 'l3' | 'off' (None: ops.COST_F24B_DEFAULT when f24 is left
         # alone too, 'off' beside an explicit f24)
         cls = ops.CostVolumeNetSplit if arith == 'split' else ops.CostVolumeNet
         self.fused = cls(layers, device, f24=f24, f24b=f24b)

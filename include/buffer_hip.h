@@ -471,7 +471,7 @@ int     buf_cost_volume_net(const float* s_eq, const float* t_eq, int m, const f
  * match i pairs row s_rows[i] with row t_rows[i] (DEVICE int64[m]); elevation rows 1..ele_n-2 are read inside the kernel. */
 int     buf_cost_volume_net_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
                                    const float* const* wt_host, const float* const* bias_host, float* ind_out, void* stream);
-/* The twins through k_cost_net_w24 (csrc/costnet_w24.hip): F(2x4, 3x3) tiles in layers 2 and 4, the Winograd F(2x2) form in layer 6.
+/* The twins with the layer forms of csrc/costnet_w24.hip: F(2x4, 3x3) tiles in layers 2 and 4, the Winograd F(2x2) form in layer 6.
  * f24_host: HOST array of 3 DEVICE pointers, each nullable -- [0], [1]: buf_winograd_f24_tile_weights of the [Cout][Cin][3][3] filters
  * of layers 2 and 4, [2]: buf_winograd_tile_filters(w2d, 64, 64, 1, 4, out) of layer 6.  A layer without a set runs as in
  * buf_cost_volume_net from wt_host (all ten matrices are still required).  The timed span is BUF_TIMED_COST_NET with the same work figure. */
@@ -480,7 +480,7 @@ int     buf_cost_volume_net_w24(const float* s_eq, const float* t_eq, int m, con
 int     buf_cost_volume_net_w24_gather(const float* equi, int ele_n, const long long* s_rows, const long long* t_rows, int m,
                                        const float* const* wt_host, const float* const* bias_host, const float* const* f24_host,
                                        float* ind_out, void* stream);
-/* The twins through k_cost_net_w24b (csrc/costnet_w24b.hip): beside the forms above, layer 1 on F(2x4) tiles (one k' plane resident at a
+/* The twins with the layer forms of csrc/costnet_w24b.hip: beside the forms above, layer 1 on F(2x4) tiles (one k' plane resident at a
  * time) and layer 3 as F(2x4) rows with an F(2x2) tail.  f24_host: HOST array of 5 DEVICE pointers, each nullable -- [0..2] as above,
  * [3]: buf_winograd_f24_tile_weights of layer 1's collapsed filter [64][96 = (dk, c)][dn][dl], [4]: the same of layer 3's [128][64][3][3].
  * A layer without a set runs as in buf_cost_volume_net_w24.  The timed span is BUF_TIMED_COST_NET with the same work figure. */
@@ -513,12 +513,12 @@ int     buf_cost_volume_net_split_safe(const float* s_eq, const float* t_eq, int
                                        int m, const void* const* wt_split_host, const float* const* bias_split_host,
                                        const float* const* wt_f32_host, const float* const* bias_f32_host, float* ind_out,
                                        int* status_dev, int* flags_ws, void* stream);
-/* The same with the masked re-run through k_cost_net_w24_rerun: f24_host as for buf_cost_volume_net_w24, whose bits the flagged matches carry. */
+/* The same with the masked re-run in the layer forms of buf_cost_volume_net_w24: f24_host as for buf_cost_volume_net_w24, whose bits the flagged matches carry. */
 int     buf_cost_volume_net_split_safe_w24(const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows, const long long* t_rows,
                                            int m, const void* const* wt_split_host, const float* const* bias_split_host,
                                            const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,
                                            float* ind_out, int* status_dev, int* flags_ws, void* stream);
-/* ... and through k_cost_net_w24b_rerun: f24_host[5] as for buf_cost_volume_net_w24b. */
+/* ... and in those of buf_cost_volume_net_w24b: f24_host[5] as for that entry point. */
 int     buf_cost_volume_net_split_safe_w24b(const float* s_eq, const float* t_eq, int ele_n, const long long* s_rows, const long long* t_rows,
                                             int m, const void* const* wt_split_host, const float* const* bias_split_host,
                                             const float* const* wt_f32_host, const float* const* bias_f32_host, const float* const* f24_host,

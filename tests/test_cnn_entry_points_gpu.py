@@ -86,7 +86,7 @@ def test_split_safe_all(layers, patches, dev):
 def test_cost_split_safe_dense_and_gathered(W, dev):
     from buffer_amd import registration
     cvs, cv32 = registration.CostVolume(W, dev, arith='split', f24='off').fused, registration.CostVolume(W, dev, f24='off').fused
-    assert cvs.safe and cvs.f32.kernel == "" and cv32.kernel == ""     # k_cost_net / k_cost_net_rerun
+    assert cvs.safe and cvs.f32.kernel == "" and cv32.kernel == ""     # the entry points without sets
     g = torch.Generator(device='cpu').manual_seed(6)
     equi = F.normalize(torch.rand((6, 32, 7, 20), generator=g), dim=1).to(dev)
     s_rows, t_rows = torch.arange(0, 3, device=dev), torch.arange(3, 6, device=dev)

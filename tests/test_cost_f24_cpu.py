@@ -1,18 +1,22 @@
-"""Host side and code object of k_cost_net_w24 / k_cost_net_w24_rerun (csrc/costnet_w24.hip: the cost net with F(2x4) tiles in layers 2
-and 4 and the Winograd F(2x2) form in layer 6): what the kernels compiled to, read off the gfx950 code object of the in-tree library; the
-three extra filter sets and the form argument of the ops classes; the argument checks of the new entry points; and the float32
-restatement of the new arithmetic (tools/cost_f24_restate.py) at one match.  No GPU needed."""
+"""Host side and code object of the layer forms the *_w24 entry points added to the cost net (csrc/costnet_w24.hip: F(2x4) tiles in layers 2
+and 4, the Winograd F(2x2) form in layer 6), in the one kernel pair that holds every form (k_cost_net_w24b / k_cost_net_w24b_rerun,
+csrc/costnet_body.hip): the k-loops these forms brought, read off the gfx950 code object of the in-tree library; the three extra filter
+sets and the form argument of the ops classes; the argument checks of the entry points; and the float32 restatement of the arithmetic
+(tools/cost_f24_restate.py) at one match.  No GPU needed.
+
+The forms were added in two steps, each to a kernel of its own beside the one before.  The loop lists of the two retired kernels live on
+as F22_LOOPS and W24_LOOPS: the fused kernel holds all of them, and each step added exactly its own loops (the fused kernel's register
+and memory bounds, its sixteen F(2x4) pass loops and its whole list: tests/test_cost_f24b_cpu.py)."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
-from test_cyl_code_object_cpu import ROOT, code_object, kernel_meta, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_code_object_cpu import ROOT, code_object, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+from test_cyl_f24_code_object_cpu import beyond, mfma_per_loop
 
-KERNELS = ['k_cost_net_w24', 'k_cost_net_w24_rerun']
 SHAPES = [(32, 32, 3, 3, 3), (64, 32, 3, 3, 3), (64, 64, 3, 1, 3), (128, 64, 3, 1, 3), (128, 128, 3, 1, 3), (64, 128, 3, 1, 3),
           (64, 64, 3, 1, 3), (32, 64, 3, 1, 3), (32, 32, 3, 1, 3), (20, 32, 2, 1, 2)]
 
@@ -23,69 +27,39 @@ def random_layers(seed=0):
             for s in SHAPES]
 
 
-@pytest.mark.parametrize('name', KERNELS)
-def test_resources(code_object, name):
-    """No scratch, no packed-fp32 instructions, both register kinds together within 256 (two workgroups per CU), and no LDS beside the
-    dynamic buffer of CV_BUF floats, which two workgroups fit into a CU's 160 KB."""
-    asm, notes = code_object
-    m = kernel_meta(notes, name)
-    print(name, m)
-    assert m['private_segment_fixed_size'] == 0, 'scratch memory'
-    assert m['vgpr_spill_count'] == 0 and m['sgpr_spill_count'] == 0
-    assert m['vgpr_count'] <= 256 and m['agpr_count'] <= 256          # .vgpr_count of the unified file counts both kinds
-    assert m['group_segment_fixed_size'] == 0, 'static LDS beside the dynamic buffer'
-    src = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'costnet.hip')).read()
-    cv_buf = int(re.search(r'#define CV_BUF (\d+)', src).group(1))
-    launch = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'cnn_launch.hip')).read()      # (the cost kernels' one launcher)
-    assert launch.count('size_t lds = sizeof(float) * CV_BUF;') == 1 and 2 * 4 * cv_buf <= 160 * 1024
-    text = kernel_text(asm, name)
-    assert not [op for _, op, _ in text if re.match(r'v_pk_(mul|add|fma)_f32', op)]
-    assert not [op for _, op, _ in text if op.startswith('scratch_')]
-    ls = loops(text)
-    assert ls, 'no loop found: the disassembly format changed?'
-    for a, b in ls:
-        bad = [op for _, op, _ in text[a:b + 1] if op == 'ds_read2_b64']
-        assert not bad, f'{len(bad)} ds_read2_b64 in the loop at {text[a][0]:#x}'
+from test_cost_f24b_cpu import KERNELS  # noqa: E402  (behind random_layers, which that module takes from here)
+
+# MFMAs per k-loop (four k-steps per iteration; the direct layers: one tap per iteration) of the retired k_cost_net, read off a build of
+# the last commit that had it -- every layer in its first form:
+# * phase A.2 (layer 1, four chunks, a pair over one M-tile): 16 loops of 32;
+# * layers 2 and 4 in the F(2x2) form (a pair over two M-tiles): four loops each of 64;
+# * layer 3 (a pair over two M-tiles, then over the third): four loops of 64 and four of 32;
+# * layer 5 (one N-tile, one M-tile; position-major stores): four loops of 16;
+# * layer 6 direct (three M-tiles, four channel groups per tap): one loop of 48; layers 7..9: 16, 8, 8.
+F22_LOOPS = [8] * 2 + [16] * 5 + [32] * 20 + [48] + [64] * 12
+# ... and of the retired k_cost_net_w24, which added:
+# * layers 2 and 4 on F(2x4) tiles (cw24_layer -> w24_round): four pass loops each of 6 components x 2 N-tiles x 4 k-steps = 48;
+# * layer 5 once more with channel-major stores: four loops of 16;
+# * layer 6 in the Winograd form (cw_layer at one N-tile and one M-tile): four loops of 4 x 4 = 16.
+W24_LOOPS = [8] * 2 + [16] * 13 + [32] * 20 + [48] * 9 + [64] * 12
 
 
 @pytest.mark.parametrize('name', KERNELS)
 def test_matrix_instruction_count(code_object, name):
-    """Static count per k-loop, four k-steps per iteration (the direct layers: one tap per iteration).  Every layer form the kernel can be
-    switched to is in it once:
-    * phase A.2 (layer 1, four chunks, a pair over one M-tile): 16 loops of 32;
-    * layers 2 and 4 on F(2x4) tiles (cw24_layer -> w24_round): four pass loops each of 6 components x 2 N-tiles x 4 k-steps = 48;
-    * layers 2 and 4 in the F(2x2) form (no set given; a pair over two M-tiles): four loops each of 64;
-    * layer 3 (a pair over two M-tiles, then over the third): four loops of 64 and four of 32;
-    * layer 5 (one N-tile, one M-tile), built twice (channel-major / position-major stores): eight loops of 16;
-    * layer 6 in the Winograd form (cw_layer at one N-tile and one M-tile): four loops of 4 x 4 = 16;
-    * layer 6 direct (three M-tiles, four channel groups per tap): one loop of 48; layers 7..9: 16, 8, 8.
-    Outside the loops are only the two fully unrolled GEMMs of phase A.1, (30 + 18) groups x 4 k-steps x 2 N-tiles = 384, as in k_cost_net
+    """Static count per k-loop.  Every layer form the kernel can be switched to is in it once: the loops of the first forms (F22_LOOPS),
+    those the forms of csrc/costnet_w24.hip added (W24_LOOPS), and beyond them exactly the loops of csrc/costnet_w24b.hip -- layer 1 and
+    layer 3 on F(2x4) tiles, four pass loops of 48 each, and layer 3's F(2x2) tail, four loops of 32.
+    Outside the loops are only the two fully unrolled GEMMs of phase A.1, (30 + 18) groups x 4 k-steps x 2 N-tiles = 384
     (cv_gemm_static has no loop to be inside of)."""
     asm, _ = code_object
     text = kernel_text(asm, name)
-    counts = sorted(sum(1 for _, op, _ in text[a:b + 1] if op.startswith('v_mfma_f32_16x16x4')) for a, b in loops(text))
-    counts = [c for c in counts if c]
+    counts = mfma_per_loop(text)
     print(f'MFMAs per k-loop of {name}:', counts)
-    assert counts == [8] * 2 + [16] * 13 + [32] * 20 + [48] * 9 + [64] * 12, counts
+    assert sum(F22_LOOPS) == 1552 and W24_LOOPS == [8] * 2 + [16] * 13 + [32] * 20 + [48] * 9 + [64] * 12
+    assert beyond(W24_LOOPS, F22_LOOPS) == ([16] * 8 + [48] * 8, [])
+    assert beyond(counts, W24_LOOPS) == ([32] * 4 + [48] * 8, []), counts
     total = sum(1 for _, op, _ in text if op.startswith('v_mfma'))
     assert total - sum(counts) == (30 + 18) * 4 * 2
-    parent = kernel_text(asm, 'k_cost_net')
-    in_loops = sum(sum(1 for _, op, _ in parent[a:b + 1] if op.startswith('v_mfma')) for a, b in loops(parent))
-    assert sum(1 for _, op, _ in parent if op.startswith('v_mfma')) - in_loops == (30 + 18) * 4 * 2
-
-
-@pytest.mark.parametrize('name', KERNELS)
-def test_the_f24_pass_loops(code_object, name):
-    """The eight pass loops of layers 2 and 4: per iteration four k-steps of two window rows of six words (24 ds_read_b64) and 48 MFMAs, no
-    copies between the register files."""
-    asm, _ = code_object
-    text = kernel_text(asm, name)
-    hit = []
-    for a, b in loops(text):
-        ops = [op for _, op, _ in text[a:b + 1]]
-        if sum(1 for o in ops if o.startswith('v_mfma')) == 48 and ops.count('ds_read_b64') == 24:
-            hit.append(sum(1 for o in ops if o.startswith('v_accvgpr')))
-    assert hit == [0] * 8, hit
 
 
 def test_issued_count_per_match():
@@ -102,7 +76,7 @@ def test_issued_count_per_match():
 
 def test_filter_sets_and_form_argument():
     """The three sets are buf_winograd_f24_tile_weights / winograd_tile_weights (group 1) of the sliced filters, live in buffers of their
-    own, and a part that is not selected passes a null pointer: that layer runs as in k_cost_net.  The ten existing buffers do not change."""
+    own, and a part that is not selected passes a null pointer: that layer runs its first form.  The ten existing buffers do not change."""
     from buffer_amd import _lib, ops
     L = _lib.lib()
     layers = random_layers(3)

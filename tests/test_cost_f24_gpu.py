@@ -1,4 +1,4 @@
-"""k_cost_net_w24 (csrc/costnet_w24.hip: F(2x4) tiles in layers 2 and 4, the Winograd F(2x2) form in layer 6) on the GPU: the released
+"""The forms of csrc/costnet_w24.hip (F(2x4) tiles in layers 2 and 4, the Winograd F(2x2) form in layer 6) on the GPU: the released
 weights against library convolutions, fixture F5 and the network in float64; synthetic weights that make a wrong window row, tap, tile
 origin or a leaking padded column an error of order one; and the bit-for-bit properties of the entry points.  m = 1, 3 and 70 matches.
 
@@ -152,8 +152,8 @@ def test_large_positive_inputs(dev, maps, layer):
 
 def test_bit_for_bit(W, dev, maps):
     """The gather form equals the dense form; a permuted batch gives the permuted result; the masked re-run equals the plain call on the
-    flagged matches and leaves the others untouched; 'off' is k_cost_net (the entry point of the parent, whose code object
-    tests/test_cyl_code_object_cpu.py pins) and equals k_cost_net_w24 without any set; no matches: an empty tensor."""
+    flagged matches and leaves the others untouched; 'off' is the entry point without sets (every layer in its first form) and
+    equals the entry point of three sets with all three null, which guards the slots the host side fills for each; no matches: an empty tensor."""
     from buffer_amd import _lib, registration
     from buffer_amd.ops import _ptr, _stream
     a, b = maps
@@ -181,7 +181,7 @@ def test_bit_for_bit(W, dev, maps):
     assert L.buf_cost_volume_net_w24(_ptr(a), _ptr(b), 70, net._wp, net._bp, (C.c_void_p * 3)(), _ptr(out2), _stream()) == 0
     assert torch.equal(out2, want_off)
     assert not torch.equal(full, want_off)                 # (the new forms round differently: the switch does something)
-    # the masked re-run: matches beyond the f16 range go through k_cost_net_w24_rerun
+    # the masked re-run: matches beyond the f16 range go through the masked twin by buf_cost_volume_net_split_safe_w24
     for part in ('all', 'l4'):
         cv32 = registration.CostVolume(W, dev, f24=part)
         cvs = registration.CostVolume(W, dev, arith='split', f24=part)

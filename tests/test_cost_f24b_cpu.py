@@ -1,7 +1,9 @@
-"""Host side and code object of k_cost_net_w24b / k_cost_net_w24b_rerun (csrc/costnet_w24b.hip: the cost net of k_cost_net_w24 with layer 1
-on F(2x4) tiles, one k' plane resident at a time, and layer 3 as F(2x4) rows with an F(2x2) tail): what the kernels compiled to, read off
-the gfx950 code object of the in-tree library; the two extra filter sets and the form argument f24b= of the ops classes; the argument
-checks of the new entry points; and the float32 restatement of the new arithmetic (tools/cost_f24b_restate.py) at one match.  No GPU."""
+"""Host side and code object of k_cost_net_w24b / k_cost_net_w24b_rerun, the cost net's one kernel pair (csrc/costnet_body.hip: every
+layer form in one body), and the forms of csrc/costnet_w24b.hip in it -- layer 1 on F(2x4) tiles, one k' plane resident at a time, and
+layer 3 as F(2x4) rows with an F(2x2) tail: what the kernels compiled to, read off the gfx950 code object of the in-tree library; that
+they are the only fp32 cost-net kernels and have one launch path; the two extra filter sets and the form argument f24b= of the ops
+classes; the argument checks of the *_w24b entry points; and the float32 restatement of the arithmetic (tools/cost_f24b_restate.py) at
+one match.  No GPU."""
 import ctypes as C
 import os
 import re
@@ -10,10 +12,10 @@ import sys
 import numpy as np
 import pytest
 
-from test_cost_f24_cpu import random_layers
-from test_cyl_code_object_cpu import ROOT, code_object, kernel_meta, kernel_text, loops  # noqa: F401  (code_object: the module's fixture)
+KERNELS = ['k_cost_net_w24b', 'k_cost_net_w24b_rerun']       # (ahead of the next import: tests/test_cost_f24_cpu.py takes the list from here)
 
-KERNELS = ['k_cost_net_w24b', 'k_cost_net_w24b_rerun']
+from test_cost_f24_cpu import random_layers  # noqa: E402
+from test_cyl_code_object_cpu import ROOT, code_object, kernel_meta, kernel_text, loops  # noqa: E402, F401  (code_object: the module's fixture)
 
 
 @pytest.mark.parametrize('name', KERNELS)
@@ -39,6 +41,7 @@ def test_resources(code_object, name):
     banks = sorted(((lk * cs + 2 * ty * rs + 4 * tx + wd) % 64) for lk in range(2) for ty in range(4) for tx in range(4) for wd in range(2))
     assert banks == list(range(64)), 'a half-wave (16 windows x 2 channels) of one ds_read_b64 takes every bank once'
     text = kernel_text(asm, name)
+    assert not [op for _, op, _ in text if re.match(r'v_pk_(mul|add|fma)_f32', op)]
     assert not [op for _, op, _ in text if op.startswith('scratch_')]
     ls = loops(text)
     assert ls, 'no loop found: the disassembly format changed?'
@@ -49,7 +52,7 @@ def test_resources(code_object, name):
 
 @pytest.mark.parametrize('name', KERNELS)
 def test_matrix_instruction_count(code_object, name):
-    """Static count per k-loop, four k-steps per iteration.  Every loop of k_cost_net_w24 (tests/test_cost_f24_cpu.py) and, once each:
+    """Static count per k-loop, four k-steps per iteration.  Every loop of W24_LOOPS (tests/test_cost_f24_cpu.py) and, once each:
     * layer 1 on F(2x4) tiles (one runtime loop over the three planes around one round): four pass loops of 6 x 2 x 4 = 48;
     * layer 3's F(2x4) round: four pass loops of 48;
     * layer 3's F(2x2) tail (a pair over the one M-tile of tile rows 4, 5): four loops of 4 x 2 x 4 = 32."""
@@ -75,6 +78,21 @@ def test_the_f24_pass_loops(code_object, name):
         if sum(1 for o in ops if o.startswith('v_mfma')) == 48 and ops.count('ds_read_b64') == 24:
             hit.append(sum(1 for o in ops if o.startswith('v_accvgpr')))
     assert hit == [0] * 16, hit
+
+
+def test_one_kernel_pair_and_one_launch_path(code_object):
+    """The fp32 cost net is one kernel and its masked twin: beside them only the split form's kernels (k_cost_net_h3...) begin with
+    k_cost_net in the gfx950 code object.  Their host side is plain functions over one parameter struct: nothing in the cost-net half of
+    csrc/cnn_launch.hip is a template."""
+    asm, _ = code_object
+    names = {s[:int(n)] for n, s in re.findall(r'^[0-9a-f]+ <_Z(\d+)(k_cost_net\w*)>:$', asm, flags=re.M)}      # _Z<length><name><arguments>
+    print(sorted(names))
+    assert {n for n in names if not n.startswith('k_cost_net_h3')} == set(KERNELS)
+    assert any(n.startswith('k_cost_net_h3') for n in names), 'the split form went missing: the pattern no longer finds kernels?'
+    launch = open(os.path.join(ROOT, 'buffer_amd', 'csrc', 'cnn_launch.hip')).read()
+    head, mark, cost = launch.partition('// ---- cost net ----')
+    assert mark and 'cost_net_launch' in cost and 'buf_cost_volume_net_w24b_gather' in cost
+    assert 'template' not in cost
 
 
 def test_issued_count_per_match():

@@ -1,4 +1,4 @@
-"""k_cost_net_w24b (csrc/costnet_w24b.hip: layer 1 on F(2x4) tiles, one k' plane resident at a time; layer 3 as F(2x4) rows with an F(2x2)
+"""The forms of csrc/costnet_w24b.hip (layer 1 on F(2x4) tiles, one k' plane resident at a time; layer 3 as F(2x4) rows with an F(2x2)
 tail) on the GPU: the released weights against library convolutions, fixture F5 and the network in float64; synthetic weights and inputs
 that make a wrong plane, tap, tile origin, seam or a bias added per plane an error of order one; and the bit-for-bit properties of the
 entry points.  m = 1, 3 and 70 matches.
@@ -38,7 +38,7 @@ def maps(dev):
 
 
 def check_forms(layers, a, b, dev, forms, what):
-    """every form of `forms` and 'off' (k_cost_net_w24) against float64; prints the figures, then asserts the bound for the new forms"""
+    """every form of `forms` and 'off' (f24 = 'all' alone) against float64; prints the figures, then asserts the bound for the new forms"""
     from buffer_amd import ops
     ref = ind64(layers, a, b)
     spread = float(ref.std()) if ref.numel() > 1 else 0.0
@@ -51,7 +51,7 @@ def check_forms(layers, a, b, dev, forms, what):
 
 def test_released_weights(W, dev, maps):
     """Every part alone and both: against library convolutions and fixture F5 at the fp32 kernel's tolerance, against float64 below 1e-4
-    (printed beside k_cost_net_w24's figure on the same input)."""
+    (printed beside the figure of f24b = 'off' on the same input)."""
     from buffer_amd import registration
     f = np.load(os.path.join(GOLD, 'match_tiny.npz'), allow_pickle=False)
     se = torch.from_numpy(f['src_equi'])[f['s_mids']][:, :, 1:6].contiguous().to(dev)
@@ -67,7 +67,7 @@ def test_released_weights(W, dev, maps):
         cv = registration.CostVolume(W, dev, f24b=part)
         got_g, got_r = cv(se, te), cv(a, b)
         eg, er = float((got_g.double() - ref_g).abs().max()), float((got_r.double() - ref_r).abs().max())
-        print(f'released weights, {part}: max |ind - ind64| = {eg:.2e} (golden matches), {er:.2e} (random maps); k_cost_net_w24 on both: {e_off:.2e}')
+        print(f'released weights, {part}: max |ind - ind64| = {eg:.2e} (golden matches), {er:.2e} (random maps); with f24b off on both: {e_off:.2e}')
         np.testing.assert_allclose(got_g.cpu().numpy(), want_g, rtol=1e-4, atol=2e-4)
         np.testing.assert_allclose(got_g.cpu().numpy(), f['ind'], rtol=1e-4, atol=2e-4)
         np.testing.assert_allclose(got_r.cpu().numpy(), want_r, rtol=1e-4, atol=2e-4)
@@ -185,7 +185,7 @@ def test_large_positive_inputs(dev, maps, layer):
 def test_bit_for_bit(W, dev, maps):
     """The gather form equals the dense form; a permuted batch gives the permuted result; m = 1 and m = 3 are the first rows of m = 70; the
     masked re-run equals the plain call on the flagged matches and leaves the others untouched; f24b = 'off' is f24 = 'all'
-    (k_cost_net_w24), and k_cost_net_w24b without the two sets returns the same bits; no matches: an empty tensor."""
+    (the entry point of three sets), and the entry point of five sets without the last two returns the same bits; no matches: an empty tensor."""
     from buffer_amd import _lib, registration
     from buffer_amd.ops import _ptr, _stream
     a, b = maps
@@ -213,7 +213,7 @@ def test_bit_for_bit(W, dev, maps):
     out = torch.empty((70,), dtype=torch.float32, device=dev)
     assert _lib.lib().buf_cost_volume_net_w24b(_ptr(a), _ptr(b), 70, net._wp, net._bp, five, _ptr(out), _stream()) == 0
     assert torch.equal(out, want_old)
-    # the masked re-run: matches beyond the f16 range go through k_cost_net_w24b_rerun
+    # the masked re-run: matches beyond the f16 range go through the masked twin by buf_cost_volume_net_split_safe_w24b
     for part in ('all', 'l1'):
         cv32 = registration.CostVolume(W, dev, f24b=part)
         cvs = registration.CostVolume(W, dev, arith='split', f24b=part)

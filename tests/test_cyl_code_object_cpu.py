@@ -4,8 +4,8 @@
 * k_cyl_net_wg / k_cyl_net_wg_rerun: no scratch, at most 256 registers of both kinds together (two workgroups per CU), no static LDS
   beside the 80 KB dynamic buffer, no ds_read2_b64 inside a loop, and 38 = 16 + 16 + 6 matrix instructions per (k-step, N-tile) in
   every layer form.
-* k_cost_net shares wg_pass / wg_round with it and must compile to what it was: its static MFMA count and its register and scratch
-  figures are constants read off a build of the commit before the change.
+* the cost net's kernel (k_cost_net_w24b) shares wg_pass / wg_round with it and must compile to what it was: its static MFMA count and
+  its register and scratch figures are constants read off a build of the commit before the change.
 """
 import os
 import re
@@ -17,10 +17,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = '/opt/rocm/lib/llvm/bin'
 
-# k_cost_net and k_cost_net_rerun in a build of the parent commit (same compiler flags: buffer_amd/build.py)
+# The cost net's kernel pair (csrc/costnet_body.hip: one body for every layer form) in a build of the commit before the two smaller pairs
+# were retired (same compiler flags: buffer_amd/build.py; profiles/cost_one_body.md).  mfma: 2 576 in the k-loops + 384 outside.
 PARENT_COST_NET = {
-    'k_cost_net': dict(mfma=1936, vgpr=190, agpr=0, scratch=0, sgpr=83),
-    'k_cost_net_rerun': dict(mfma=1936, vgpr=190, agpr=0, scratch=0, sgpr=83),
+    'k_cost_net_w24b': dict(mfma=2960, vgpr=212, agpr=0, scratch=0, sgpr=90),
+    'k_cost_net_w24b_rerun': dict(mfma=2960, vgpr=212, agpr=0, scratch=0, sgpr=92),
 }
 
 

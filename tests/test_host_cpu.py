@@ -464,7 +464,7 @@ def test_traffic_summary_keeps_full_step_launches_only(tmp_path):
                         counter, per_patch_kb * 64, 0, 1])
             for k in range(3):                                  # a kernel whose launches legitimately differ in size: all kept
                 d += 1
-                w.writerow([d, d, "Agent 2", 1, 1, 1, (k + 1) * 1024, 9, "k_cost_net(float const*, float const*, CostNetParams, float*)", 256, 0, 0, 128,
+                w.writerow([d, d, "Agent 2", 1, 1, 1, (k + 1) * 1024, 9, "k_cost_net_w24b(float const*, float const*, CostNetParams, float*)", 256, 0, 0, 128,
                             128, 32, counter, 10.0 * (k + 1), 0, 1])
     write(tmp_path / 'fetch.csv', 'FETCH_SIZE', 14.0)          # KB per patch (the raw counter; doubled by the tool)
     write(tmp_path / 'write.csv', 'WRITE_SIZE', 17.5)
@@ -480,6 +480,7 @@ def test_traffic_summary_keeps_full_step_launches_only(tmp_path):
     assert k['launches_profiled'] == 5 and k['launches_dropped'] == 1
     assert abs(k['hbm_bytes_per_unit'] - (2 * 14.0 + 17.5) * 1024) < 1e-6          # not diluted by the probe launch
     assert t['k_cost_net']['launches_profiled'] == 3 and t['k_cost_net']['launches_dropped'] == 0
+    assert t['k_cost_net'] == dict(t['k_cost_net_w24b'], measured_on='k_cost_net_w24b')      # (bench.py looks the cost net up as k_cost_net)
 
 
 def test_bench_last_step_poses_follow_the_job_s_pair_order():

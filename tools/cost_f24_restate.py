@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The cost net restated on the CPU in float32 with the arithmetic of k_cost_net_w24 (csrc/costnet_w24.hip): F(2x4, 3x3) tiles in layers 2
+"""The cost net restated on the CPU in float32 with the arithmetic of the layer forms of csrc/costnet_w24.hip: F(2x4, 3x3) tiles in layers 2
 and 4 -- the last tile column's window fed from the first two words of the NEXT map row (zeros behind the last row), as the kernel reads
-them -- and the Winograd F(2x2) form in layer 6, beside the parent's order (k_cost_net: F(2x2) in layers 1..5, layer 6 direct).  Both
+them -- and the Winograd F(2x2) form in layer 6, beside the parent's order (the first forms: F(2x2) in layers 1..5, layer 6 direct).  Both
 against the network in float64, on the matches of tests/golden/match_tiny.npz and on 70 random normalised maps (seed 1, as in
 tests/test_model_gpu.py::test_fused_cost_volume_vs_library_convs):
 
@@ -48,7 +48,7 @@ def conv_f22(x, w, b):
 
 
 def conv_f24(x, w, b):
-    """F(2x4, 3x3) in float32 over the flat channel-major map as k_cost_net_w24 reads it: x [C, H, W] (H even) -> [O, H - 2, W - 2].  The
+    """F(2x4, 3x3) in float32 over the flat channel-major map as cw24_layer reads it: x [C, H, W] (H even) -> [O, H - 2, W - 2].  The
     window of tile (ty, tx) is 4 rows x 6 words from column 4 tx; words past the row's end are the next row's first ones (zeros behind the
     last row) and only meet output columns >= W - 2, which are dropped."""
     c, h, wd = x.shape
@@ -74,7 +74,7 @@ def cost_volume(s, t, dt):
 
 
 def ind_of(s, t, layers, form):
-    """one match; form: 'f64' (the network in float64), 'parent' (k_cost_net's forms in float32), 'new' (k_cost_net_w24's), or a tuple of
+    """one match; form: 'f64' (the network in float64), 'parent' (the first forms in float32), 'new' (those of csrc/costnet_w24.hip), or a tuple of
     the layers (2, 4, 6) that take the new form"""
     dt = np.float64 if form == 'f64' else f32
     new = {'f64': (), 'parent': (), 'new': (2, 4, 6)}.get(form, form)

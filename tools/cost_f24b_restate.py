@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The two forms of k_cost_net_w24b (csrc/costnet_w24b.hip) restated on the CPU in float32, beside those of tools/cost_f24_restate.py:
+"""The two layer forms of csrc/costnet_w24b.hip restated on the CPU in float32, beside those of tools/cost_f24_restate.py:
 
 * layer 1 on F(2x4) tiles in the kernel's summation order: one k' plane (32 of the 96 collapsed input channels) at a time; inside a plane
   each of the four row-component passes starts from cleared accumulators (the bias in column component 1 of pass 1 of plane 0), A4^T is
@@ -13,7 +13,7 @@
 
     python tools/cost_f24b_restate.py
 
-prints max |ind - ind64| against the network in float64 for 'all', 'l1', 'l3' and for the parent's forms (k_cost_net_w24: 'off'), on the 40
+prints max |ind - ind64| against the network in float64 for 'all', 'l1', 'l3' and for the parent's forms (those of csrc/costnet_w24.hip: 'off'), on the 40
 matches of tests/golden/match_tiny.npz and on 70 random normalised maps (seed 1), released weights.  The kernel's tests bound it by 1e-4
 (ind in [0, 20)).  As in the sibling, numpy sums a K range in its own order: the figure is the size of the rounding error, not a bit
 pattern."""
@@ -93,7 +93,7 @@ def conv_l3_hybrid(x, w, b):
 
 
 def ind_of(s, t, layers, form):
-    """one match; form: 'f64', 'off' (k_cost_net_w24's forms), 'all', 'l1', 'l3', 'l1-running'"""
+    """one match; form: 'f64', 'off' (the forms of csrc/costnet_w24.hip), 'all', 'l1', 'l3', 'l1-running'"""
     if form == 'f64':
         return r.ind_of(s, t, layers, 'f64')
     mine = {'off': (), 'all': (1, 3), 'l1': (1,), 'l3': (3,), 'l1-running': (1,)}[form]

@@ -38,10 +38,9 @@ for k in ('k_patch_voxelize', 'k_cyl_net_wg', 'k_cyl_net_w24k', 'k_cyl_net_w25t'
 # the cost net, per match (one workgroup per match; matches per launch from the work figure of its timed span, as in make_traffic.py)
 cost = [o for o in bench.get('roofline_other', []) if o and o['kernel'].startswith('k_cost_net')]
 matches = cost[0]['avg_algorithmic_flops'] / 51905536.0 if cost else None
-for k in ('k_cost_net', 'k_cost_net_w24', 'k_cost_net_w24b'):
-    d = list(rows.get(k, {}).values())
-    if not d or not matches:
-        continue
+d = list(rows.get('k_cost_net_w24b', {}).values())
+if d and matches:
+    k = 'k_cost_net_w24b'
     g = max(x['grid'] for x in d)
     d = [x for x in d if x['grid'] == g]
     kernels[k] = {'launches': len(d), 'matches_per_launch': matches}
@@ -51,7 +50,7 @@ for k in ('k_cost_net', 'k_cost_net_w24', 'k_cost_net_w24b'):
 lib = ctypes.CDLL(os.path.join(ROOT, 'buffer_amd', 'libbuffer_hip.so'))
 src = {f: hashlib.sha256(open(os.path.join(ROOT, 'buffer_amd', 'csrc', f), 'rb').read()).hexdigest()[:16]
        for f in ('voxelize.hip', 'convnet_wg.hip', 'convnet_w24.hip', 'convnet_w24k.hip', 'convnet_w24p.hip', 'convnet_w24a.hip', 'convnet_w25.hip', 'convnet_w25t.hip', 'convnet_h3.hip',
-                 'costnet.hip', 'costnet_w24.hip', 'costnet_w24b.hip')}
+                 'costnet.hip', 'costnet_w24.hip', 'costnet_w24b.hip', 'costnet_body.hip')}
 json.dump(dict(source='rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVES on the bench.py command of the line in `bench` '
                       '(wave-level instruction counts; SQ_INSTS_VALU includes the MFMAs)',
                lib_version=int(lib.buf_version()), csrc_sha256_16=src, bench=dict(value=bench['value'], config=cfg), kernels=kernels),

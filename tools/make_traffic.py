@@ -73,8 +73,6 @@ units = {
     'k_desc_head': (patches, 'patch', 2 * 32 * 140 * 4 + 128),
     'k_patch_voxelize': (patches, 'patch', 12 * 512 + 4 * 16 * 420),
     'k_select_patches_grid': (patches, 'patch', 12 * 512 + 12),
-    'k_cost_net': (matches, 'match', 2 * 3200 * 4 + 4),
-    'k_cost_net_w24': (matches, 'match', 2 * 3200 * 4 + 4),
     'k_cost_net_w24b': (matches, 'match', 2 * 3200 * 4 + 4),
     'k_cyl_net_h3': (patches, 'patch', 48 * 140 * 4 + 32 * 140 * 4),
     'k_cost_net_h3': (matches, 'match', 2 * 3200 * 4 + 4),
@@ -93,10 +91,9 @@ for k, (u, unit, alg) in units.items():
     kernels[k] = dict(fetch_size_bytes_per_launch_raw=fetch[k], write_size_bytes_per_launch=write[k], hbm_bytes_per_launch=hbm,
                       launches_profiled=n_f[k], launches_dropped=dropped.get(k, 0), units_per_launch=u, unit=unit, hbm_bytes_per_unit=hbm / u,
                       algorithmic_bytes_per_unit=alg)
-# bench.py looks the cost net up as k_cost_net: when the profiled run went through k_cost_net_w24, its bytes are recorded under both names
-for twin in ('k_cost_net_w24b', 'k_cost_net_w24'):
-    if 'k_cost_net' not in kernels and twin in kernels:
-        kernels['k_cost_net'] = dict(kernels[twin], measured_on=twin)
+# bench.py looks the cost net up as k_cost_net: the bytes of its one fp32 kernel are recorded under both names
+if 'k_cost_net_w24b' in kernels:
+    kernels['k_cost_net'] = dict(kernels['k_cost_net_w24b'], measured_on='k_cost_net_w24b')
 json.dump(dict(source='rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on the bench.py command of '
                       'the line in `bench`; per-dispatch means over the full-step launches',
                correction='gfx950: FETCH_SIZE tallies 128-B requests at 64 B -> doubled (MI355X_MICROARCH.md, HBM); WRITE_SIZE as is; '
