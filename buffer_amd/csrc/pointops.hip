@@ -535,7 +535,8 @@ extern "C" int buf_permute_clouds(const float* const* clouds_host, const int* le
 __global__ void __launch_bounds__(SPB_WAVES * WAVE) k_select_patches_grid(const CellGrid* __restrict__ grids, const int* __restrict__ table,
                                                                       const float4* __restrict__ sorted, const float* __restrict__ pts,
                                                                       const int* __restrict__ s_off, const float* __restrict__ kpts, int m,
-                                                                      float r2, int nsample, int mask_words, float* __restrict__ patches)
+                                                                      float r2, int nsample, int mask_words, int force_path,
+                                                                      float* __restrict__ patches)
 {
     extern __shared__ unsigned long long spb_mask[];             // [SPB_WAVES][mask_words]
     // XCD-contiguous block order (common.h): the keypoints of one cloud go to ONE XCD, whose L2 then holds that cloud's
@@ -570,7 +571,9 @@ __global__ void __launch_bounds__(SPB_WAVES * WAVE) k_select_patches_grid(const 
     // Path choice (speed only).  Expected in-ball points ~ 0.4 * candidates on surface-like clouds; the ordered scan stops
     // after about keep / that * n indices at ~25 instructions per 64 indices, the grid path tests every candidate at ~35 per 64.
     const float in_ball = 0.4f * (float)total;
-    const bool grid_path = mask_words > 0 && (in_ball <= (float)keep || (float)keep / in_ball * (float)n * 25.f > (float)total * 35.f + 64.f * 300.f);
+    const bool by_speed = in_ball <= (float)keep || (float)keep / in_ball * (float)n * 25.f > (float)total * 35.f + 64.f * 300.f;
+    // force_path (wave-uniform; BUF_SPB_PATH, for tests): 1 = the mask for every query of a call that has one, 2 = the scan for every query
+    const bool grid_path = mask_words > 0 && (force_path == 0 ? by_speed : force_path == 1);
     if (grid_path) {
         unsigned long long* M = spb_mask + (size_t)w * mask_words;
         const int nw = (n + 63) >> 6;
@@ -677,10 +680,14 @@ extern "C" int buf_select_patches_batched(const float* pts, const int* lengths_h
     static LdsGrant grant;
     if (lds > 48 * 1024)
         if (int rc2 = grant_dynamic_lds((const void*)k_select_patches_grid, lds, grant)) return rc2;
+    // development switch, read on every call (tests/test_patch_select_gpu.py): BUF_SPB_PATH=grid | scan takes every query of the call down
+    // the bitmask path (where the call has a mask) or the ordered scan; anything else leaves the choice to the kernel's speed heuristic
+    int force_path = 0;
+    { const char* e_ = getenv("BUF_SPB_PATH"); if (e_) force_path = !strcmp(e_, "grid") ? 1 : (!strcmp(e_, "scan") ? 2 : 0); }
     TimedSpan span;
     bool timed = timing_begin(s, &span, 12.0 * ntot + (12.0 + 12.0 * nsample) * (double)nc * m, BUF_TIMED_SELECT_PATCHES);
     k_select_patches_grid<<<dim3(cdiv(m, SPB_WAVES), nc), SPB_WAVES * WAVE, lds, s>>>((const CellGrid*)g.desc, g.table, (const float4*)g.sorted, pts,
-                                                                                 g.s_off, kpts, m, radius * radius, nsample, mask_words, patches);
+                                                                                 g.s_off, kpts, m, radius * radius, nsample, mask_words, force_path, patches);
     if (timed) timing_end(s, &span);
     BUF_LAUNCH_CHECK();
     return BUF_OK;

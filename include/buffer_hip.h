@@ -190,7 +190,10 @@ int     buf_select_patches(const float* pts, const float* kpts, int n, int m, fl
 /* The same (models/patch_embedder.py:93-121) for every cloud of a step in one launch: pts f32[sum n_c,3] = the (already permuted) support clouds stacked,
  * lengths_host int[nc], kpts f32[nc*m,3] (m keypoints per cloud) -> patches f32[nc*m,nsample,3].  Builds an A2 cell grid
  * over the stacked clouds in `ws` and walks a per-query bitmask of in-ball points in index order (identical results to
- * buf_select_patches cloud by cloud). */
+ * buf_select_patches cloud by cloud).  Per query the kernel takes the bitmask or the index-ordered scan, whichever its candidate
+ * count makes faster; the development switch BUF_SPB_PATH (environment, read on every call) overrides that for every query of the
+ * call: `grid` = the bitmask wherever the call has one (clouds up to 131 072 points), `scan` = the ordered scan, anything else or
+ * unset = the kernel's own choice.  The result does not depend on it (tests/test_patch_select_gpu.py runs all three). */
 size_t  buf_select_patches_batched_ws_bytes(int n_total, int nc);
 int     buf_select_patches_batched(const float* pts, const int* lengths_host, int nc, const float* kpts, int m, float radius,
                                    int nsample, float* patches, void* ws, size_t ws_bytes, void* stream);
